@@ -12,7 +12,12 @@ Workload at N=1: descr/trna.descr (4-stem cloverleaf, bits()+efn() score) over t
 synthetic FASTA of BASELINE.md (100 records x 1 Mbase, iid uniform acgt, numpy default_rng(20240601))
 -- BASELINE config 2.  `value` is that, over exactly --steps steps.
 
-Next to it, on rank 0 at N=1 with the default workload (none of it inside the timed K steps):
+A plain run sets up, warms up, times the --steps steps and prints the line; with --dump-outputs DIR it
+also writes the hit records of the last timed step, one DIR/hits_<descriptor>.npy per descriptor
+(float64, int32 words exactly; the inputs are the same from run to run).  Everything below, the
+roofline and the kernel times included, is measured only under --full.
+
+Next to it under --full, on rank 0 at N=1 with the default workload (none of it inside the timed K steps):
   h2d_inclusive    the same step with the upload of its batch inside
   real_db          the reference's own test database x 44 (100 Mbase in 179 k short entries): trna / pk1 / mp.ends,
                    kernel ms as short entries and as the same bases in long entries, candidates cross-checked
@@ -228,6 +233,35 @@ def cli_end_to_end(descr_path, seqs, tmp, threads_env=None):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, descr_files, records, strides):
+    """--dump-outputs: the hit records of the last timed step, DIR/hits_<descriptor>.npy per descriptor, as float64
+    (every int32 word exactly).  Where they would pass 64 MB in all, a fixed seeded sample of the records, in order."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = []
+    for r, stride in zip(records, strides):
+        if isinstance(r, list):         # (torch.distributed gather: the per-rank parts in rank order)
+            r = np.concatenate(r, axis=0) if r else None
+        arrays.append(np.zeros((0, stride), dtype=np.int32) if r is None else r)
+    total = sum(a.size * 8 for a in arrays)
+    budget = DUMP_BYTES - 4096 * len(arrays)        # (room for the .npy headers)
+    rng = np.random.default_rng(SEED)
+    names = []
+    for i, (f, a) in enumerate(zip(descr_files, arrays)):
+        stem = os.path.basename(f)
+        stem = stem[: -len(".descr")] if stem.endswith(".descr") else stem
+        name = "hits_" + stem if ("hits_" + stem) not in names else "hits_%d_%s" % (i, stem)
+        names.append(name)
+        if total > budget and a.shape[0] > 0:
+            keep = int(a.shape[0] * budget / total)
+            a = a[np.sort(rng.choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(np.float64))
+    return names
+
+
 REAL_DB = os.path.join(ROOT, "tests", "golden", "test", "gbrna.111.0.fastn.gz")
 REAL_DB_COPIES = 44
 # candidates (before the score program) of one copy of the reference's test database: the oracle's counts, which
@@ -298,7 +332,14 @@ def main():
     ap.add_argument("--gather", choices=("native", "torch"), default="native", help="N > 1: rma_gather_hits (RCCL behind the C ABI) or torch.distributed")
     ap.add_argument("--backend", default=os.environ.get("RNAMOTIF_DIST_BACKEND", "nccl"),
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo: tests with several ranks on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, kernel times and the legs beside the headline (CPU baselines, north star, "
+                         "command line, real database); a plain run times the steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the hit records of the last timed step to DIR/hits_<descriptor>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # `value` is measured with the inputs already in HBM when the timed region starts (the round's measurement rule); the
     # PCIe-inclusive step of SURVEY.md 8d stands beside it as `h2d_inclusive` (and is `value` only under --h2d)
     args.resident = not args.h2d
@@ -309,7 +350,7 @@ def main():
         args.total_records = 1000           # BASELINE config 4 / 5: 1 Gbase divided among the ranks
     default_workload = (args.descr == ap.get_default("descr") and args.records == 100 and
                         args.record_len == 1_000_000 and args.total_records == 0 and args.resident)
-    extras = world_env == 1 and args.cpu_bases > 0 and "," not in args.descr
+    extras = args.full and world_env == 1 and args.cpu_bases > 0 and "," not in args.descr
     strong = args.total_records > 0
     if strong:
         per = -(-args.total_records // world_env)
@@ -400,21 +441,25 @@ def main():
         for s_ in sets[k]:
             s_.scan_begin(db)
 
+    last = [None] * len(descrs)         # the records of the step ended last, per descriptor (for --dump-outputs)
+
     def scan_end(k=0):
         """Energies, ordering, the records of all descriptors on rank 0; their number."""
         n = 0
-        for d_, s_ in zip(descrs, sets[k]):
+        for i, (d_, s_) in enumerate(zip(descrs, sets[k])):
             if world == 1:
-                n += s_.scan_end(copy=False).shape[0]
+                # (a view of the scanner's buffer, valid until that scanner's next scan)
+                last[i] = s_.scan_end(copy=False)
+                n += last[i].shape[0]
             elif native is not None:
                 s_.scan_end_on_device()
-                h, _ = native.gather(s_, my_index)
-                n += h.shape[0]
+                last[i], _ = native.gather(s_, my_index)
+                n += last[i].shape[0]
             else:
                 # every rank holds a consecutive run of entries: the per-rank arrays in rank order are the
                 # ordered hit stream of the whole job, left as they arrive (no concatenation on rank 0)
-                n += sum(part.shape[0] for part in torch_gather(s_.scan_end(copy=False), my_index, d_.hit_stride,
-                                                                device=coll_dev, concat=False))
+                last[i] = torch_gather(s_.scan_end(copy=False), my_index, d_.hit_stride, device=coll_dev, concat=False)
+                n += sum(part.shape[0] for part in last[i])
         return n
 
     state = {"cur": new_db(True)}
@@ -481,8 +526,10 @@ def main():
         job_bases = int(tb.item())
     else:
         job_bases = db.bases
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, descr_files, last, [d.hit_stride for d in descrs])
 
-    # kernel time of the dominant kernel, HIP events on the scanner's own stream; then the pre-filter alone
+    # (--full) kernel time of the dominant kernel, HIP events on the scanner's own stream; then the pre-filter alone
     parts = {"rma_search_kernel": [], "rma_drain_kernel": []}
 
     def kernel_ms(reps=5, keep_parts=False):
@@ -504,10 +551,10 @@ def main():
                 parts["rma_drain_kernel"].append(p1)
         return float(np.mean(s_tot)), float(np.mean(e_tot))
 
-    search_ms, efn_ms = kernel_ms(keep_parts=True)
-    drain_ms = float(np.mean(parts["rma_drain_kernel"]))
+    search_ms, efn_ms = kernel_ms(keep_parts=True) if args.full else (None, None)
+    drain_ms = float(np.mean(parts["rma_drain_kernel"])) if args.full else None
     pass_a_ms = None
-    if rank == 0 and world == 1 and args.cpu_bases > 0:       # (not under the profiler: profiles/collect.sh passes --cpu-bases 0,
+    if args.full and rank == 0 and world == 1 and args.cpu_bases > 0:       # (not under the profiler: profiles/collect.sh passes --cpu-bases 0,
         # so that every launch of the kernel it counts is a whole one)
         for s_ in scs:
             s_.set_option("dbg", 1)
@@ -526,7 +573,7 @@ def main():
     # what RCCL itself says the job is (ncclCommCount of the native gather's communicator), and every rank's kernel time
     rccl_ranks = native.comm_count() if native is not None else None
     per_rank_kernel_ms = None
-    if world > 1:
+    if args.full and world > 1:
         t = torch.zeros(world, dtype=torch.float64, device=coll_dev)
         t[rank] = search_ms
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -538,9 +585,9 @@ def main():
         ms_per_step = dt / args.steps * 1e3
         value = total_bases / (dt / args.steps) / 1e6
         algo_bytes = ALGO_BYTES_PER_BASE * bases_per_gpu * len(descrs)
-        achieved = algo_bytes / (search_ms * 1e-3) / 1e9
+        achieved = algo_bytes / (search_ms * 1e-3) / 1e9 if args.full else None
         names = "+".join(os.path.basename(f) for f in descr_files)
-        counters = profile_counters() if default_workload and world == 1 else None
+        counters = profile_counters() if args.full and default_workload and world == 1 else None
         traffic = None
         secondary = None
         if counters and "FETCH_SIZE" in counters and "WRITE_SIZE" in counters:
@@ -592,7 +639,9 @@ def main():
                 "candidates": total_hits,
                 "parallelism": f"{world} rank(s), sequences sharded, gather of hit records: {gather_kind}" if world > 1 else "1 GPU",
             },
-            "roofline": {
+        }
+        if args.full:
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "rma_search_kernel + rma_drain_kernel" if drain_ms > 0 else "rma_search_kernel",
                 "kernel_parts_ms": {k: round(float(np.mean(v)), 3) for k, v in parts.items()},
@@ -616,8 +665,7 @@ def main():
                         "search kernel's filters let through), HIP events on the scanner's stream; pass A = "
                         "pre-filter (decode, bit rows, first-pairs test, queue), pass B = the search proper; "
                         "kernel-only rate = %.1f Mbases/s" % (bases_per_gpu * len(descrs) / (search_ms * 1e-3) / 1e6),
-            },
-        }
+            }
 
     if rank == 0 and extras:
         def timed(fn, min_steps, min_s):

@@ -11,8 +11,8 @@ O=$R/gpurun_out/prof_$1
 shift
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 1 --warmup 0 --cpu-bases 0 $*"
-python3 $R/bench.py --cpu-bases 0 $* > $O/bench_plain.log 2>&1
+B="$R/bench.py --full --steps 1 --warmup 0 --cpu-bases 0 $*"
+python3 $R/bench.py --full --cpu-bases 0 $* > $O/bench_plain.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- python3 $B > $O/bench_trace.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch --output-format csv -- python3 $B > $O/bench_fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write --output-format csv -- python3 $B > $O/bench_write.log 2>&1

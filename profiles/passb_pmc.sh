@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/passb
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 1 --warmup 0 --cpu-bases 0 --north-star-records 0 $*"
+B="$R/bench.py --full --steps 1 --warmup 0 --cpu-bases 0 --north-star-records 0 $*"
 for v in 0 1; do
 	if [ $v = 1 ]; then export RNAMOTIF_DBG=1; fi
 	timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $O/a$v --output-format csv -- python3 $B > $O/a$v.log 2>&1

@@ -1,6 +1,7 @@
 """CPU: efn2() -- the product's table loader (rma_efn2data_load) and the oracle's restatement
 of RM_efn2 (oracle/rm_oracle_efn2.c) against the reference's own efn2_drv (oracle/_ref/efn2_drv,
-built from /root/reference/src/efn2.c as it lies) on random nested structures: hairpins,
+built from the reference's efn2.c as it lies; its energies pinned in tests/golden/ref_pins.json,
+tests/ref_pins.py) on random nested structures: hairpins,
 bulges, interior loops of every special size, multi-branch loops with coaxial stacking."""
 import ctypes as C
 import os
@@ -9,6 +10,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from ref_pins import md5, pinned
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EFN2_DRV = os.path.join(ROOT, "oracle", "_ref", "efn2_drv")
@@ -53,11 +56,20 @@ def _ct(seq, pairs):
     return "\n".join(lines) + "\n"
 
 
-def _reference(cts):
-    p = subprocess.run([EFN2_DRV], input="".join(cts).encode(), env=dict(os.environ, EFNDATA=EFNDATA),
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+def _efn2_drv(data, timeout=120):
+    """efn2_drv's energies (1/100 kcal/mol) for the structures of `data` (.ct text)."""
+    p = subprocess.run([EFN2_DRV], input=data, env=dict(os.environ, EFNDATA=EFNDATA, LC_ALL="C"),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     assert p.returncode == 0, p.stderr.decode()
     return [int(round(float(m) * 100)) for m in re.findall(r"dG =\s*(-?[0-9.]+)", p.stdout.decode())]
+
+
+def _reference(what, cts):
+    """_efn2_drv over the structures `cts`, pinned as `what`."""
+    data = "".join(cts).encode()
+    pin = pinned("efn2_drv dG, " + what, lambda: {"input": md5(data), "dG": _efn2_drv(data)})
+    assert pin["input"] == md5(data), "not the structures the pin %r was made from" % what
+    return pin["dG"]
 
 
 def _closed_structure(rng, n):
@@ -114,11 +126,10 @@ def test_known_answers(efn2):
     assert _oracle(efn2, "ggggaaaacccc", [(0, 11), (1, 10), (2, 9), (3, 8)]) == (-540, 0)
 
 
-@pytest.mark.skipif(not os.path.exists(EFN2_DRV), reason="oracle/_ref/efn2_drv not built (no /root/reference)")
 def test_random_closed_structures_match_efn2_drv(efn2):
     rng = np.random.default_rng(20240602)
     cases = [_closed_structure(rng, int(rng.integers(9, 120))) for _ in range(400)]
-    want = _reference([_ct(s, p) for s, p in cases])
+    want = _reference("closed structures of default_rng(20240602)", [_ct(s, p) for s, p in cases])
     assert len(want) == len(cases)
     kinds = 0
     for (s, p), w in zip(cases, want):
@@ -132,21 +143,19 @@ def test_random_closed_structures_match_efn2_drv(efn2):
     assert kinds > 300
 
 
-@pytest.mark.skipif(not os.path.exists(EFN2_DRV), reason="oracle/_ref/efn2_drv not built (no /root/reference)")
 def test_exterior_loop_where_defined_and_flagged_where_not(efn2):
     helix = [(1, 12), (2, 11), (3, 10), (4, 9)]
     e, und = _oracle(efn2, "aggggaaaacccca", helix)          # exterior helix starts at base 2: defined
-    assert und == 0 and [e] == _reference([_ct("aggggaaaacccca", helix)])
+    assert und == 0 and [e] == _reference("aggggaaaacccca", [_ct("aggggaaaacccca", helix)])
     two = [(1, 9), (2, 8), (3, 7), (10, 18), (11, 17), (12, 16)]  # second helix flush against the first
     s = "agggaaacccgggaaaccca"
     e, und = _oracle(efn2, s, two)
-    assert und == 0 and [e] == _reference([_ct(s, two)])
+    assert und == 0 and [e] == _reference(s, [_ct(s, two)])
     # a helix further in: the reference reads rm_basepr[1] == -1 as a partner (efn2.c:1337-1345)
     e, und = _oracle(efn2, "aaggggaaaaccccaa", [(2, 13), (3, 12), (4, 11), (5, 10)])
     assert und == 1 and e == 9999999
 
 
-@pytest.mark.skipif(not os.path.exists(EFN2_DRV), reason="oracle/_ref/efn2_drv not built (no /root/reference)")
 def test_efn2_scores_of_a_search_equal_efn2_drv_on_the_hits(built, workdir):
     """End to end on the CPU: the score column efn2() produces for every hit of a hairpin search
     equals what the reference's pipeline `rnamotif | rm2ct | efn2_drv` gives for the same hits."""
@@ -160,8 +169,14 @@ def test_efn2_scores_of_a_search_equal_efn2_drv_on_the_hits(built, workdir):
     scores = [int(round(float(l.split()[1]) * 100)) for l in lines]
     ct = subprocess.run([os.path.join(ROOT, "rnamotif_amd", "bin", "rm2ct")], input=p.stdout, stdout=subprocess.PIPE,
                         timeout=300).stdout
-    q = subprocess.run([EFN2_DRV], input=ct, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    want = [int(round(float(m) * 100)) for m in re.findall(r"dG =\s*(-?[0-9.]+)", q.stdout.decode())]
-    assert len(want) == len(scores)
+
+    def run_ref():
+        want = _efn2_drv(ct, timeout=600)
+        return {"input": md5(ct), "n": len(want), "dG": md5(" ".join(map(str, want)).encode())}
+
+    # (the hits' energies pinned by their number and the md5 of their list)
+    pin = pinned("efn2_drv dG, hairpin.efn2.descr -N 400 over gbrna.111.0.fastn, through rm2ct", run_ref)
+    assert md5(ct) == pin["input"]
+    assert len(scores) == pin["n"]
     # %8.3f of a float holding 0.01*e against %5.2f of a double: equal to the cent
-    assert scores == want
+    assert md5(" ".join(map(str, scores)).encode()) == pin["dG"]

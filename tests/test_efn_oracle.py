@@ -1,12 +1,15 @@
 """CPU: the oracle's energy function against the reference's own efn_drv
-(oracle/_ref/efn_drv, built from /root/reference/src/efn.c as it lies) on
-random nested structures, and against the known answer of SURVEY.md 8c."""
+(oracle/_ref/efn_drv, built from the reference's efn.c as it lies; its energies pinned in
+tests/golden/ref_pins.json, tests/ref_pins.py) on random nested structures, and against the
+known answer of SURVEY.md 8c."""
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 import pytest
+
+from ref_pins import md5, pinned
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EFN_DRV = os.path.join(ROOT, "oracle", "_ref", "efn_drv")
@@ -79,22 +82,30 @@ def test_known_answer(efn):
     assert _oracle_efn(lib, ed, "gaaac", [(0, 4)]) == 570          # energy = 5.700
 
 
-@pytest.mark.skipif(not os.path.exists(EFN_DRV), reason="oracle/_ref/efn_drv not built (no /root/reference)")
 def test_against_reference_efn_drv(efn, tmp_path):
     lib, ed = efn
     rng = np.random.default_rng(5)
-    env = dict(os.environ, EFNDATA=EFNDATA)
+    cases = [c for c in (_random_structure(rng, int(rng.integers(12, 120))) for t in range(300)) if c[1]]
+    cases_md5 = md5("".join(_ct(s, p) for s, p in cases).encode())
+
+    def run_ref():
+        env = dict(os.environ, EFNDATA=EFNDATA)
+        energies = []
+        for seq, pairs in cases:
+            f = tmp_path / "s.ct"
+            f.write_text(_ct(seq, pairs))
+            p = subprocess.run([EFN_DRV, str(f)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=60)
+            assert p.returncode == 0, p.stderr.decode()
+            line = [l for l in p.stdout.decode().splitlines() if l.startswith("energy")][0]
+            energies.append(float(line.split("=")[1]))
+        return {"input": cases_md5, "energy": energies}
+
+    pin = pinned("efn_drv energy, random structures of default_rng(5)", run_ref)
+    assert pin["input"] == cases_md5
+    wants = pin["energy"]
+    assert len(wants) == len(cases)
     checked = 0
-    for t in range(300):
-        seq, pairs = _random_structure(rng, int(rng.integers(12, 120)))
-        if not pairs:
-            continue
-        f = tmp_path / "s.ct"
-        f.write_text(_ct(seq, pairs))
-        p = subprocess.run([EFN_DRV, str(f)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=60)
-        assert p.returncode == 0, p.stderr.decode()
-        line = [l for l in p.stdout.decode().splitlines() if l.startswith("energy")][0]
-        want = float(line.split("=")[1])
+    for (seq, pairs), want in zip(cases, wants):
         got = _oracle_efn(lib, ed, seq, pairs)
         assert abs(0.01 * got - want) < 0.0051, (seq, pairs, got, want)
         checked += 1

@@ -3,7 +3,8 @@ printer) + the scalar oracle reproduce the reference's outputs byte for byte.
 
 Pins: md5 of raw stdout recorded from the reference's own objects
  and the reference's test/*.chk files (through the
-reference's own rmfmt when oracle/_ref holds it)."""
+reference's own rmfmt, oracle/_ref/rmfmt, whose outputs are pinned in
+tests/golden/ref_pins.json, tests/ref_pins.py)."""
 import hashlib
 import os
 import subprocess
@@ -11,6 +12,7 @@ import subprocess
 import pytest
 
 import pins
+from ref_pins import md5, pinned
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_RMFMT = os.path.join(ROOT, "oracle", "_ref", "rmfmt")
@@ -54,15 +56,20 @@ CHK = [(n, False) for n in ("nanlin", "pk1", "pk_j1+2", "qu+tr", "score.1", "sco
 CHK += [(n, True) for n, _ in CHK]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_RMFMT), reason="oracle/_ref/rmfmt not built (no /root/reference)")
 @pytest.mark.parametrize("name,strict", CHK, ids=[n + (".strict" if s else "") for n, s in CHK])
 def test_chk_files_through_reference_rmfmt(built, workdir, name, strict):
     """test/Makefile:34-37,139-245: rnamotif [-sh -context -Dctx_maxlen=5] -descr NAME[.strict].descr
     gbrna.111.0.fastn | rmfmt -l  must equal the reference's NAME[.strict].chk -- the vectors the
-    reference itself holds for this path, through the reference's own rmfmt."""
+    reference itself holds for this path, through the reference's own rmfmt (pinned: the search output
+    it was given, and what it printed)."""
     stem = name + (".strict" if strict else "")
     out, _ = _run(built, workdir, (pins.STRICT_ARGS if strict else []) + ["-descr", stem + ".descr"])
-    p = subprocess.run([REF_RMFMT, "-l"], input=out, cwd=workdir, stdout=subprocess.PIPE, timeout=300,
-                       env=dict(os.environ, LC_ALL="C"))
+
+    def run_ref():
+        p = subprocess.run([REF_RMFMT, "-l"], input=out, cwd=workdir, stdout=subprocess.PIPE, timeout=300,
+                           env=dict(os.environ, LC_ALL="C"))
+        return {"input": md5(out), "stdout": md5(p.stdout)}
+
+    pin = pinned("rmfmt -l, " + stem, run_ref)
     want = open(os.path.join(ROOT, "tests", "golden", "test", stem + ".chk"), "rb").read()
-    assert p.stdout == want
+    assert md5(out) == pin["input"] and pin["stdout"] == md5(want)

@@ -1,11 +1,13 @@
 """CPU: the post-processors of the hit stream -- rm2ct, rmfmt, rmprune -- against outputs
 of the reference's own tools: committed fixtures (tests/golden/tools/*.ref, made by
-make_tool_goldens.py with oracle/_ref) and, when oracle/_ref is present, the reference
-binaries run here on a complete search output."""
+make_tool_goldens.py with oracle/_ref) and what the reference binaries (oracle/_ref) print for a
+complete search output, pinned in tests/golden/ref_pins.json (tests/ref_pins.py)."""
 import os
 import subprocess
 
 import pytest
+
+from ref_pins import md5, pinned
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "tools")
@@ -32,17 +34,26 @@ def test_tool_matches_reference_fixture(built, name, tool, opts):
     assert rc == 0 and got == want
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "rmprune")), reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("name", ["trna.descr", "qu+tr.descr", "sprintf.descr"])
 def test_tools_match_reference_binaries_on_full_output(built, workdir, name):
     p = subprocess.run([built["oracle_cli"], "-descr", name, "gbrna.111.0.fastn"], cwd=workdir, env=ENV,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0
+
+    def run_ref():
+        outs = {}
+        for tool, opts in CASES:
+            rc_ref, want = _run(os.path.join(REF, tool), opts, p.stdout)
+            outs[" ".join([tool] + opts)] = {"ok": rc_ref == 0, "stdout": md5(want)}
+        return {"input": md5(p.stdout), "tools": outs}
+
+    pin = pinned("tools on the search output of " + name, run_ref)
+    assert md5(p.stdout) == pin["input"]
     for tool, opts in CASES:
-        rc_ref, want = _run(os.path.join(REF, tool), opts, p.stdout)
+        want = pin["tools"][" ".join([tool] + opts)]
         rc, got = _run(os.path.join(BIN, tool), opts, p.stdout)
-        assert (rc == 0) == (rc_ref == 0), (tool, opts)          # e.g. rm2ct refuses triple / quad helices
-        assert got == want, (tool, opts)
+        assert (rc == 0) == want["ok"], (tool, opts)          # e.g. rm2ct refuses triple / quad helices
+        assert md5(got) == want["stdout"], (tool, opts)
 
 
 def test_pipeline_of_the_reference_test_suite(built, workdir):
