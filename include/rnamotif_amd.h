@@ -150,6 +150,27 @@ void	rma_free( void *p );
 int	rma_db_create_packed_ranges( rma_scanner_t *sc, const rma_pack_t *pk, const int32_t *entry,
 		const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, rma_db_t **out, char *err, size_t errlen );
 
+/* ---- databases from text already in device memory.  Entry i is the slen[i] bytes at text + start[i]
+ * (start, slen, pos_lo, pos_hi are host arrays; pos_lo/pos_hi may be NULL, else as rma_db_create_ranges),
+ * all inside the text_bytes bytes at text, which is memory of the scanner's device.  The words are the
+ * ones rma_db_create() makes of the same bytes, packed by a kernel on the device's upload stream.
+ * table: NULL = the readers' letters (acgtu in either case, every other byte ambiguous), else 256 codes,
+ * byte -> 0-3 or 4 (ambiguous), in host memory or on the scanner's device (there a code above 3 counts as
+ * 4).  stream: the caller's hipStream_t the text was written on (NULL = the default stream): the packing
+ * runs behind what is queued there now.  The text stays as it is, and allocated, until rma_db_wait()
+ * returns or a scan of the database has ended.  Pointers are checked (device memory of the scanner's
+ * device, ranges inside the text and its allocation) before anything is launched. */
+int	rma_db_create_device( rma_scanner_t *sc, const void *text, int64_t text_bytes, const int64_t *start, const int32_t *slen,
+		const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, const uint8_t *table, void *stream,
+		rma_db_t **out, char *err, size_t errlen );
+/* the default table of rma_db_create_device: byte -> code (0-3) or 4, the readers' letters */
+void	rma_letter_codes( uint8_t codes[ 256 ] );
+/* a database's packed words read back (for verification; whichever path made them): codes[ 2 * w ],
+ * amask[ w ] with w = rma_db_mask_words( db ), base_off[ n ], slen[ n ]; any of them may be NULL */
+int64_t	rma_db_mask_words( const rma_db_t *db );
+int	rma_db_read_packed( const rma_db_t *db, uint32_t *codes, uint32_t *amask, int64_t *base_off, int32_t *slen,
+		char *err, size_t errlen );
+
 /* ---- scan every sequence of db (both strands when the program says so).
  * *hits receives *n_hits records of rma_hit_stride( prog ) words, sorted by
  * (seq, comp, szero, rank, order) = the reference's output order; the memory
@@ -168,6 +189,12 @@ int	rma_scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, char
 /* rma_scan_end() that leaves the ordered records in HBM (*d_hits is a device pointer, valid until
  * the scanner's next scan): for rma_gather_hits(), which sends them from there. */
 int	rma_scan_end_on_device( rma_scanner_t *sc, const int32_t **d_hits, int64_t *n_hits, char *err, size_t errlen );
+
+/* The last scan's ordered records (left in HBM by rma_scan_end_on_device, or by rma_scan_end when they
+ * were ordered on the device) into dst, device memory of the scanner's device with room for dst_words
+ * words: the copy is ordered after the scanner's work and before what is queued on `stream` (the caller's
+ * hipStream_t, NULL = the default stream) from now on.  dst is checked as rma_db_create_device's text. */
+int	rma_scan_records_to_device( rma_scanner_t *sc, int32_t *dst, int64_t dst_words, void *stream, char *err, size_t errlen );
 
 /* The device part of rma_scan() alone (search kernel + efn kernel, no copy back,
  * no sort), for measurement: returns the candidate count and the time of the

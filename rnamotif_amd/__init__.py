@@ -115,6 +115,14 @@ def lib() -> C.CDLL:
     L.rma_replay_batch.argtypes = [vp, cpp, cpp, cpp, i32p, C.c_int32, i32p, C.c_int64, i64p,
                                    C.c_char_p, C.c_size_t]
     L.rma_replay_close.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.rma_db_create_device.argtypes = [vp, vp, C.c_int64, i64p, i32p, i32p, i32p, C.c_int32, C.c_char_p, vp,
+                                       C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.rma_letter_codes.argtypes = [C.c_char_p]
+    L.rma_letter_codes.restype = None
+    L.rma_db_mask_words.argtypes = [vp]
+    L.rma_db_mask_words.restype = C.c_int64
+    L.rma_db_read_packed.argtypes = [vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_scan_records_to_device.argtypes = [vp, vp, C.c_int64, vp, C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -219,6 +227,20 @@ class Database:
         self._h = h
         self.bases = L.rma_db_bases(h)
 
+    def packed(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The words in HBM, read back (verification): (codes uint32 [2 w], amask uint32 [w], base_off int64 [n],
+        slen int32 [n]), w the mask words."""
+        L = lib()
+        w = int(L.rma_db_mask_words(self._h))
+        codes = np.zeros(2 * w, dtype=np.uint32)
+        amask = np.zeros(w, dtype=np.uint32)
+        base_off = np.zeros(self.n_seqs, dtype=np.int64)
+        slen = np.zeros(self.n_seqs, dtype=np.int32)
+        err = C.create_string_buffer(_ERRLEN)
+        _check(L.rma_db_read_packed(self._h, codes.ctypes.data, amask.ctypes.data, base_off.ctypes.data,
+                                    slen.ctypes.data, err, _ERRLEN), err)
+        return codes, amask, base_off, slen
+
     def wait(self) -> None:
         """Until the upload is complete (wait=False databases)."""
         err = C.create_string_buffer(_ERRLEN)
@@ -228,12 +250,92 @@ class Database:
         if self._h:
             lib().rma_db_destroy(self._h)
             self._h = None
+        self._text = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+def text_entries(text, offsets=None, lengths=None):
+    """The entries of a byte tensor as (start, slen): int64 / int32 numpy arrays, start in bytes from the first
+    byte of the tensor's storage.  Only the tensor's metadata is read (a CPU tensor will do).
+
+    1-D uint8/int8 tensor: `offsets` (n+1 ascending, entry i = text[offsets[i]:offsets[i+1]]) or `lengths` (the
+    entries one after the other), neither: one entry, the whole tensor.  2-D [N, L]: row i is entry i, its first
+    `lengths[i]` bytes (default L); rows may lie at any stride(0), the bytes of a row one after the other."""
+    import torch
+    if not isinstance(text, torch.Tensor):
+        raise TypeError(f"text is a {type(text).__name__}, not a torch.Tensor")
+    if text.dtype not in (torch.uint8, torch.int8):
+        raise TypeError(f"text is {text.dtype}: uint8 or int8 bytes are needed")
+
+    def ints(x, what):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        a = np.asarray(x)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"{what}: a 1-D sequence of integers is needed")
+        return a.astype(np.int64)
+
+    so = int(text.storage_offset())
+    if text.ndim == 1:
+        if offsets is not None and lengths is not None:
+            raise ValueError("offsets or lengths, not both")
+        if text.numel() > 1 and text.stride(0) != 1:
+            raise ValueError(f"text has stride {text.stride(0)}: the bytes of an entry one after the other are needed")
+        size = int(text.numel())
+        if offsets is not None:
+            off = ints(offsets, "offsets")
+            if off.size == 0:
+                raise ValueError("offsets: n+1 values are needed (0 for no entry)")
+            slen = np.diff(off)
+            if off[0] < 0 or off[-1] > size or (slen < 0).any():
+                raise ValueError(f"offsets: an ascending sequence inside the text's {size} bytes is needed")
+            start = off[:-1]
+        else:
+            slen = ints(lengths, "lengths") if lengths is not None else np.array([size], dtype=np.int64)
+            if (slen < 0).any() or int(slen.sum()) > size:
+                raise ValueError(f"lengths: non-negative, {int(slen.sum())} bytes in all, the text has {size}")
+            start = np.concatenate([[0], np.cumsum(slen)[:-1]]).astype(np.int64)
+        start = start + so
+    elif text.ndim == 2:
+        if offsets is not None:
+            raise ValueError("offsets are for a 1-D text; a 2-D text takes per-row lengths")
+        rows, width = int(text.shape[0]), int(text.shape[1])
+        if width > 1 and text.stride(1) != 1:
+            raise ValueError(f"text has inner stride {text.stride(1)}: the bytes of a row one after the other are needed")
+        if lengths is None:
+            slen = np.full(rows, width, dtype=np.int64)
+        else:
+            slen = ints(lengths, "lengths")
+            if slen.size != rows:
+                raise ValueError(f"lengths: one per row, {rows}, not {slen.size}")
+            if (slen < 0).any() or (slen > width).any():
+                raise ValueError(f"lengths: 0 to the row length {width}")
+        start = so + np.arange(rows, dtype=np.int64) * int(text.stride(0))
+    else:
+        raise ValueError(f"text has {text.ndim} dimensions: 1 (entries concatenated) or 2 (one entry per row)")
+    if slen.size and slen.max() > 0x7fffffff:
+        raise ValueError("an entry of 2**31 bases or more")
+    return np.ascontiguousarray(start, dtype=np.int64), np.ascontiguousarray(slen, dtype=np.int32)
+
+
+def alphabet_table(alphabet: str) -> bytes:
+    """The 256-byte table of database_from_tensor(alphabet=...): value i is the letter alphabet[i] (its code as the
+    readers take it, 4 for a letter that is not acgtu), every other value ambiguous (4)."""
+    if not isinstance(alphabet, str) or not 0 < len(alphabet) <= 256:
+        raise ValueError(f"alphabet: a string of 1 to 256 letters is needed, not {alphabet!r}")
+    if any(ord(ch) > 255 for ch in alphabet):
+        raise ValueError(f"alphabet: letters are single bytes, not {alphabet!r}")
+    codes = C.create_string_buffer(256)
+    lib().rma_letter_codes(codes)
+    tab = bytearray([4] * 256)
+    for i, ch in enumerate(alphabet):
+        tab[i] = codes.raw[ord(ch)]
+    return bytes(tab)
 
 
 class Scanner:
@@ -246,6 +348,7 @@ class Scanner:
         err = C.create_string_buffer(_ERRLEN)
         _check(L.rma_scanner_create(descr.program, descr.efndata, device, C.byref(h), err, _ERRLEN), err)
         self._h = h
+        self.device = device
         if descr.efn2data:
             _check(L.rma_scanner_set_efn2data(h, descr.efn2data, err, _ERRLEN), err)
 
@@ -256,6 +359,57 @@ class Scanner:
                            entries: Optional[Sequence[int]] = None,
                            ranges: Optional[Sequence[Tuple[int, int]]] = None, wait: bool = True) -> Database:
         return Database(self, pack=pack, first=first, count=count, entries=entries, ranges=ranges, wait=wait)
+
+    def database_from_tensor(self, text, offsets=None, lengths=None, ranges: Optional[Sequence[Tuple[int, int]]] = None,
+                             alphabet: Optional[str] = None, wait: bool = False) -> Database:
+        """A database of bytes already on this scanner's GPU, packed there (rma_db_create_device): the same words
+        database() makes of the same bytes.  text and the entries in it as text_entries() takes them; ranges as
+        database(); alphabet: value i of the text is letter alphabet[i] (default: the bytes are letters).  The
+        packing runs behind the work queued on torch's current stream; the database keeps the tensor until it is
+        closed.  Records of its scans are candidates as rma_scan returns them: there is no host text to replay."""
+        import torch
+        if not isinstance(text, torch.Tensor):
+            raise TypeError(f"text is a {type(text).__name__}, not a torch.Tensor")
+        if text.device.type != "cuda" or (text.device.index if text.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"text is on {text.device}: the scanner is on cuda:{self.device}")
+        start, slen = text_entries(text, offsets, lengths)
+        n = len(slen)
+        lo = hi = None
+        if ranges is not None:
+            if len(ranges) != n:
+                raise ValueError(f"ranges: one per entry, {n}, not {len(ranges)}")
+            lo = np.ascontiguousarray([int(r[0]) for r in ranges], dtype=np.int32)
+            hi = np.ascontiguousarray([int(r[1]) for r in ranges], dtype=np.int32)
+        table = alphabet_table(alphabet) if alphabet is not None else None
+        storage = text.untyped_storage()
+        stream = torch.cuda.current_stream(text.device).cuda_stream
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        h = C.c_void_p()
+        err = C.create_string_buffer(_ERRLEN)
+        _check(lib().rma_db_create_device(self._h, storage.data_ptr(), storage.nbytes(), start.ctypes.data_as(i64p),
+                                          slen.ctypes.data_as(i32p), lo.ctypes.data_as(i32p) if lo is not None else None,
+                                          hi.ctypes.data_as(i32p) if hi is not None else None, n, table, stream,
+                                          C.byref(h), err, _ERRLEN), err)
+        db = Database.__new__(Database)
+        db.scanner, db.n_seqs, db._h, db._text = self, n, h, text
+        db.bases = lib().rma_db_bases(h)
+        if wait:
+            db.wait()
+        return db
+
+    def scan_tensor(self, db: Database):
+        """scan(db) with the records left on the GPU: an int32 tensor [n, hit_stride] on the scanner's device, the
+        same records in the same order, ready on torch's current stream."""
+        import torch
+        self.scan_begin(db)
+        n = self.scan_end_on_device()
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((n, self.descr.hit_stride), dtype=torch.int32, device=dev)
+        if n > 0:
+            err = C.create_string_buffer(_ERRLEN)
+            _check(lib().rma_scan_records_to_device(self._h, out.data_ptr(), out.numel(),
+                                                    torch.cuda.current_stream(dev).cuda_stream, err, _ERRLEN), err)
+        return out
 
     def set_option(self, name: str, value: int) -> None:
         """A launch-shape / diagnostic switch between scans (rma_scanner_set_option); the RNAMOTIF_*

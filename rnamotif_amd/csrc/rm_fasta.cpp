@@ -279,20 +279,27 @@ bool FastaReader::next_fastn( SeqRecord &rec )	// FN_fgetseq, dbutil.c:42-128
 	return true;
 }
 
+const unsigned char *letter_codes()
+{
+	struct Lut {
+		unsigned char	v[ 256 ];
+		Lut()
+		{
+			for( int c = 0; c < 256; c++ )
+				v[ c ] = 4;
+			v[ 'a' ] = v[ 'A' ] = 0;
+			v[ 'c' ] = v[ 'C' ] = 1;
+			v[ 'g' ] = v[ 'G' ] = 2;
+			v[ 't' ] = v[ 'T' ] = v[ 'u' ] = v[ 'U' ] = 3;
+		}
+	};
+	static const Lut	lut;
+	return lut.v;
+}
+
 void PackedDb::add( const char *seq, int n )
 {
-	// letter -> 2-bit code (bits 0-1) and ambiguity flag (bit 2)
-	static unsigned char	lut[ 256 ];
-	static bool	init = false;
-	if( !init ){
-		for( int c = 0; c < 256; c++ )
-			lut[ c ] = 4;
-		lut[ 'a' ] = lut[ 'A' ] = 0;
-		lut[ 'c' ] = lut[ 'C' ] = 1;
-		lut[ 'g' ] = lut[ 'G' ] = 2;
-		lut[ 't' ] = lut[ 'T' ] = lut[ 'u' ] = lut[ 'U' ] = 3;
-		init = true;
-	}
+	const unsigned char	*lut = letter_codes();
 	base_off.push_back( padded_bases() );
 	slen.push_back( n );
 	total_bases += n;

@@ -51,6 +51,10 @@ private:
 	size_t	pos_ = 0, len_ = 0;
 };
 
+// letter -> 2-bit code (bits 0-1) and ambiguity flag (bit 2): a=0 c=1 g=2 t=u=3 in either case, every other
+// byte 4.  The readers' letters, for PackedDb::add() and the device packer's default table alike.
+const unsigned char	*letter_codes();
+
 // Packed database layout (device side):
 //   codes: 2 bits per base, 16 bases per uint32 word, base i of a sequence at
 //          bits 2*(i%16) of word i/16; a=0 c=1 g=2 t=3, ambiguous letters 0

@@ -36,6 +36,7 @@
 #include "rm_pack.h"
 #include "rm_hitsort.h"
 #include "rm_hitsort_dev.h"
+#include "rm_dbpack_dev.h"
 #include "rnamotif_amd.h"
 
 #define HIPCHK( call )	do{ hipError_t e_ = ( call ); if( e_ != hipSuccess ){ \
@@ -271,6 +272,8 @@ struct rma_db {
 	int32_t	*d_slen = nullptr, *d_pos_lo = nullptr, *d_pos_hi = nullptr;
 	std::vector<int32_t>	h_slen, h_pos_lo, h_pos_hi;	// (host copies: the tilings are made from them)
 	std::vector<int64_t>	h_base_off;
+	std::vector<int64_t>	h_text_start;		// (rma_db_create_device: what the copies to the device read)
+	std::vector<uint8_t>	h_table;
 	int32_t	n_seq = 0, max_slen = 0;
 	int64_t	total_bases = 0, sum_slen = 0;
 	int64_t	padded_bases = 0;	// bases the packed arrays hold, padding between the entries included
@@ -625,15 +628,13 @@ extern "C" void rma_scanner_destroy( rma_scanner_t *sc )
 // ---------------------------------------------------------------- databases
 static size_t align256( size_t x ) { return ( x + 255 ) & ~size_t( 255 ); }
 
-// Upload n packed entries: `pieces` are runs of whole words of the source arrays that follow each
-// other in the device arrays (one run for a slice of a pack, one per entry for chosen entries);
-// base_off[] are the entries' offsets in bases (multiples of 32) in the device arrays.  wait:
-// return when the copies are complete (the source may then go away); otherwise the caller keeps
-// the source as it is until rma_db_wait() or the end of the first scan.
-struct Piece { const uint32_t *codes, *amask; size_t mask_words; };
-
-static int db_upload( int device, const std::vector<Piece> &pieces, const int64_t *base_off, const int32_t *slen, int32_t n,
-	const int32_t *pos_lo, const int32_t *pos_hi, bool wait, rma_db_t **out, char *err, size_t errlen )
+// A database of n entries in a block of its own, the small tables -- base_off[] (the entries' offsets in
+// bases, multiples of 32, in the device arrays), slen, pos_lo / pos_hi -- on their way on the device's
+// upload stream; the packed words (n_mask mask words, twice as many code words) are the caller's to fill,
+// on that stream, before db_ready().  extra: bytes of room past the tables (db_from_device's inputs), at
+// *extra_at.
+static int db_alloc( int device, const int64_t *base_off, const int32_t *slen, int32_t n, const int32_t *pos_lo, const int32_t *pos_hi,
+	size_t n_mask, size_t extra, rma_db_t **out, char **extra_at, char *err, size_t errlen )
 {
 	*out = nullptr;
 	if( pos_lo != nullptr )
@@ -666,9 +667,6 @@ static int db_upload( int device, const std::vector<Piece> &pieces, const int64_
 		else
 			db->total_bases += slen[ i ];
 	}
-	size_t	n_mask = 0;
-	for( const Piece &p : pieces )
-		n_mask += p.mask_words;
 	db->padded_bases = int64_t( n_mask ) * 32;
 	for( int i = 0; i < n; i++ )
 		if( base_off[ i ] < 0 || base_off[ i ] + slen[ i ] > db->padded_bases || ( i + 1 < n && base_off[ i ] + slen[ i ] > base_off[ i + 1 ] ) )
@@ -677,7 +675,8 @@ static int db_upload( int device, const std::vector<Piece> &pieces, const int64_
 	const size_t	o_codes = 0, o_amask = align256( std::max<size_t>( 2 * n_mask, 1 ) * 4 );
 	const size_t	o_off = o_amask + align256( std::max<size_t>( n_mask, 1 ) * 4 ), o_slen = o_off + align256( nn * 8 );
 	const size_t	o_lo = o_slen + align256( nn * 4 ), o_hi = o_lo + ( pos_lo ? align256( nn * 4 ) : 0 );
-	const size_t	total = o_hi + ( pos_lo ? align256( nn * 4 ) : 0 );
+	const size_t	o_extra = o_hi + ( pos_lo ? align256( nn * 4 ) : 0 );
+	const size_t	total = o_extra + extra;
 	HIPCHK( ctx->take( total, &db->blk ) );
 	char	*base = static_cast<char *>( db->blk.p );
 	db->d_codes = reinterpret_cast<uint32_t *>( base + o_codes );
@@ -688,16 +687,10 @@ static int db_upload( int device, const std::vector<Piece> &pieces, const int64_
 		db->d_pos_lo = reinterpret_cast<int32_t *>( base + o_lo );
 		db->d_pos_hi = reinterpret_cast<int32_t *>( base + o_hi );
 	}
+	if( extra_at != nullptr )
+		*extra_at = base + o_extra;
 	HIPCHK( hipEventCreateWithFlags( &db->ready, hipEventDisableTiming ) );
 	hipStream_t	up = ctx->upload;
-	size_t	at = 0;		// mask words uploaded so far
-	for( const Piece &p : pieces ){
-		if( p.mask_words == 0 )
-			continue;
-		HIPCHK( hipMemcpyAsync( db->d_codes + 2 * at, p.codes, 2 * p.mask_words * 4, hipMemcpyHostToDevice, up ) );
-		HIPCHK( hipMemcpyAsync( db->d_amask + at, p.amask, p.mask_words * 4, hipMemcpyHostToDevice, up ) );
-		at += p.mask_words;
-	}
 	if( n > 0 ){
 		// (the small tables come from the host copies the database keeps: they outlive the call)
 		HIPCHK( hipMemcpyAsync( db->d_base_off, db->h_base_off.data(), size_t( n ) * 8, hipMemcpyHostToDevice, up ) );
@@ -707,12 +700,55 @@ static int db_upload( int device, const std::vector<Piece> &pieces, const int64_
 			HIPCHK( hipMemcpyAsync( db->d_pos_hi, db->h_pos_hi.data(), size_t( n ) * 4, hipMemcpyHostToDevice, up ) );
 		}
 	}
-	HIPCHK( hipEventRecord( db->ready, up ) );
-	if( wait )
-		HIPCHK( hipEventSynchronize( db->ready ) );
 	guard.p = nullptr;
 	*out = db;
 	return 0;
+}
+
+// The words of db are on their way on the upload stream: db->ready behind them (wait: until they are in).
+// On failure db is destroyed.
+static int db_ready( rma_db_t **out, bool wait, char *err, size_t errlen )
+{
+	struct DbGuard { rma_db *p; ~DbGuard(){ if( p ) rma_db_destroy( p ); } }	guard{ *out };
+	*out = nullptr;
+	HIPCHK( hipEventRecord( guard.p->ready, guard.p->ctx->upload ) );
+	if( wait )
+		HIPCHK( hipEventSynchronize( guard.p->ready ) );
+	*out = guard.p;
+	guard.p = nullptr;
+	return 0;
+}
+
+// Upload n packed entries: `pieces` are runs of whole words of the source arrays that follow each
+// other in the device arrays (one run for a slice of a pack, one per entry for chosen entries);
+// base_off[] are the entries' offsets in bases (multiples of 32) in the device arrays.  wait:
+// return when the copies are complete (the source may then go away); otherwise the caller keeps
+// the source as it is until rma_db_wait() or the end of the first scan.
+struct Piece { const uint32_t *codes, *amask; size_t mask_words; };
+
+static int db_upload( int device, const std::vector<Piece> &pieces, const int64_t *base_off, const int32_t *slen, int32_t n,
+	const int32_t *pos_lo, const int32_t *pos_hi, bool wait, rma_db_t **out, char *err, size_t errlen )
+{
+	size_t	n_mask = 0;
+	for( const Piece &p : pieces )
+		n_mask += p.mask_words;
+	if( db_alloc( device, base_off, slen, n, pos_lo, pos_hi, n_mask, 0, out, nullptr, err, errlen ) )
+		return 1;
+	rma_db	*db = *out;
+	struct DbGuard { rma_db *p; ~DbGuard(){ if( p ) rma_db_destroy( p ); } }	guard{ db };
+	*out = nullptr;
+	hipStream_t	up = db->ctx->upload;
+	size_t	at = 0;		// mask words uploaded so far
+	for( const Piece &p : pieces ){
+		if( p.mask_words == 0 )
+			continue;
+		HIPCHK( hipMemcpyAsync( db->d_codes + 2 * at, p.codes, 2 * p.mask_words * 4, hipMemcpyHostToDevice, up ) );
+		HIPCHK( hipMemcpyAsync( db->d_amask + at, p.amask, p.mask_words * 4, hipMemcpyHostToDevice, up ) );
+		at += p.mask_words;
+	}
+	guard.p = nullptr;
+	*out = db;
+	return db_ready( out, wait, err, errlen );
 }
 
 // the device a database made for scanner sc lives on (sc may be null: device 0)
@@ -823,6 +859,174 @@ extern "C" int rma_db_create_packed_ranges( rma_scanner_t *sc, const rma_pack_t 
 		return 1;
 	return tile_at_creation( sc, out, err, errlen );
 }
+
+// ---------------------------------------------------------------- databases from device memory
+// A pointer a kernel (or a copy on the device) is to be handed: memory of `device` the runtime knows, and
+// bytes [lo, hi) from it inside its allocation where the runtime can say where that ends (memory it maps
+// itself it cannot -- torch's expandable segments: the caller's extent governs alone).  A host pointer
+// handed to a kernel faults the GPU; nothing is launched before this has said yes.
+static int check_device_bytes( const void *p, int device, int64_t lo, int64_t hi, const char *what, char *err, size_t errlen )
+{
+	hipPointerAttribute_t	a;
+	memset( &a, 0, sizeof( a ) );
+	hipError_t	e = hipPointerGetAttributes( &a, p );
+	if( e != hipSuccess ){
+		( void )hipGetLastError();
+		snprintf( err, errlen, "%s (%p) is not device memory: the HIP runtime does not know it (%s)", what, p, hipGetErrorString( e ) );
+		return 1;
+	}
+	if( a.type != hipMemoryTypeDevice || a.isManaged ){
+		const char	*kind = a.isManaged || a.type == hipMemoryTypeManaged ? "managed" : a.type == hipMemoryTypeHost ? "page-locked host" :
+			a.type == hipMemoryTypeUnregistered ? "unregistered host" : "not device";
+		snprintf( err, errlen, "%s (%p) is %s memory: device memory of device %d is needed", what, p, kind, device );
+		return 1;
+	}
+	if( a.device != device ){
+		snprintf( err, errlen, "%s (%p) is memory of device %d, the scanner is on device %d", what, p, a.device, device );
+		return 1;
+	}
+	hipDeviceptr_t	base = nullptr;
+	size_t	size = 0;
+	e = hipMemGetAddressRange( &base, &size, const_cast<void *>( p ) );
+	if( e != hipSuccess || base == nullptr ){
+		( void )hipGetLastError();
+		return 0;
+	}
+	const uintptr_t	q = reinterpret_cast<uintptr_t>( p ), b = reinterpret_cast<uintptr_t>( base );
+	if( int64_t( q - b ) + lo < 0 || int64_t( q - b ) + hi > int64_t( size ) ){
+		snprintf( err, errlen, "%s: bytes [%lld, %lld) from %p lie outside its allocation (%zu bytes at %p)", what,
+			( long long )lo, ( long long )hi, p, size, base );
+		return 1;
+	}
+	return 0;
+}
+
+// the caller's stream has reached this point before anything later on `on` runs
+static int stream_after( hipStream_t on, hipStream_t caller, char *err, size_t errlen )
+{
+	hipEvent_t	ev = nullptr;
+	HIPCHK( hipEventCreateWithFlags( &ev, hipEventDisableTiming ) );
+	hipError_t	e = hipEventRecord( ev, caller );
+	if( e == hipSuccess )
+		e = hipStreamWaitEvent( on, ev, 0 );
+	( void )hipEventDestroy( ev );		// (the wait holds what it needs)
+	if( e != hipSuccess ){
+		snprintf( err, errlen, "ordering behind the caller's stream: %s", hipGetErrorString( e ) );
+		return 1;
+	}
+	return 0;
+}
+
+extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_t text_bytes, const int64_t *start, const int32_t *slen,
+	const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, const uint8_t *table, void *stream, rma_db_t **out, char *err, size_t errlen )
+{
+	*out = nullptr;
+	const int	device = device_of( sc );
+	if( n < 0 || text_bytes < 0 || ( n > 0 && ( start == nullptr || slen == nullptr ) ) || ( pos_lo == nullptr ) != ( pos_hi == nullptr ) ){
+		snprintf( err, errlen, "rma_db_create_device: %d entries, %lld bytes of text: bad arguments", n, ( long long )text_bytes );
+		return 1;
+	}
+	// every entry inside the declared text, before anything else
+	int64_t	lo = text_bytes, hi = 0;
+	for( int i = 0; i < n; i++ ){
+		if( slen[ i ] < 0 || start[ i ] < 0 ){
+			snprintf( err, errlen, "entry %d: negative %s (start %lld, length %d)", i, slen[ i ] < 0 ? "length" : "start",
+				( long long )start[ i ], slen[ i ] );
+			return 1;
+		}
+		if( start[ i ] > text_bytes - slen[ i ] ){
+			snprintf( err, errlen, "entry %d: bytes [%lld, %lld) lie past the text's %lld bytes", i, ( long long )start[ i ],
+				( long long )start[ i ] + slen[ i ], ( long long )text_bytes );
+			return 1;
+		}
+		if( slen[ i ] > 0 ){
+			lo = std::min( lo, start[ i ] );
+			hi = std::max( hi, start[ i ] + slen[ i ] );
+		}
+	}
+	HIPCHK( hipSetDevice( device ) );
+	if( hi > lo && check_device_bytes( text, device, lo, hi, "the text", err, errlen ) )
+		return 1;
+	// the table: on the device (copied there, device to device) or on the host (checked, copied up)
+	bool	table_on_device = false;
+	std::vector<uint8_t>	tab( rma::letter_codes(), rma::letter_codes() + 256 );
+	if( table != nullptr ){
+		hipPointerAttribute_t	a;
+		memset( &a, 0, sizeof( a ) );
+		if( hipPointerGetAttributes( &a, table ) != hipSuccess )
+			( void )hipGetLastError();
+		else if( a.type == hipMemoryTypeDevice && !a.isManaged )
+			table_on_device = true;
+		if( table_on_device ){
+			if( check_device_bytes( table, device, 0, 256, "the table", err, errlen ) )
+				return 1;
+		}else{
+			for( int c = 0; c < 256; c++ )
+				if( table[ c ] > 4 ){
+					snprintf( err, errlen, "table[ %d ] = %d: the codes are 0-3 and 4 (ambiguous)", c, table[ c ] );
+					return 1;
+				}
+			tab.assign( table, table + 256 );
+		}
+	}
+	// the layout PackedDb::add() makes: every entry on a 32-base boundary, one after the other
+	std::vector<int64_t>	base_off( static_cast<size_t>( n ) );
+	int64_t	padded = 0;
+	for( int i = 0; i < n; i++ ){
+		base_off[ size_t( i ) ] = padded;
+		padded += ( int64_t( slen[ i ] ) + 31 ) / 32 * 32;
+	}
+	const size_t	n_mask = size_t( padded / 32 );
+	char	*extra = nullptr;
+	if( db_alloc( device, base_off.data(), slen, n, pos_lo, pos_hi, n_mask, align256( size_t( std::max( n, 1 ) ) * 8 ) + 256, out, &extra, err, errlen ) )
+		return 1;
+	rma_db	*db = *out;
+	struct DbGuard { rma_db *p; ~DbGuard(){ if( p ) rma_db_destroy( p ); } }	guard{ db };
+	*out = nullptr;
+	int64_t	*d_start = reinterpret_cast<int64_t *>( extra );
+	uint8_t	*d_table = reinterpret_cast<uint8_t *>( extra + align256( size_t( std::max( n, 1 ) ) * 8 ) );
+	hipStream_t	up = db->ctx->upload;
+	// (host copies the database keeps until it is destroyed: the copies read them after this returns)
+	db->h_text_start.assign( start, start + n );
+	db->h_table = tab;
+	if( n > 0 )
+		HIPCHK( hipMemcpyAsync( d_start, db->h_text_start.data(), size_t( n ) * 8, hipMemcpyHostToDevice, up ) );
+	if( !table_on_device )
+		HIPCHK( hipMemcpyAsync( d_table, db->h_table.data(), 256, hipMemcpyHostToDevice, up ) );
+	// the text (and a device table) as the caller's stream leaves them
+	if( stream_after( up, static_cast<hipStream_t>( stream ), err, errlen ) )
+		return 1;
+	if( table_on_device )
+		HIPCHK( hipMemcpyAsync( d_table, table, 256, hipMemcpyDeviceToDevice, up ) );
+	HIPCHK( rma::pack_text( static_cast<const uint8_t *>( text ), d_start, db->d_base_off, db->d_slen, n, int64_t( n_mask ), d_table,
+		db->d_codes, db->d_amask, up ) );
+	guard.p = nullptr;
+	*out = db;
+	if( db_ready( out, false, err, errlen ) )
+		return 1;
+	return tile_at_creation( sc, out, err, errlen );
+}
+
+extern "C" int64_t rma_db_mask_words( const rma_db_t *db ) { return db->padded_bases / 32; }
+
+extern "C" int rma_db_read_packed( const rma_db_t *db, uint32_t *codes, uint32_t *amask, int64_t *base_off, int32_t *slen,
+	char *err, size_t errlen )
+{
+	HIPCHK( hipSetDevice( db->device ) );
+	HIPCHK( hipEventSynchronize( db->ready ) );
+	const size_t	n_mask = size_t( db->padded_bases / 32 ), n = size_t( db->n_seq );
+	if( codes != nullptr && n_mask > 0 )
+		HIPCHK( hipMemcpy( codes, db->d_codes, n_mask * 8, hipMemcpyDeviceToHost ) );
+	if( amask != nullptr && n_mask > 0 )
+		HIPCHK( hipMemcpy( amask, db->d_amask, n_mask * 4, hipMemcpyDeviceToHost ) );
+	if( base_off != nullptr && n > 0 )
+		HIPCHK( hipMemcpy( base_off, db->d_base_off, n * 8, hipMemcpyDeviceToHost ) );
+	if( slen != nullptr && n > 0 )
+		HIPCHK( hipMemcpy( slen, db->d_slen, n * 4, hipMemcpyDeviceToHost ) );
+	return 0;
+}
+
+extern "C" void rma_letter_codes( uint8_t codes[ 256 ] ) { memcpy( codes, rma::letter_codes(), 256 ); }
 
 extern "C" int rma_db_wait( rma_db_t *db, char *err, size_t errlen )
 {
@@ -1655,6 +1859,33 @@ extern "C" int rma_scan_end_on_device( rma_scanner_t *sc, const int32_t **d_hits
 		return 1;
 	*d_hits = *n_hits > 0 ? sc->d_last : nullptr;
 	return 0;
+}
+
+// The last scan's ordered records into caller device memory: the copy on the scanner's stream, between the
+// caller's stream and the scanner's both ways (behind what the caller has queued that may still use dst,
+// ahead of the caller's next work and of the scanner's next scan).
+extern "C" int rma_scan_records_to_device( rma_scanner_t *sc, int32_t *dst, int64_t dst_words, void *stream, char *err, size_t errlen )
+{
+	if( sc->last_state != 1 ){
+		snprintf( err, errlen, "rma_scan_records_to_device: %s", sc->last_state == 0 ? "no scan has ended" :
+			"the last scan's records are on the host only (end the scan with rma_scan_end_on_device)" );
+		return 1;
+	}
+	const int64_t	words = sc->n_last * sc->dprog.hit_stride;
+	if( dst_words < words ){
+		snprintf( err, errlen, "rma_scan_records_to_device: %lld words of records, room for %lld", ( long long )words, ( long long )dst_words );
+		return 1;
+	}
+	if( words == 0 )
+		return 0;
+	HIPCHK( hipSetDevice( sc->device ) );
+	if( check_device_bytes( dst, sc->device, 0, words * 4, "the destination", err, errlen ) )
+		return 1;
+	hipStream_t	caller = static_cast<hipStream_t>( stream );
+	if( stream_after( sc->stream, caller, err, errlen ) )
+		return 1;
+	HIPCHK( hipMemcpyAsync( dst, sc->d_last, size_t( words ) * 4, hipMemcpyDeviceToDevice, sc->stream ) );
+	return stream_after( caller, sc->stream, err, errlen );
 }
 
 // One scan of eight start positions, so that what the runtime sets up on first use (code objects of
