@@ -711,6 +711,7 @@ RMD_COLD int rmd_chk_sites( const rmd_program_t *P, const TB &L, const SQ &sq )	
 // ---------------------------------------------------------------- helpers of the level generators
 RMD_FN int rmd_imin( int a, int b ) { return a < b ? a : b; }
 RMD_FN int rmd_imax( int a, int b ) { return a > b ? a : b; }
+RMD_FN int rmd_iadd_sat( int a, int c ) { return rmd_imin( a, 0x7fffffff - c ) + c; }	// min( a + c, INT_MAX ), c >= 0
 
 RMD_FN int rmd_s3lim( int szero, int sdollar, int i_minl, int h_maxl )	// find_motif.c:426-429
 {
@@ -763,8 +764,9 @@ RMD_COLD void rmd_fill_hit( const rmd_program_t *P, const rmd_lane_t *L, int seq
 RMD_FN void rmd_level0_range( const rmd_program_t *P, int szero, int slen, int *hi, int *lo )
 {
 	const rmd_elem_t	&stp = P->elems[ P->searches[ 0 ] ];
-	int	d0 = rmd_imin( szero + P->w_winsize - 1, slen - 1 );
-	if( stp.maxglen != RMA_UNBOUNDED && szero + stp.maxglen - 1 < d0 )
+	// (min( szero + winsize - 1, slen - 1 ), no sum past INT_MAX: an entry may have 2^31 - 1 bases)
+	int	d0 = rmd_imin( szero, slen - P->w_winsize ) + P->w_winsize - 1;
+	if( stp.maxglen != RMA_UNBOUNDED && stp.maxglen - 1 < d0 - szero )
 		d0 = szero + stp.maxglen - 1;
 	*hi = d0;
 	*lo = szero + stp.minglen - 1;
@@ -863,7 +865,7 @@ RMD_FN int rmd_lean_begin( const rmd_program_t *P, LR &lr, rmd_lean_t &st, int s
 	st.hm_level = -1;
 	st.only_hl = -1;
 	st.pending = 0;
-	int	d0 = rmd_imin( szero + P->w_winsize - 1, slen - 1 ) - szero;
+	int	d0 = ( rmd_imin( szero, slen - P->w_winsize ) + P->w_winsize - 1 ) - szero;
 	rmd_lrec_t	r = rmd_lean_open( P, 0, 0, d0 );
 	const rmd_elem_t	&stp = P->elems[ P->searches[ 0 ] ];
 	st.hi0 = r.sd;
@@ -1168,7 +1170,7 @@ RMD_FN int rmd_gen_begin( const rmd_program_t *P, GR &gr, rmd_gen_t &st, int sze
 	st.paused = 0;
 	rmd_grec_t	r;
 	r.zero = 0;
-	r.osd = int16_t( rmd_imin( szero + P->w_winsize - 1, slen - 1 ) - szero );
+	r.osd = int16_t( ( rmd_imin( szero, slen - P->w_winsize ) + P->w_winsize - 1 ) - szero );
 	st.wend = r.osd;
 	r.sd = r.a = r.c = 0;
 	r.hl = r.ph = 0;

@@ -700,7 +700,7 @@ __device__ inline int pool_item_begin( const rmd_program_t *P, const DbView &db,
 	const int	islen = db.slen[ iseq ];
 	const int64_t	off = db.base_off[ iseq ];
 	// the window's bases [ p0, p1 ) of the strand = [ f_lo, f_hi ) of the entry as stored
-	const int	p0 = rmd_imax( szero - lm, 0 ), p1 = rmd_imin( szero + w + rm, islen );
+	const int	p0 = rmd_imax( szero - lm, 0 ), p1 = rmd_imin( szero, islen - w - rm ) + w + rm;	// (min( szero + w + rm, islen ): no sum past INT_MAX)
 	const int	f_lo = icomp ? islen - p1 : p0, f_hi = icomp ? islen - p0 : p1;
 	const int64_t	g0 = ( off + f_lo ) & ~int64_t( 7 );
 	const int	n_dw = int( ( off + f_hi - g0 + 7 ) >> 3 );
@@ -1268,9 +1268,8 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		// decode the bases this tile can touch: [ z0 - lm, z0 + T + w - 1 + rm )
 		p_lo = z0 - lm;
 		int	p_from = p_lo < 0 ? 0 : p_lo;
-		int	p_to = z0 + T + w - 1 + rm;
-		if( p_to > slen )
-			p_to = slen;
+		// (min( z0 + T + w - 1 + rm, slen ) taken so that no sum passes INT_MAX: an entry may have 2^31 - 1 bases)
+		int	p_to = rmd_imin( z0, slen - ( T + w - 1 + rm ) ) + ( T + w - 1 + rm );
 		if( !live )
 			p_to = p_from;		// slot past the last tile: nothing to decode, no start position
 		// Tile position 0 is moved back (by less than 32) to where a group of 32 bases of the packed database
@@ -1280,7 +1279,8 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		// base stands and, ORed from those by the pair table, the pair rows.  (Until round 3 a lane unpacked 16
 		// bases byte by byte and the rows were made by ten wave ballots per 64 positions: 0.78 of trna.descr's
 		// 2.4 ms.)
-		p_lo -= comp ? ( ( ( p_lo - slen ) % 32 ) + 32 ) % 32 : ( ( p_lo % 32 ) + 32 ) % 32;
+		// ((p_lo - slen) mod 32 for strand 1, the difference of the residues: p_lo - slen itself may pass INT_MIN)
+		p_lo -= comp ? ( ( ( p_lo % 32 ) - ( slen % 32 ) ) % 32 + 32 ) % 32 : ( ( p_lo % 32 ) + 32 ) % 32;
 		vec_words = rmd_imin( pb_words, ( p_to - p_lo + 64 + 63 ) / 64 + 1 );	// bit vector words in use
 		{
 			const int	n_dw = ( p_to - p_lo + 31 ) / 32;
@@ -1431,7 +1431,8 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				res_ = x_ != 0; \
 			} \
 		} }while( 0 )
-#define LIT_OK( szero_, res_ )	LIT_IN( ( szero_ ) + P->lit_lo, ( szero_ ) + lit_hi, res_ )
+// (the sums saturate at INT_MAX, where an entry of 2^31 - 1 bases ends: no literal starts there or past it)
+#define LIT_OK( szero_, res_ )	LIT_IN( rmd_iadd_sat( szero_, P->lit_lo ), rmd_iadd_sat( szero_, lit_hi ), res_ )
 		// LIT_OK for the 64 start positions from bit x of the vectors on, or more (undecided near the vectors' end: kept)
 		auto	lit_starts = [ & ]( int x ) -> unsigned long long {
 			if( !lit )
@@ -1836,7 +1837,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					if( j >= ( by_words ? 0 : n_pos ) )
 						break;
 					rel0 = j + utid;
-					valid0 = rel0 < T && z0 + rel0 <= slen - P->dminlen && z0 + rel0 < pos_hi;
+					valid0 = rel0 < n_pos;		// (rel0 < T, z0 + rel0 <= slen - dminlen and < pos_hi, without the sum)
 					last_j = j + UNIT >= n_pos;
 					j += UNIT;
 				}
@@ -1917,7 +1918,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 									if( pred && P->lit_ehi >= 0 ){
 										const int	e_ = hi - r;
 										const int	a_ = rmd_imax( szero + P->lit_lo, e_ - P->lit_ehi );
-										const int	b_ = rmd_imin( szero + lit_hi, e_ - P->lit_elo );
+										const int	b_ = rmd_imin( szero, e_ - P->lit_elo - lit_hi ) + lit_hi;	// (min( szero + lit_hi, .. ) without passing INT_MAX)
 										if( a_ > b_ )
 											pred = false;
 										else
@@ -1943,7 +1944,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 										// an admissible distance from that end
 										const int	e_ = hi - r;
 										const int	a_ = rmd_imax( szero + P->lit_lo, e_ - P->lit_ehi );
-										const int	b_ = rmd_imin( szero + lit_hi, e_ - P->lit_elo );
+										const int	b_ = rmd_imin( szero, e_ - P->lit_elo - lit_hi ) + lit_hi;	// (min( szero + lit_hi, .. ) without passing INT_MAX)
 										if( a_ > b_ )
 											pred = false;
 										else
@@ -1994,8 +1995,8 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		}
 		for( int j = 0; j < ( by_words ? 0 : n_pos ); j += UNIT ){
 			const int	rel = j + utid;
-			const int	szero = z0 + rel;
-			bool	valid = rel < T && szero <= slen - P->dminlen && szero < pos_hi;
+			bool	valid = rel < n_pos;		// (rel < T, z0 + rel <= slen - dminlen and < pos_hi: z0 + rel of a lane past n_pos may pass INT_MAX)
+			const int	szero = valid ? z0 + rel : z0;
 			if( valid )
 				LIT_OK( szero, valid );
 			int	hi = 0, lo = 1;
@@ -2016,7 +2017,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 						// also sit at an admissible distance from that end
 						const int	e_ = hi - r;
 						const int	a_ = rmd_imax( szero + P->lit_lo, e_ - P->lit_ehi );
-						const int	b_ = rmd_imin( szero + lit_hi, e_ - P->lit_elo );
+						const int	b_ = rmd_imin( szero, e_ - P->lit_elo - lit_hi ) + lit_hi;	// (min( szero + lit_hi, .. ) without passing INT_MAX)
 						if( a_ > b_ )
 							pred = false;
 						else

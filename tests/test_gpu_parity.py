@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import pins
+from large_db import sorted_unique as _sorted_unique
 
 pytestmark = pytest.mark.gpu
 
@@ -372,13 +373,6 @@ def test_syn10m_cli_hit_counts(built, workdir, tmp_path_factory, name):
     if name == "trna.efn.descr":
         first = [l for l in lines if l.startswith(b"syn")][0]
         assert b" ".join(first.split()) == b" ".join(SYN10M_FIRST_TRNA.split())
-
-
-def _sorted_unique(h):
-    key = h[:, :5]
-    order = np.lexsort(key.T[::-1])
-    assert np.array_equal(order, np.arange(len(order))), "records are not in (seq, comp, szero, rank, order) order"
-    assert len(np.unique(key, axis=0)) == len(key)
 
 
 @pytest.mark.parametrize("name", ["trna.efn.descr", "mp.ends.descr", "pk1.descr"])
