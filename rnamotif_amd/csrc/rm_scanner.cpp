@@ -1,6 +1,6 @@
 // rm_scanner.cpp -- the scanner / database half of the C ABI (include/rnamotif_amd.h) on the
-// host: device memory, streams, launch shapes.  The kernels are in rm_scan_kernel.h, reached
-// through the launchers of rm_kernels.h.
+// host: device memory, streams, the launches.  Their shapes are chosen in rm_launch_plan.cpp; the
+// kernels are in rm_scan_kernel.h, reached through the launchers of rm_kernels.h.
 //
 // What belongs to whom:
 //   DevCtx (one per GPU)  the upload stream and a cache of device blocks: a database that is
@@ -18,7 +18,6 @@
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +29,7 @@
 #define RMD_FN		static inline
 #define RMD_FN_MEMBER	inline
 #include "rm_kernels.h"
+#include "rm_launch_plan.h"
 #include "rm_efn_core.h"
 #include "rm_efndata.h"
 #include "rm_fasta.h"
@@ -132,74 +132,12 @@ DevCtx *dev_ctx( int device, char *err, size_t errlen )
 	return g_ctx.back().get();
 }
 
-// launch-shape and diagnostic switches: read from the environment once, when the scanner is
-// created (DESIGN.md has the table), changed afterwards only through rma_scanner_set_option()
-struct Options {
-	int	dbg = 0;
-	int	pool = -1;		// -1: by the descriptor, 0: pass B tile by tile
-	int	pool_min = 1024, pool_refill = 48;
-	int	drain = 1;		// pooled instance: the items are walked by a kernel of their own (0: by the workgroup that found them)
-	int	glist = 0;		// > 0: items of the drain kernel's list (tests: a list that overflows), 0: by the database's size
-	int	drain_waves = 6;	// workgroups (of one wave) of the drain kernel per CU; 0: what LDS and registers allow (16).  Six: the kernel alone
-				// is as fast as with 16 (profiles/overlap_try.py: 0.29 ms), and the next scan's search kernel starts beside it
-	int	flush = -1;		// pooled instance that walks nothing (RMK_LEAN_FLUSH): -1 where the descriptor has a look-ahead chain, 0 never, 1 wherever the pooled instance runs
-	int	efn_light = -1;		// the energy kernel in workgroups of one wave that stage no tables (rma_efn_light_kernel): -1 by the scan's instance, 0 never, 1 always
-	int	search_wgs = 0;		// > 0: workgroups of a lean search kernel per CU (fewer than fit: another scanner's drain kernel runs beside it)
-	int	host_sort = 0, timing = 0;
-	int	short_force = -1;	// -1: by the mean entry length, 0 never, 1 always groups of small tiles, 2 always tiles over the concatenation
-	int	tile = 0, qcap = 0;	// forced tile size / queue entries, 0: computed
-	int	spill = -1;		// forced spill area, -1: SPILL_ITEMS
-	int	budget = 0;
-	static int	env_int( const char *name, int dflt )
-	{
-		const char	*v = getenv( name );
-		return v != nullptr && v[ 0 ] != '\0' ? atoi( v ) : dflt;
-	}
-	void	latch()
-	{
-		dbg = env_int( "RNAMOTIF_DBG", 0 );
-		pool = env_int( "RNAMOTIF_POOL", -1 );
-		pool_min = std::max( 1, env_int( "RNAMOTIF_POOL_MIN", 1024 ) );
-		pool_refill = env_int( "RNAMOTIF_POOL_REFILL", 48 );
-		drain = env_int( "RNAMOTIF_DRAIN", 1 );
-		glist = env_int( "RNAMOTIF_GLIST", 0 );
-		drain_waves = env_int( "RNAMOTIF_DRAIN_WAVES", 6 );
-		search_wgs = env_int( "RNAMOTIF_SEARCH_WGS", 0 );
-		flush = env_int( "RNAMOTIF_FLUSH", -1 );
-		efn_light = env_int( "RNAMOTIF_EFN_LIGHT", -1 );
-		host_sort = env_int( "RNAMOTIF_HOSTSORT", 0 );
-		timing = getenv( "RNAMOTIF_TIMING" ) != nullptr;
-		if( const char *f = getenv( "RNAMOTIF_SHORT" ) )
-			short_force = f[ 0 ] == '1' ? 1 : f[ 0 ] == '2' ? 2 : 0;
-		tile = env_int( "RNAMOTIF_TILE", 0 );
-		if( tile < 0 || tile > 16384 )
-			tile = 0;
-		qcap = env_int( "RNAMOTIF_QCAP", 0 );
-		spill = env_int( "RNAMOTIF_SPILL", -1 );
-		budget = env_int( "RNAMOTIF_BUDGET", 0 );
-	}
-};
-
-// the tiling of a database for one launch shape
-struct Layout {
-	int	tile_t = 0, dminlen = 0, strands = 0, group = 1, qcap = 0;
-	bool	flush = false;		// tiles of the size of the pooled instance that walks nothing (RMK_LEAN_FLUSH)
-	// Tiles over the CONCATENATION of the entries (round 4; databases of short entries, pooled lean instance): a
-	// strand of the whole packed array -- the entries one after the other, each padded to 32 bases -- is tiled as
-	// if it were one long entry, so that the vectors of a tile are full whatever the entries' lengths; what a
-	// tile's tests let through is brought back to its entry when it enters the pool (super_convert in the kernel).
-	bool	concat = false;
-	int64_t	concat_bases = 0;
+// the tiling of a database for one launch shape, on the host and (blk) on the device
+struct Layout : rma::LayoutKey, rma::Tiling {
 	Block	blk;
 	int64_t	*d_tile_start = nullptr;
 	int32_t	*d_tile_seq = nullptr;
-	int64_t	n_tiles = 0;
-	std::vector<int64_t>	h_tile_start;	// (what the copies read: alive as long as the layout)
-	std::vector<int32_t>	h_tile_seq;
-	// one tile per workgroup pass: all a workgroup needs to know of tile t in one 32-byte line (RMK_META_*), so that it
-	// is one load -- made a tile ahead, straight into LDS -- instead of three dependent ones at the tile's start
 	int32_t	*d_tile_meta = nullptr;
-	std::vector<int32_t>	h_tile_meta;
 	hipEvent_t	ready = nullptr;	// the copies are complete: every scan waits for it on its stream
 	~Layout(){ if( ready != nullptr ) ( void )hipEventDestroy( ready ); }
 };
@@ -209,7 +147,8 @@ struct Layout {
 struct rma_scanner {
 	rma_program_t	prog;
 	rmd_program_t	dprog;
-	Options	opt;
+	rma::Options	opt;
+	rma::ProgramPlan	plan;		// tile sizes of the descriptor (rma_scanner_create)
 	int	device = 0;
 	DevCtx	*ctx = nullptr;
 	hipStream_t	stream = nullptr;
@@ -220,7 +159,6 @@ struct rma_scanner {
 	bool	need_efn2 = false;
 	rmd_program_t	*d_prog = nullptr;	// compact image, prog_bytes long
 	int	prog_bytes = 0;
-	int	qcap = QCAP;		// work queue entries per workgroup
 	int16_t	*d_t16 = nullptr;
 	int32_t	*d_tlkey = nullptr, *d_loginc = nullptr;
 	bool	have_efn = false;
@@ -232,8 +170,6 @@ struct rma_scanner {
 	bool	whole_items = false;		// ... which takes the items whole, not in pieces (see search_finish)
 	int	glist_cap = 0;			// pooled instance: items of the list the drain kernel walks (the head of d_pool)
 	int	glist_need = 0;			// ... and what a scan of the instance that walks nothing asked for (search_finish)
-	bool	flush = false;			// long entries are searched by RMK_LEAN_FLUSH, on tiles of its own size
-	int	tile_t_flush = 0, qcap_flush = 0;
 	unsigned	*d_pool = nullptr;		// [grid_blocks][pool_cap][3] pooled instance: items waiting for pass B
 	int	pool_cap = 0;
 	int32_t	*h_raw = nullptr;		// pinned
@@ -242,19 +178,13 @@ struct rma_scanner {
 	std::vector<rma::HitKey>	keys, keys_tmp;
 	rma::DevHitSort	dsort;		// ordering on the device (rm_hitsort_dev.h)
 	unsigned long long	*h_ctr = nullptr;	// pinned: the counters a launch leaves
-	int	tile_t = 2048;
-	int	drain_grid = 0, drain_nib = 0;
-	size_t	drain_lds = 0;
 	int	grid_blocks = 0;		// most workgroups of a launch of a lean instance (eight of four waves per CU)
 	int	spill_blocks = 0;		// workgroups d_spill has areas for
-	int	kinds = 0;			// RMD_KIND_* of the descriptor
 	// the scan between rma_scan_begin() and rma_scan_end()
 	struct InFlight {
 		const rma_db	*db = nullptr;
 		const Layout	*lay = nullptr;
-		int	inst = 0, grid = 0, tile_bytes = 0;
-		size_t	lds = 0;
-		bool	lean = false, grouped = false;
+		rma::LaunchPlan	plan;
 	}	fly;
 	// what the last scan left on the device, in order (rma_scan_end): for rma_gather_hits()
 	const int32_t	*d_last = nullptr;
@@ -318,31 +248,6 @@ hipError_t rmk_launch_search( int inst, int grid, size_t lds, hipStream_t s, con
 	return hipErrorInvalidValue;
 }
 
-// LDS of one search workgroup: program image | queue | tile | 6 bit vectors | lean records
-static size_t search_lds_bytes( int prog_bytes, const rmd_program_t &dp, int tile_t, bool lean, int qcap, int group = 1, bool flush = false )
-{
-	const int	tile_bytes = tile_t + dp.w_winsize + dp.lmargin + dp.rmargin + 80;
-	// (bit vectors of a tile: the literal's, five per pair-row set, four of a leading 4-plex' strand filter, five more when a triplex follows it)
-	// (lean with a look-ahead chain: one more -- the start positions that remain; the chain's other vectors
-	// borrow the place of the search records, which pass A does not use)
-	// (... and five when the descriptor has a best literal: where each base stands, for the literal's occurrence vector)
-	const size_t	pb_bytes = ( ( lean ? 6 + ( ( dp.chain.on || dp.lit_re >= 0 ) && group == 1 ? 1 : 0 ) : 1 + 5 * size_t( dp.n_rowsets ) + ( dp.q1f.on ? ( dp.q1f.t_on ? 9 : 4 ) : 0 ) + ( dp.lit_re >= 0 ? 1 : 0 ) ) +
-			( dp.lit_re >= 0 && group == 1 ? 5 : 0 ) ) *
-		( size_t( tile_bytes + 63 ) / 64 + 3 ) * sizeof( unsigned long long );
-	size_t	lds = size_t( prog_bytes ) + size_t( qcap ) * sizeof( unsigned ) +
-		size_t( group ) * ( ( ( size_t( tile_bytes ) + 15 ) & ~size_t( 15 ) ) + pb_bytes );
-	// (the instance that walks nothing has no records: only the look-ahead chain's ten working vectors, which elsewhere borrow their place)
-	if( flush )
-		lds += dp.chain.on ? size_t( 10 ) * ( size_t( tile_bytes + 63 ) / 64 + 3 ) * sizeof( unsigned long long ) : 0;
-	else
-		lds += lean ? size_t( dp.n_searches ) * SEARCH_BLOCK * LEAN_REC_BYTES : size_t( dp.n_rec_dwords ) * GENERAL_BLOCK * 4;
-	if( lean && group > 1 && dp.lit_re >= 0 )	// (groups: the literal's five vectors once per wave, behind the records)
-		lds += 8 + size_t( SEARCH_BLOCK / 64 ) * 6 * ( size_t( tile_bytes + 63 ) / 64 + 3 ) * sizeof( unsigned long long );	// (the sixth: the literal's start positions)
-	if( !lean && dp.split_s >= 0 )		// resume states of the levels up to the split level, queue of continuations
-		lds += size_t( dp.split_s + 1 ) * GENERAL_BLOCK * 8 + size_t( DEEP_QUEUE ) * ( 2 + 2 * ( dp.split_s + 1 ) ) * 4;
-	return lds;
-}
-
 extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_t *efn, int device,
 	rma_scanner_t **out, char *err, size_t errlen )
 {
@@ -374,13 +279,6 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 			snprintf( err, errlen, "the program has efn() call sites but no energy tables were given" );
 			return 1;
 		}
-	}
-	for( int k = 0; k < sc->dprog.n_searches; k++ ){
-		const rmd_elem_t	&e = sc->dprog.elems[ sc->dprog.searches[ k ] ];
-		if( e.type == RMA_T_H5 && !e.proper )
-			sc->kinds |= RMD_KIND_PK;
-		if( e.type == RMA_T_P5 || e.type == RMA_T_T1 || e.type == RMA_T_Q1 )
-			sc->kinds |= RMD_KIND_TQ;
 	}
 	sc->device = device;
 	HIPCHK( hipSetDevice( device ) );
@@ -414,121 +312,10 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 	HIPCHK( hipGetDeviceProperties( &prop, device ) );
 	sc->grid_blocks = prop.multiProcessorCount * 8;
 	// (the general instances run workgroups of one wave, four times as many, on tiles a quarter the size)
-	const int	per_wave0 = sc->dprog.lean_ok ? 1 : SEARCH_BLOCK / GENERAL_BLOCK;
-	sc->spill_blocks = sc->grid_blocks * per_wave0;
-	sc->spill_cap = sc->opt.spill >= 0 ? sc->opt.spill : SPILL_ITEMS / per_wave0;	// (tests: 0 = overflow searched in place)
+	sc->spill_blocks = sc->grid_blocks * rma::wgs_per_wave( sc->dprog );
+	sc->spill_cap = sc->opt.spill >= 0 ? sc->opt.spill : SPILL_ITEMS / rma::wgs_per_wave( sc->dprog );	// (tests: 0 = overflow searched in place)
 	HIPCHK( hipMalloc( &sc->d_spill, std::max<size_t>( size_t( sc->spill_blocks ) * sc->spill_cap, 1 ) * sizeof( unsigned ) ) );
-	if( sc->dprog.lean_ok ){
-		// The search of a tile ends with a few long-running items on a few lanes, so fewer,
-		// larger tiles are better as long as four workgroups still share a CU's 160 KB of LDS
-		// (trna.descr, ms per 100 Mbase: T = 2048 6.97, 4096 5.87, 6144 5.40 with 8-byte records;
-		// 6656 4.38, 9984 3.99 with 6-byte records; one step further only three fit: 5.0) and the
-		// work queue still holds what the pre-filter lets through: on random sequence a start
-		// position yields n_rank * P( first minlen pairs hold, at most lim mispairs ) items.
-		const rmd_program_t	&dp = sc->dprog;
-		const rmd_elem_t	&e0 = dp.elems[ dp.searches[ 0 ] ];
-		double	density = 1.0;
-		if( e0.type == RMA_T_H5 && e0.pairset >= 0 && e0.minlen >= 1 ){
-			const uint32_t	m2 = rmd_pairsets( &dp )[ e0.pairset ].mat2;
-			int	np = 0;
-			for( int a = 0; a < 4; a++ )
-				for( int b = 0; b < 4; b++ )
-					np += ( m2 >> ( a * 5 + b ) ) & 1;
-			const double	pp = np / 16.0;
-			const int	lim = ( e0.ends & RMA_5PAIRED ) ? e0.mplim : std::max( e0.mplim, 1 );
-			double	p = 0, comb = 1;
-			for( int m = 0; m <= lim && m <= e0.minlen; m++ ){
-				p += comb * std::pow( pp, e0.minlen - m ) * std::pow( 1 - pp, m );
-				comb = comb * ( e0.minlen - m ) / ( m + 1 );
-			}
-			const int	w = dp.w_winsize;
-			const int	n_rank = ( e0.maxglen != RMA_UNBOUNDED && e0.maxglen < w ? e0.maxglen : w ) - e0.minglen + 1;
-			density = std::min( 1.0, p ) * std::max( 1, n_rank );
-		}
-		if( dp.lit_re >= 0 ){
-			// ... and only where the best literal occurs at an allowed offset
-			const rmd_regex_t	&lre = rmd_regexes( &dp )[ dp.lit_re ];
-			double	pl = 1.0;
-			for( int j = 0; j < lre.n_states; j++ ){
-				int	n = 0;
-				for( int c = 0; c < 4; c++ )
-					n += int( ( lre.accept[ c ] >> j ) & 1 );
-				pl *= n / 4.0;
-			}
-			density *= std::min( 1.0, pl * ( dp.lit_hi - dp.lit_lo + 1 ) );
-		}
-		const size_t	budget = ( 160 * 1024 ) / SEARCH_WAVES_PER_SIMD - 1152;	// (static __shared__: the waves' buffers of start positions that passed the look-ahead, 1 KB, and 40 bytes)
-		// What the LDS queue cannot hold spills to HBM at 4 bytes per item, so LDS goes to the tile
-		// first and the queue gets what is left, up to the expected number of items (trna.descr:
-		// queue 1024 / T 9984 3.99 ms, 512 / 11008 3.94, 256 / 11520 3.91 -- the last spills a
-		// third of its items for that 1 %: the queue starts at 512).  A tile should still not
-		// produce more than half the spill area on average.
-		const int	q_min = 512;
-		sc->tile_t = 2048;
-		for( int t = 16384; t >= 2048; t -= 256 )
-			if( search_lds_bytes( sc->prog_bytes, dp, t, true, q_min ) <= budget &&
-				density * t * 1.1 <= q_min + std::max( sc->spill_cap, 2 * 512 ) / 2 ){
-				sc->tile_t = t;
-				break;
-			}
-		sc->qcap = q_min;
-		const int	q_want = int( std::min( 8192.0, std::ceil( density * sc->tile_t * 1.2 / 256 ) * 256 ) );
-		while( sc->qcap + 256 <= q_want && search_lds_bytes( sc->prog_bytes, dp, sc->tile_t, true, sc->qcap + 256 ) <= budget )
-			sc->qcap += 256;
-		// The pooled instance that walks nothing (RMK_LEAN_FLUSH: every survivor of pass A' goes to the drain kernel's list):
-		// FLUSH_WAVES_PER_SIMD workgroups a CU, tiles as large as its smaller share of LDS holds without the search records.
-		// For descriptors with a look-ahead chain -- a few dozen long walks per workgroup, which the drain kernel takes anyway;
-		// hundreds of cheap items (ire.descr, mp.ends.descr) are walked best where they are found.
-		// (sc->flush: it can run; use_flush(): the options of the moment want it)
-		sc->flush = ( dp.w_winsize + dp.lmargin + dp.rmargin + 14 ) / 8 <= 32;
-		if( sc->flush ){
-			const size_t	budget_f = ( 160 * 1024 ) / FLUSH_WAVES_PER_SIMD - 1152;
-			sc->tile_t_flush = 0;
-			// (no larger than one pass of the workgroup's 256 lanes decodes, 32 bases a lane: profiles/flush_matrix.sh -- tiles of
-			// 7936 positions 0.639 ms, of 8192, a second pass for ten lanes, 0.757; of 10752 0.658)
-			const int	t_one = ( 254 * 32 - 61 - ( dp.w_winsize + dp.lmargin + dp.rmargin ) ) / 256 * 256;
-			for( int t = std::max( 2048, std::min( 16384, t_one ) ); t >= 2048; t -= 256 )
-				if( search_lds_bytes( sc->prog_bytes, dp, t, true, q_min, 1, true ) <= budget_f &&
-					density * t * 1.1 <= q_min + std::max( sc->spill_cap, 2 * 512 ) / 2 ){
-					sc->tile_t_flush = t;
-					break;
-				}
-			sc->qcap_flush = q_min;
-			const int	q_want_f = int( std::min( 8192.0, std::ceil( density * sc->tile_t_flush * 1.2 / 256 ) * 256 ) );
-			while( sc->tile_t_flush > 0 && sc->qcap_flush + 256 <= q_want_f &&
-				search_lds_bytes( sc->prog_bytes, dp, sc->tile_t_flush, true, sc->qcap_flush + 256, 1, true ) <= budget_f )
-				sc->qcap_flush += 256;
-			if( sc->tile_t_flush == 0 )
-				sc->flush = false;
-		}
-	}
-	if( !sc->dprog.lean_ok ){
-		// general instance: workgroups of one wave (GENERAL_BLOCK), as many per SIMD as the registers allow
-		// (GENERAL_WAVES) and as still leave every one of them a tile of a thousand positions or more next
-		// to its records -- 12 bytes per level and lane -- and its queue (what the queue cannot hold spills
-		// to HBM)
-		const int	per_wave = SEARCH_BLOCK / GENERAL_BLOCK;	// workgroups where one of four waves stood
-		sc->qcap = 512 / per_wave < 128 ? 128 : 512 / per_wave;
-		sc->tile_t = 1024;
-		bool	found = false;
-		// (descriptors with triplexes / 4-plexes: two workgroups per SIMD on tiles of three thousand positions
-		// rather than three on a thousand -- a tile's second round then has a few dozen continuations for
-		// its lanes instead of five: qu+tr 19.6 -> 16.7 ms; pk1 and pk_j1+2 are best at 2048, four per SIMD)
-		const int	wg0 = ( sc->kinds & RMD_KIND_TQ ) ? 2 : GENERAL_WAVES( 0 );
-		for( int wg = wg0; wg >= 1 && !found; wg-- ){
-			const size_t	budget = ( 160 * 1024 ) / ( wg * per_wave ) - ( per_wave > 1 ? 1024 : 2560 );	// (static __shared__ -- the pre-filter's wave buffers -- and allocation granules)
-			for( int t = ( per_wave > 1 ? 4096 : 8192 ); t >= ( wg > 1 ? 3072 / per_wave : 1024 / per_wave ); t -= 256 )
-				if( search_lds_bytes( sc->prog_bytes, sc->dprog, t, false, sc->qcap ) <= budget ){
-					sc->tile_t = t;
-					found = true;
-					break;
-				}
-		}
-	}
-	if( sc->opt.qcap >= 64 && sc->opt.qcap <= 16384 )
-		sc->qcap = sc->qcap_flush = ( sc->opt.qcap + 3 ) & ~3;	// (what follows the queue in LDS is read 8 bytes at a time)
-	if( sc->opt.tile > 0 )
-		sc->tile_t = sc->opt.tile;
+	sc->plan = rma::plan_program( *prog, sc->dprog, sc->prog_bytes, sc->spill_cap, sc->opt );
 	// room for the candidates of a few hundred Mbase at the densities of the reference's descriptors
 	// (63 per Mbase for trna.descr); a scan that finds more is repeated into a buffer of the right
 	// size (count-then-emit, rma_scan_end)
@@ -548,28 +335,14 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 extern "C" int rma_scanner_set_option( rma_scanner_t *sc, const char *name, int value, char *err, size_t errlen )
 {
 	const std::string	n = name ? name : "";
-	Options	&o = sc->opt;
-	if( n == "dbg" ) o.dbg = value;
-	else if( n == "pool" ) o.pool = value;
-	else if( n == "pool_min" ) o.pool_min = std::max( 1, value );
-	else if( n == "pool_refill" ) o.pool_refill = value;
-	else if( n == "drain" ) o.drain = value;
-	else if( n == "glist" ) o.glist = std::max( 0, value );
-	else if( n == "drain_waves" ) o.drain_waves = std::max( 0, value );
-	else if( n == "search_wgs" ) o.search_wgs = std::max( 0, value );
-	else if( n == "flush" ) o.flush = value;
-	else if( n == "efn_light" ) o.efn_light = value;
-	else if( n == "host_sort" ) o.host_sort = value;
-	else if( n == "timing" ) o.timing = value;
-	else if( n == "short" ) o.short_force = value;
-	else if( n == "forget_last" ){
+	if( n == "forget_last" ){
 		// (not a switch: the last scan's records are no longer there for rma_gather_hits() -- a rank whose share of a
 		// round is empty sends nothing, whatever the round before left)
 		sc->d_last = nullptr;
 		sc->n_last = 0;
 		sc->last_state = 0;
 		sc->last_relabelled = false;
-	}else{
+	}else if( !sc->opt.set( n, value ) ){
 		snprintf( err, errlen, "rma_scanner_set_option: no option '%s' that can change after creation "
 			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
 		return 1;
@@ -1094,169 +867,25 @@ extern "C" int rma_pack_pin( rma_pack_t *pack, char *err, size_t errlen )
 	return 0;
 }
 
-// the pooled lean instance (see the kernel): when the window of an item, four bits a base, fits the
-// column a lane gets of the tile's place in LDS
-// the pooled instance that walks nothing: where it can run (rma_scanner_create) and the options do not ask for the other one
-static bool use_flush( const rma_scanner_t *sc )
-{
-	const Options	&o = sc->opt;
-	return sc->flush && o.drain != 0 && o.pool != 0 && !( o.dbg & ( 16 | 2048 | 8388608 ) ) &&
-		( o.flush < 0 ? sc->dprog.chain.on != 0 : o.flush != 0 );
-}
-
-static bool pooled_fits( const rma_scanner_t *sc, int tile_t, bool flush = false )
-{
-	const rmd_program_t	&dp = sc->dprog;
-	if( !dp.lean_ok || ( sc->opt.dbg & 16 ) )
-		return false;
-	if( flush )		// (the instance that walks nothing lays out no window: rma_scanner_create asked what the drain kernel asks)
-		return use_flush( sc );
-	const int	tile_bytes = tile_t + dp.w_winsize + dp.lmargin + dp.rmargin + 80;
-	const int	n_dw = ( dp.w_winsize + dp.lmargin + dp.rmargin + 14 ) / 8;
-	const size_t	room = size_t( ( tile_bytes + 15 ) & ~15 ) + size_t( 6 + ( dp.chain.on ? 1 : 0 ) ) * ( ( tile_bytes + 63 ) / 64 + 3 ) * sizeof( unsigned long long );
-	bool	pooled = n_dw <= 32 && size_t( n_dw ) * SEARCH_BLOCK * sizeof( uint32_t ) <= room;
-	if( sc->opt.pool >= 0 )		// 0: pass B tile by tile (tests, profiles/pool_matrix.py)
-		pooled = pooled && sc->opt.pool != 0;
-	return pooled;
-}
-
 // ---------------------------------------------------------------- tilings
-// The launch shape of database db under scanner sc, and its tiling.  Long entries: the scanner's
-// tile, one per workgroup pass.  A database of many short entries (GenBank divisions, transcript
-// sets) never fills such a tile, and a few dozen queue items cannot occupy 256 lanes: it gets small
-// tiles in groups of SHORT_GROUP per workgroup pass (rma_search_kernel<.., G>), if the descriptor is
-// lean and the group fits the LDS budget.
+// The tiling of database db for scanner sc's launch shape (rma::choose_layout): made and uploaded when the
+// scanner first meets the database with that shape, found again afterwards.
 static const Layout *layout_for( rma_scanner_t *sc, const rma_db_t *cdb, char *err, size_t errlen, hipStream_t on )
 {
 	if( on == nullptr )
 		on = sc->stream;
 	rma_db	*db = const_cast<rma_db *>( cdb );
-	int	tile_t = sc->tile_t, qcap = sc->qcap, group = 1;
-	const int	n = db->n_seq;
-	// (cloverleaf-like descriptors -- a look-ahead chain whose first helix is tested jointly with the stem-loop behind
-	// it -- do better tile by tile even there: chain, pass A' and the drain kernel are the one-tile instance's;
-	// trna.descr over the reference's test database x 20: 3.36 against 3.70 ms.  bulge.descr, a chain of one
-	// stem-loop, stays with the groups: 1.57 against 2.30.)
-	bool	grouped = n >= 64 && db->sum_slen / n < SHORT_ENTRY_MEAN && sc->opt.tile == 0 && !( sc->dprog.chain.on && sc->dprog.chain.hn_on );
-	if( sc->opt.short_force >= 0 )		// 0 never, 1 always (tests)
-		grouped = sc->opt.short_force == 1;
-	// Short entries and a descriptor the pooled instance takes: tiles over the concatenation of the entries (round 4)
-	// -- whole start positions only (no slices), entries in order in the packed arrays, positions within 30 bits.
-	const bool	short_db = n >= 64 && db->sum_slen / n < SHORT_ENTRY_MEAN && sc->opt.tile == 0;
-	bool	concat = ( sc->opt.short_force < 0 ? short_db : sc->opt.short_force == 2 ) && n >= 1 &&
-		db->h_pos_lo.empty() && db->ascending && db->padded_bases < ( int64_t( 1 ) << 30 ) &&
-		( pooled_fits( sc, tile_t ) || !sc->dprog.lean_ok || ( sc->opt.dbg & 16 ) ) && !sc->dprog.wide;		// (the pooled lean instance, or a general one)
-	if( concat )
-		grouped = false;
-	// (long entries, a descriptor with a look-ahead chain: the instance that walks nothing, on tiles of its own size)
-	const bool	flush = use_flush( sc ) && !grouped;
-	if( flush ){
-		tile_t = sc->opt.tile > 0 ? sc->opt.tile : sc->tile_t_flush;
-		qcap = sc->qcap_flush;
-	}
-	if( grouped && sc->dprog.lean_ok && !( sc->opt.dbg & 16 ) ){
-		const size_t	budget = ( 160 * 1024 ) / SEARCH_WAVES_PER_SIMD - 64 - SHORT_GROUP * 32;
-		// (tiles of 1024 positions measured slower than of 768 where both fit: mp.ends 1.56 / 1.40 ms)
-		for( int t = 768; t >= 256; t -= 256 ){
-			int	q = 256;	// LDS goes to the slots; what a group queues beyond this spills
-			if( sc->opt.qcap > 0 )	// tests: force the overflow path
-				q = std::max( 64, sc->opt.qcap );
-			if( search_lds_bytes( sc->prog_bytes, sc->dprog, t, true, q, SHORT_GROUP ) <= budget ){
-				tile_t = t;
-				qcap = q;
-				group = SHORT_GROUP;
-				break;
-			}
-		}
-	}
-	const int	strands = sc->prog.chk_both_strs ? 2 : 1, dminlen = sc->prog.dminlen;
-	// A general instance's tile is one wave's, walks and all, for milliseconds: a database of fewer tiles than the device
-	// holds workgroups (eight a CU) gets smaller ones -- down to 256 positions -- so that a short database, or one heavy
-	// region of it, is not the work of a handful of waves (a 6 000 base database of repeats: 3 tiles, 90 s).
-	if( !sc->dprog.lean_ok && group == 1 && sc->opt.tile == 0 ){
-		const int64_t	positions = ( concat ? db->padded_bases : db->sum_slen ) * strands, slots = sc->grid_blocks;
-		if( positions / tile_t < slots )
-			tile_t = int( std::min<int64_t>( tile_t, std::max<int64_t>( 256, ( positions / slots + 63 ) / 64 * 64 ) ) );
-	}
+	const rma::DbShape	shape{ db->n_seq, db->sum_slen, db->padded_bases, !db->h_pos_lo.empty(), db->ascending };
+	const rma::LayoutKey	key = rma::choose_layout( sc->plan, sc->opt, shape, sc->grid_blocks / 8 );
 	std::lock_guard<std::mutex>	lk( db->mu );
 	for( auto &l : db->layouts )
-		if( l->tile_t == tile_t && l->dminlen == dminlen && l->strands == strands && l->group == group && l->qcap == qcap && l->concat == concat && l->flush == flush )
+		if( static_cast<const rma::LayoutKey &>( *l ) == key )
 			return l.get();
 	std::unique_ptr<Layout>	l( new Layout );
-	l->tile_t = tile_t;
-	l->dminlen = dminlen;
-	l->strands = strands;
-	l->group = group;
-	l->qcap = qcap;
-	l->concat = concat;
-	l->flush = flush;
-	l->concat_bases = db->padded_bases;
-	std::vector<int64_t>	&tile_start = l->h_tile_start;
-	tile_start.assign( size_t( n ) + 1, 0 );
-	if( concat ){
-		// one "entry" of padded_bases bases per strand; a tile's line names the entries its start positions fall into
-		// (RMK_META_SEQ: the first, RMK_META_PAD: how many -- the search of an item's entry stays within them)
-		const int64_t	total = db->padded_bases, nsz = total - dminlen + 1;
-		const int64_t	nt = nsz > 0 ? ( nsz + tile_t - 1 ) / tile_t : 0;
-		l->n_tiles = nt * strands;
-		tile_start[ n ] = l->n_tiles;		// (nothing reads the per-entry sums of such a tiling)
-		l->h_tile_seq.assign( 1, 0 );
-		std::vector<int32_t>	&meta = l->h_tile_meta;
-		meta.assign( size_t( std::max<int64_t>( l->n_tiles, 1 ) ) * RMK_META_WORDS, 0 );
-		const std::vector<int64_t>	&bo = db->h_base_off;
-		auto entry_at = [ & ]( int64_t g ) -> int {	// the last entry that begins at or before base g of the arrays
-			const int	k = int( std::upper_bound( bo.begin(), bo.end(), g ) - bo.begin() ) - 1;
-			return k < 0 ? 0 : k;
-		};
-		for( int64_t t = 0; t < l->n_tiles; t++ ){
-			const int	comp = int( t / nt );
-			const int64_t	z0 = ( t % nt ) * tile_t, z1 = std::min<int64_t>( z0 + tile_t, nsz ) - 1;
-			const int64_t	g_lo = comp ? total - 1 - z1 : z0, g_hi = comp ? total - 1 - z0 : z1;
-			const int	k_lo = entry_at( g_lo ), k_hi = entry_at( g_hi );
-			int32_t	*m = &meta[ size_t( t ) * RMK_META_WORDS ];
-			m[ RMK_META_SEQ ] = k_lo;
-			m[ RMK_META_COMP ] = comp;
-			m[ RMK_META_Z0 ] = int32_t( z0 );
-			m[ RMK_META_SLEN ] = int32_t( total );
-			m[ RMK_META_OFF_LO ] = m[ RMK_META_OFF_HI ] = 0;
-			m[ RMK_META_POS_HI ] = 0x7fffffff;
-			m[ RMK_META_PAD ] = k_hi - k_lo + 1;
-		}
-	}else
-	for( int i = 0; i < n; i++ ){
-		int64_t	nsz = int64_t( db->h_slen[ i ] ) - dminlen + 1;	// start positions of a strand
-		if( !db->h_pos_lo.empty() )
-			nsz = std::min<int64_t>( nsz, db->h_pos_hi[ i ] ) - db->h_pos_lo[ i ];
-		const int64_t	nt = nsz > 0 ? ( nsz + tile_t - 1 ) / tile_t : 0;
-		tile_start[ i + 1 ] = tile_start[ i ] + nt * strands;
-	}
-	l->n_tiles = tile_start[ n ];
-	std::vector<int32_t>	&tile_seq = l->h_tile_seq;
-	if( !concat ){
-		tile_seq.resize( size_t( std::max<int64_t>( l->n_tiles, 1 ) ) );
-		for( int i = 0; i < n; i++ )
-			for( int64_t t = tile_start[ i ]; t < tile_start[ i + 1 ]; t++ )
-				tile_seq[ size_t( t ) ] = i;
-	}
-	std::vector<int32_t>	&tile_meta = l->h_tile_meta;
-	if( group == 1 && !concat ){
-		tile_meta.assign( size_t( std::max<int64_t>( l->n_tiles, 1 ) ) * RMK_META_WORDS, 0 );
-		for( int i = 0; i < n; i++ ){
-			const int64_t	per_strand = ( tile_start[ i + 1 ] - tile_start[ i ] ) / strands;
-			const int	lo = db->h_pos_lo.empty() ? 0 : db->h_pos_lo[ i ], hi = db->h_pos_hi.empty() ? 0x7fffffff : db->h_pos_hi[ i ];
-			for( int64_t t = tile_start[ i ]; t < tile_start[ i + 1 ]; t++ ){
-				int32_t	*m = &tile_meta[ size_t( t ) * RMK_META_WORDS ];
-				const int64_t	local = t - tile_start[ i ];
-				m[ RMK_META_SEQ ] = i;
-				m[ RMK_META_COMP ] = int32_t( local / per_strand );
-				m[ RMK_META_Z0 ] = lo + int32_t( local % per_strand ) * tile_t;
-				m[ RMK_META_SLEN ] = db->h_slen[ i ];
-				m[ RMK_META_OFF_LO ] = int32_t( uint64_t( db->h_base_off[ i ] ) & 0xffffffffu );
-				m[ RMK_META_OFF_HI ] = int32_t( uint64_t( db->h_base_off[ i ] ) >> 32 );
-				m[ RMK_META_POS_HI ] = hi;
-			}
-		}
-	}
+	static_cast<rma::LayoutKey &>( *l ) = key;
+	rma::make_tiling( key, db->h_slen, db->h_base_off, db->h_pos_lo, db->h_pos_hi, db->padded_bases, l.get() );
+	const std::vector<int64_t>	&tile_start = l->h_tile_start;
+	const std::vector<int32_t>	&tile_seq = l->h_tile_seq, &tile_meta = l->h_tile_meta;
 	const size_t	o_seq = align256( tile_start.size() * 8 ), o_meta = align256( o_seq + tile_seq.size() * 4 );
 	hipError_t	e = db->ctx->take( o_meta + tile_meta.size() * 4, &l->blk );
 	// On the stream given: the upload stream when the database is being made for a scanner (its first
@@ -1317,6 +946,43 @@ static DbView view_of( const rma_db *db, const Layout *l )
 }
 
 // ---------------------------------------------------------------- scans
+// Work areas that grow when a scan asks for more; what was there is freed first.
+// The spill area: room for `need` items a workgroup.
+static int grow_spill( rma_scanner_t *sc, unsigned long long need, char *err, size_t errlen )
+{
+	( void )hipFree( sc->d_spill );
+	sc->d_spill = nullptr;
+	sc->spill_cap = int( need ) + 1024;
+	HIPCHK( hipMalloc( &sc->d_spill, size_t( sc->spill_blocks ) * sc->spill_cap * sizeof( unsigned ) ) );
+	return 0;
+}
+
+// The pooled instance's d_pool: the drain kernel's list of `list` items, then `cap` items of every workgroup's pool.
+static int grow_pool( rma_scanner_t *sc, int list, int cap, char *err, size_t errlen )
+{
+	( void )hipFree( sc->d_pool );
+	sc->d_pool = nullptr;
+	sc->pool_cap = sc->glist_cap = 0;
+	HIPCHK( hipMalloc( &sc->d_pool, ( size_t( list ) + size_t( sc->grid_blocks ) * cap ) * RMK_POOL_WORDS * sizeof( unsigned ) ) );
+	sc->pool_cap = cap;
+	sc->glist_cap = list;
+	return 0;
+}
+
+// The pinned staging buffer of the records (the copy back is a single DMA): twice `words` when they do not fit.
+static int grow_h_raw( rma_scanner_t *sc, size_t words, char *err, size_t errlen )
+{
+	if( words <= sc->h_raw_cap )
+		return 0;
+	if( sc->h_raw != nullptr )
+		( void )hipHostFree( sc->h_raw );
+	sc->h_raw = nullptr;
+	sc->h_raw_cap = 0;
+	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_raw ), words * 2 * sizeof( int32_t ), hipHostMallocDefault ) );
+	sc->h_raw_cap = words * 2;
+	return 0;
+}
+
 static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
 {
 	const rma_scanner::InFlight	&f = sc->fly;
@@ -1326,21 +992,20 @@ static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
 	a.prog_bytes = sc->prog_bytes;
 	a.qcap = f.lay->qcap;
 	a.db = view_of( f.db, f.lay );
-	const bool	listed = f.inst == RMK_LEAN_POOL || f.inst == RMK_LEAN_CONCAT || f.inst == RMK_LEAN_FLUSH || f.inst == RMK_LEAN_CONCAT_FLUSH;
-	const bool	drain = listed && sc->glist_cap > 0;
+	const bool	listed = f.plan.listed, drain = listed && sc->glist_cap > 0;
 	a.hb = HitBuf{ sc->d_hits, sc->d_counters, sc->d_counters + 1, sc->hit_cap, sc->d_spill, sc->spill_cap, sc->d_pool, sc->pool_cap,
 		sc->opt.pool_min, sc->opt.pool_refill, listed ? sc->glist_cap : 0 };
-	a.tile_bytes = f.tile_bytes;
+	a.tile_bytes = f.plan.tile_bytes;
 	a.dbg = sc->opt.dbg | ( sc->whole_items ? 2097152 : 0 );
 	HIPCHK( hipEventRecord( sc->ev[ 0 ], sc->stream ) );
-	HIPCHK( rmk_launch_search( f.inst, f.grid, f.lds, sc->stream, a ) );
+	HIPCHK( rmk_launch_search( f.plan.inst, f.plan.grid, f.plan.lds, sc->stream, a ) );
 	sc->drained = drain;
 	sc->searched = true;
 	sc->efn_ran = false;
 	if( drain ){	// the items the search kernel left in the list: walked by a kernel of their own
 		HIPCHK( hipEventRecord( sc->ev[ 4 ], sc->stream ) );
-		a.tile_bytes = sc->drain_nib;
-		HIPCHK( rmk_launch_lean_drain( sc->drain_grid, sc->drain_lds, sc->stream, a ) );
+		a.tile_bytes = f.plan.drain_nib;
+		HIPCHK( rmk_launch_lean_drain( f.plan.drain_grid, f.plan.drain_lds, sc->stream, a ) );
 	}
 	HIPCHK( hipEventRecord( sc->ev[ 1 ], sc->stream ) );
 	// [0] candidates, [3] queue overflow of the general instance, [RMK_GCTL] items reserved in the drain kernel's list,
@@ -1357,12 +1022,12 @@ static void debug_report( rma_scanner_t *sc, unsigned long long count )
 	unsigned long long	q = 0;
 	( void )hipMemcpy( &q, sc->d_counters + 2, sizeof( q ), hipMemcpyDeviceToHost );
 	fprintf( stderr, "[dbg] queued items: %llu, candidates %llu (tile %d x %d, queue %d, LDS %zu, %lld tiles)\n", q, count,
-		f.lay->tile_t, f.grouped ? f.lay->group : 1, f.lay->qcap, f.lds, ( long long )f.lay->n_tiles );
-	if( ( dbg & 1048576 ) && f.lean ){
+		f.lay->tile_t, f.plan.grouped ? f.lay->group : 1, f.lay->qcap, f.plan.lds, ( long long )f.lay->n_tiles );
+	if( ( dbg & 1048576 ) && f.plan.lean ){
 		unsigned long long	tl[ 5 ];
 		( void )hipMemcpy( tl, sc->d_counters + 1 + 87, sizeof( tl ), hipMemcpyDeviceToHost );
 		const double	t0 = double( ~tl[ 1 ] ), g = double( tl[ 0 ] );
-		fprintf( stderr, "[dbg] workgroups that had tiles (%.0f of %d): out of tiles after %.1f us (mean), done after %.1f us (mean), %.1f us (last)\n", g, f.grid,
+		fprintf( stderr, "[dbg] workgroups that had tiles (%.0f of %d): out of tiles after %.1f us (mean), done after %.1f us (mean), %.1f us (last)\n", g, f.plan.grid,
 			( double( tl[ 2 ] ) / g - t0 ) * 0.01, ( double( tl[ 4 ] ) / g - t0 ) * 0.01, ( double( tl[ 3 ] ) - t0 ) * 0.01 );
 	}
 	if( ( dbg & 536870912 ) && sc->drained ){
@@ -1382,12 +1047,12 @@ static void debug_report( rma_scanner_t *sc, unsigned long long count )
 			tot += double( ph[ i ] );
 		unsigned long long	lv[ 80 ];
 		( void )hipMemcpy( lv, sc->d_counters + 16, sizeof( lv ), hipMemcpyDeviceToHost );
-		const bool	listed = f.inst == RMK_LEAN_POOL || f.inst == RMK_LEAN_CONCAT || f.inst == RMK_LEAN_FLUSH || f.inst == RMK_LEAN_CONCAT_FLUSH;
-		if( f.lean && !( listed && sc->glist_cap > 0 ) )
+		const bool	lean = f.plan.lean, drained = f.plan.listed && sc->glist_cap > 0;
+		if( lean && !drained )
 			fprintf( stderr, "[dbg] pool sessions: %.3g wave cycles popping (%.0f per round), %.3g stepping (%.0f per step)\n",
 				double( lv[ 4 ] ), lv[ 0 ] ? double( lv[ 4 ] ) / lv[ 0 ] : 0.0, double( lv[ 5 ] ), lv[ 2 ] ? double( lv[ 5 ] ) / lv[ 2 ] : 0.0 ),
 			fprintf( stderr, "[dbg] longest step %.3g cycles, most stepping in one wave (one session) %.3g cycles\n", double( lv[ 6 ] ), double( lv[ 7 ] ) );
-		if( listed && sc->glist_cap > 0 ){
+		if( drained ){
 			// (the drain kernel's items)
 			unsigned long long	g[ 2 ];
 			( void )hipMemcpy( g, sc->d_counters + RMK_GCTL, sizeof( g ), hipMemcpyDeviceToHost );
@@ -1410,7 +1075,7 @@ static void debug_report( rma_scanner_t *sc, unsigned long long count )
 				if( lv[ 45 + kk ] )
 					fprintf( stderr, " %llu,%.0f", lv[ 45 + kk ], double( lv[ 61 + kk ] ) / lv[ 45 + kk ] );
 			fprintf( stderr, "\n" );
-		}else if( f.lean ){
+		}else if( lean ){
 			fprintf( stderr, "[dbg] steps by log2( cycles ):" );
 			for( int b = 8; b < 32; b++ )
 				if( lv[ 8 + b ] )
@@ -1422,11 +1087,11 @@ static void debug_report( rma_scanner_t *sc, unsigned long long count )
 					fprintf( stderr, " %d:%llu,%.0f", kk, lv[ 61 + kk ], double( lv[ 45 + kk ] ) / lv[ 61 + kk ] );
 			fprintf( stderr, "\n" );
 		}
-		if( f.lean && !( listed && sc->glist_cap > 0 ) )
+		if( lean && !drained )
 			fprintf( stderr, "[dbg] pass B: %llu pop rounds of %.1f lanes, %llu steps of %.1f lanes; wave cycles popping %.1f%%, stepping %.1f%%\n",
 				lv[ 0 ], lv[ 0 ] ? double( lv[ 1 ] ) / lv[ 0 ] : 0.0, lv[ 2 ], lv[ 2 ] ? double( lv[ 3 ] ) / lv[ 2 ] : 0.0,
 				100.0 * lv[ 4 ] / double( lv[ 4 ] + lv[ 5 ] + 1 ), 100.0 * lv[ 5 ] / double( lv[ 4 ] + lv[ 5 ] + 1 ) );
-		for( int kk = 0; kk < dp.n_searches && kk < 32 && !f.lean; kk++ )
+		for( int kk = 0; kk < dp.n_searches && kk < 32 && !lean; kk++ )
 			fprintf( stderr, "[dbg] level %2d (element %2d, type %d): %llu wave rounds, %.1f lanes each\n", kk, dp.searches[ kk ],
 				dp.elems[ dp.searches[ kk ] ].type, lv[ 2 * kk ], lv[ 2 * kk ] ? double( lv[ 2 * kk + 1 ] ) / lv[ 2 * kk ] : 0.0 );
 		fprintf( stderr, "[dbg] wave cycles: decode %.1f%%, literal %.1f%%, rows %.1f%%, pre-filter %.1f%%, search %.1f%%, waiting %.1f%%\n",
@@ -1472,28 +1137,14 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 			mdb->busy.erase( std::find( mdb->busy.begin(), mdb->busy.end(), sc ) );
 			sc->fly.db = nullptr;
 		} } }	unfly{ sc, true };
+	f.plan = rma::LaunchPlan();
 	if( lay->n_tiles == 0 ){
-		f.grid = 0;
 		unfly.armed = false;
 		return 0;
 	}
-	const rmd_program_t	&dp = sc->dprog;
-	f.lean = dp.lean_ok && !( sc->opt.dbg & 16 );
-	f.grouped = f.lean && lay->group > 1;
-	f.tile_bytes = lay->tile_t + dp.w_winsize + dp.lmargin + dp.rmargin + 80;
-	f.lds = search_lds_bytes( sc->prog_bytes, dp, lay->tile_t, f.lean, lay->qcap, f.grouped ? SHORT_GROUP : 1, f.lean && lay->flush );
-	if( f.lds > 150 * 1024 ){
-		snprintf( err, errlen, "window of %d bases does not fit the LDS tile (%zu bytes needed)", dp.w_winsize, f.lds );
+	if( rma::plan_launch( *lay, lay->n_tiles, sc->plan, sc->opt, sc->grid_blocks / 8, &f.plan, err, errlen ) )
 		return 1;
-	}
-	// the pooled lean instance (see the kernel): when the window of an item, four bits a base, fits the
-	// column a lane gets of the tile's place in LDS
-	const bool	pooled = f.lean && !f.grouped && pooled_fits( sc, lay->tile_t, lay->flush );
-	if( lay->concat && f.lean && !pooled ){
-		snprintf( err, errlen, "a tiling over the concatenation of the entries is for the pooled lean instance and the general ones" );	// (layout_for asks pooled_fits too)
-		return 1;
-	}
-	if( pooled ){
+	if( f.plan.pooled ){
 		// The list of the drain kernel: room for an item per 32 bases (trna.descr leaves one per 70 before the
 		// stem-loop tests and one per 4500 after them); a workgroup that finds it full walks its own items.
 		int	want = !sc->opt.drain ? 0 : sc->opt.glist > 0 ? sc->opt.glist :
@@ -1503,36 +1154,10 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 		const int	cap = sc->opt.pool_min + lay->qcap + sc->spill_cap;
 		if( cap > sc->pool_cap || want > sc->glist_cap || ( want == 0 && sc->glist_cap != 0 ) || ( sc->opt.glist > 0 && want != sc->glist_cap && !lay->flush ) ){
 			HIPCHK( hipStreamSynchronize( sc->stream ) );
-			( void )hipFree( sc->d_pool );
-			sc->d_pool = nullptr;
-			const int	cap1 = std::max( cap, sc->pool_cap );
-			sc->pool_cap = sc->glist_cap = 0;
-			HIPCHK( hipMalloc( &sc->d_pool, ( size_t( want ) + size_t( sc->grid_blocks ) * cap1 ) * RMK_POOL_WORDS * sizeof( unsigned ) ) );
-			sc->pool_cap = cap1;
-			sc->glist_cap = want;
+			if( grow_pool( sc, want, std::max( cap, sc->pool_cap ), err, errlen ) )
+				return 1;
 		}
-		// the drain kernel: one wave per workgroup -- the program, a window column and the records of 64 lanes
-		sc->drain_nib = ( dp.w_winsize + dp.lmargin + dp.rmargin + 14 ) / 8;	// (n_dw above: at most 32)
-		sc->drain_lds = size_t( sc->prog_bytes ) + size_t( sc->drain_nib + dp.n_searches ) * 64 * sizeof( uint32_t ) + size_t( dp.n_searches ) * 64 * sizeof( uint16_t );
-		const int	per_cu = int( std::min<size_t>( 4 * SEARCH_WAVES_PER_SIMD, ( 160 * 1024 ) / ( sc->drain_lds + 64 ) ) );
-		sc->drain_grid = ( sc->grid_blocks / 8 ) * std::max( 1, sc->opt.drain_waves > 0 ? std::min( sc->opt.drain_waves, per_cu ) : per_cu );
 	}
-	// the kernel instance: lean (pooled, one tile or a group of small ones per pass), or the general one
-	// compiled for the kinds of element the descriptor has
-	f.inst = pooled ? ( lay->concat ? ( lay->flush ? RMK_LEAN_CONCAT_FLUSH : RMK_LEAN_CONCAT ) : lay->flush ? RMK_LEAN_FLUSH : RMK_LEAN_POOL ) : f.grouped ? RMK_LEAN_GROUP : f.lean ? RMK_LEAN_TILE :
-		dp.wide ? RMK_GEN_WIDE :
-		lay->concat ? ( sc->kinds == 0 ? RMK_GEN_PLAIN_CONCAT : sc->kinds == RMD_KIND_PK ? RMK_GEN_PK_CONCAT : sc->kinds == RMD_KIND_TQ ? RMK_GEN_TQ_CONCAT : RMK_GEN_PKTQ_CONCAT ) :
-		sc->kinds == 0 ? RMK_GEN_PLAIN : sc->kinds == RMD_KIND_PK ? RMK_GEN_PK : sc->kinds == RMD_KIND_TQ ? RMK_GEN_TQ : RMK_GEN_PKTQ;
-	const int64_t	n_units = f.grouped ? ( lay->n_tiles + SHORT_GROUP - 1 ) / SHORT_GROUP : lay->n_tiles;
-	f.grid = int( std::min<int64_t>( n_units, f.lean ? sc->grid_blocks : sc->spill_blocks ) );
-	if( f.lean && sc->opt.search_wgs > 0 )		// (option search_wgs: workgroups of a lean search kernel per CU -- room for another scanner's drain kernel beside it)
-		f.grid = std::min( f.grid, sc->opt.search_wgs * ( sc->grid_blocks / 8 ) );
-	else if( f.inst == RMK_LEAN_FLUSH || f.inst == RMK_LEAN_CONCAT_FLUSH )
-		// The instance that walks nothing is compiled for five workgroups a CU (96 registers, a fifth of the LDS) and runs
-		// four: a fifth measures the same (0.642 against 0.639 ms), and what it would take -- 33 KB of LDS, a wave's registers
-		// on every SIMD -- is where the drain kernel and the energy kernel of the scanner that had the step before run
-		// meanwhile (two scanners in turns).
-		f.grid = std::min( f.grid, FLUSH_WGS_PER_CU * ( sc->grid_blocks / 8 ) );
 	// the database's upload and the tiling's, on the device's upload stream, come first
 	HIPCHK( hipStreamWaitEvent( sc->stream, db->ready, 0 ) );
 	HIPCHK( hipStreamWaitEvent( sc->stream, lay->ready, 0 ) );
@@ -1548,7 +1173,7 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 {
 	rma_scanner::InFlight	&f = sc->fly;
 	*n_hits = 0;
-	if( f.grid == 0 )
+	if( f.plan.grid == 0 )
 		return 0;
 	const rmd_program_t	&dp = sc->dprog;
 	unsigned long long	count = 0;
@@ -1558,7 +1183,7 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 		if( sc->opt.dbg )
 			debug_report( sc, count );
 		bool	again = false;
-		if( !f.lean ){
+		if( !f.plan.lean ){
 			// the general instance does not search queue overflow in place: a larger spill area, and again
 			const unsigned long long	need = sc->h_ctr[ 3 ];
 			if( need > 0 ){
@@ -1566,14 +1191,12 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 					snprintf( err, errlen, "work queue overflow after regrow (%llu items in a tile)", need );
 					return 1;
 				}
-				( void )hipFree( sc->d_spill );
-				sc->d_spill = nullptr;
-				sc->spill_cap = int( need ) + 1024;
-				HIPCHK( hipMalloc( &sc->d_spill, size_t( sc->spill_blocks ) * sc->spill_cap * sizeof( unsigned ) ) );
+				if( grow_spill( sc, need, err, errlen ) )
+					return 1;
 				again = true;
 			}
 		}
-		if( f.inst == RMK_LEAN_FLUSH || f.inst == RMK_LEAN_CONCAT_FLUSH ){
+		if( f.plan.walks_nothing ){
 			// the instance that walks nothing reports what it had no room for -- a tile's items beyond queue and spill area, the
 			// list's items beyond its end -- and the scan is repeated with room for them
 			const unsigned long long	q_need = sc->h_ctr[ RMK_GCTL + 2 ], l_need = sc->h_ctr[ RMK_GCTL ];
@@ -1582,10 +1205,8 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 				return 1;
 			}
 			if( q_need > 0 ){
-				( void )hipFree( sc->d_spill );
-				sc->d_spill = nullptr;
-				sc->spill_cap = int( q_need ) + 1024;
-				HIPCHK( hipMalloc( &sc->d_spill, size_t( sc->spill_blocks ) * sc->spill_cap * sizeof( unsigned ) ) );
+				if( grow_spill( sc, q_need, err, errlen ) )
+					return 1;
 				again = true;
 			}
 			if( l_need > ( unsigned long long )sc->glist_cap ){
@@ -1593,18 +1214,13 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 					snprintf( err, errlen, "%llu items for the drain kernel's list: more than it can be made to hold", l_need );
 					return 1;
 				}
-				( void )hipFree( sc->d_pool );
-				sc->d_pool = nullptr;
 				sc->glist_need = int( l_need + l_need / 8 ) + 1024;
-				const int	cap1 = sc->pool_cap;
-				sc->pool_cap = sc->glist_cap = 0;
-				HIPCHK( hipMalloc( &sc->d_pool, ( size_t( sc->glist_need ) + size_t( sc->grid_blocks ) * cap1 ) * RMK_POOL_WORDS * sizeof( unsigned ) ) );
-				sc->pool_cap = cap1;
-				sc->glist_cap = sc->glist_need;
+				if( grow_pool( sc, sc->glist_need, sc->pool_cap, err, errlen ) )
+					return 1;
 				again = true;
 			}
 		}
-		if( f.lean && sc->h_ctr[ 3 ] != 0 && !sc->whole_items ){
+		if( f.plan.lean && sc->h_ctr[ 3 ] != 0 && !sc->whole_items ){
 			// a piece of an item found more candidates than the order words of the pieces leave room for
 			// (PIECE_ORDER_BITS): once more, and from now on, with whole items
 			sc->whole_items = true;
@@ -1644,10 +1260,7 @@ static int launch_efn( rma_scanner_t *sc, int64_t count, char *err, size_t errle
 		sc->have_efn ? sc->d_t16 : nullptr, sc->d_tlkey, sc->d_loginc, sc->d_efn2 };
 	sc->efn_ran = true;
 	HIPCHK( hipEventRecord( sc->ev[ 2 ], sc->stream ) );
-	// (behind the search instance that walks nothing: workgroups of one wave that find room next to another scanner's search
-	// kernel -- the staged form's 136 KB of LDS wait until that kernel is through)
-	const bool	light = !sc->dprog.efn_big && ( sc->opt.efn_light < 0 ? ( sc->fly.inst == RMK_LEAN_FLUSH || sc->fly.inst == RMK_LEAN_CONCAT_FLUSH ) : sc->opt.efn_light != 0 );
-	if( light )
+	if( sc->fly.plan.efn_light )
 		HIPCHK( rmk_launch_efn_light( int( std::min<int64_t>( ( count + 63 ) / 64, sc->grid_blocks * 2 ) ), sc->stream, a ) );
 	else
 	HIPCHK( sc->dprog.efn_big ? rmk_launch_efn_big( int( blocks ), sc->stream, a ) : rmk_launch_efn( int( blocks ), sc->stream, a ) );
@@ -1750,16 +1363,9 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 	}
 	const rma_db	*db = sc->fly.db;
 	const int	stride = sc->dprog.hit_stride;
-	// pinned staging buffer: the copy back is a single DMA
 	const size_t	words = size_t( n ) * stride;
-	if( copy_back && words > sc->h_raw_cap ){
-		if( sc->h_raw != nullptr )
-			( void )hipHostFree( sc->h_raw );
-		sc->h_raw = nullptr;
-		sc->h_raw_cap = 0;
-		HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_raw ), words * 2 * sizeof( int32_t ), hipHostMallocDefault ) );
-		sc->h_raw_cap = words * 2;
-	}
+	if( copy_back && grow_h_raw( sc, words, err, errlen ) )
+		return 1;
 	// Reference order -- (entry, strand, start, rank, order), order word renumbered -- on the device,
 	// behind the efn kernel on the same stream: what comes back is the final stream (rm_hitsort_dev.h).
 	// Header words that do not fit the 64-bit key (or host_sort): the host's sort_hits().
@@ -1807,14 +1413,8 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 			*hits = copy_back ? sc->h_raw : nullptr;
 		return 0;
 	}
-	if( words > sc->h_raw_cap ){		// (not asked to copy back, but the host has to order)
-		if( sc->h_raw != nullptr )
-			( void )hipHostFree( sc->h_raw );
-		sc->h_raw = nullptr;
-		sc->h_raw_cap = 0;
-		HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_raw ), words * 2 * sizeof( int32_t ), hipHostMallocDefault ) );
-		sc->h_raw_cap = words * 2;
-	}
+	if( grow_h_raw( sc, words, err, errlen ) )		// (not asked to copy back, but the host has to order)
+		return 1;
 	HIPCHK( hipMemcpyAsync( sc->h_raw, sc->d_hits, words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream ) );
 	HIPCHK( hipStreamSynchronize( sc->stream ) );
 	lap( "copy back" );
@@ -1898,7 +1498,7 @@ extern "C" int rma_scanner_warmup( rma_scanner_t *sc, char *err, size_t errlen )
 	if( sc->prog.dminlen > 2000 )
 		return 0;
 	HIPCHK( hipSetDevice( sc->device ) );
-	const Options	keep = sc->opt;
+	const rma::Options	keep = sc->opt;
 	sc->opt.dbg = 0;		// (no diagnostics of the warm-up)
 	sc->opt.timing = 0;
 	const std::string	warm( size_t( std::max( sc->prog.dminlen, 1 ) + 7 ), 'a' );
