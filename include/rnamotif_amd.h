@@ -49,6 +49,10 @@ int	rma_descr_maxlen( const rma_descr_t *d );			/* rm_dmaxlen, RMA_UNBOUNDED if 
 /* for bindings that do not want to mirror the struct: n_elems, n_searches, hit stride,
  * ctx offset, efn offset, n_efn_sites, chk_both_strs, windowsize */
 void	rma_program_info( const rma_program_t *prog, int32_t info[ 8 ] );
+/* the number of elements whose seq= the scan tests loosely (rma_regex_t::loose: back references, letters that
+ * are not acgt with iupac = 0): a scan's records of such a program are a superset of the reference's candidates
+ * until they are replayed (rma_replay_*), which applies the whole expression to the text */
+int	rma_program_loose( const rma_program_t *prog );
 
 /* ---- energy tables on their own: RM_getefndata() efn.c:157 / RM_getefn2data() efn2.c:130
  * from the directory dir (the reference's efn_datadir / $EFNDATA). */
@@ -158,7 +162,8 @@ int	rma_db_create_packed_ranges( rma_scanner_t *sc, const rma_pack_t *pk, const 
  * byte -> 0-3 or 4 (ambiguous), in host memory or on the scanner's device (there a code above 3 counts as
  * 4).  stream: the caller's hipStream_t the text was written on (NULL = the default stream): the packing
  * runs behind what is queued there now.  The text stays as it is, and allocated, until rma_db_wait()
- * returns or a scan of the database has ended.  Pointers are checked (device memory of the scanner's
+ * returns or a scan of the database has ended, and, to replay (rma_replay_device), until the replay
+ * returns.  Pointers are checked (device memory of the scanner's
  * device, ranges inside the text and its allocation) before anything is launched. */
 int	rma_db_create_device( rma_scanner_t *sc, const void *text, int64_t text_bytes, const int64_t *start, const int32_t *slen,
 		const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, const uint8_t *table, void *stream,
@@ -175,7 +180,9 @@ int	rma_db_read_packed( const rma_db_t *db, uint32_t *codes, uint32_t *amask, in
  * *hits receives *n_hits records of rma_hit_stride( prog ) words, sorted by
  * (seq, comp, szero, rank, order) = the reference's output order; the memory
  * belongs to the scanner and is valid until its next scan or destruction.
- * Energies of the program's efn sites are filled in. */
+ * Energies of the program's efn sites are filled in.  The records are candidates before the score section;
+ * for a program with loose seq= elements (rma_program_loose() > 0) they are a superset of the reference's
+ * candidates until replayed. */
 int	rma_scan( rma_scanner_t *sc, const rma_db_t *db, const int32_t **hits, int64_t *n_hits,
 		char *err, size_t errlen );
 
@@ -183,7 +190,8 @@ int	rma_scan( rma_scanner_t *sc, const rma_db_t *db, const int32_t **hits, int64
  * returns; rma_scan_end() waits for it, runs the energy kernel and the ordering, copies the records
  * back and returns them as rma_scan() does.  Between the two the host is free: to begin the scan of
  * another scanner (two descriptors over one database run side by side), or to upload the next
- * database (rma_db_create_packed_async).  One scan in flight per scanner. */
+ * database (rma_db_create_packed_async).  One scan in flight per scanner.  rma_scan_end's records are
+ * rma_scan's: a superset of the candidates for a program with loose seq= elements until replayed. */
 int	rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err, size_t errlen );
 int	rma_scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, char *err, size_t errlen );
 /* rma_scan_end() that leaves the ordered records in HBM (*d_hits is a device pointer, valid until
@@ -269,6 +277,24 @@ int	rma_replay_batch( rma_replay_t *rp, const char *const *sids, const char *con
  * text of an entry is rebuilt for the span of each hit only */
 int	rma_replay_pack( rma_replay_t *rp, const rma_pack_t *pk, int32_t first,
 		const int32_t *hits, int64_t n_hits, int64_t *n_printed, char *err, size_t errlen );
+/* Replay candidates of a database made by rma_db_create_device(): the score program, the loose seq= test and
+ * the printer, as rma_replay_batch() runs them, over text read from the database's device text -- of each
+ * record only its window, the bases its elements and contexts cover, cut out on the device and copied back.
+ * d_hits: n_hits records of rma_hit_stride() words of the replay's program in device memory of the database's
+ * device (a subset of a scan's records, in any order; printed in the order given).  letters: 256 bytes,
+ * byte -> the letter the replay sees, or NULL: the readers' letters (an ASCII letter in lower case, u as t,
+ * every other byte n) for a database made with the default table, else "acgt" for codes 0-3 of its table and
+ * n for the rest.  On strand 1 the letters are complemented as mk_rcmp() does (a t, c g, g c, t/u a, else n).
+ * sids / sdefs: one per entry, or NULL (sid = the entry's number in decimal, sdef "").  stream: the caller's
+ * hipStream_t the records and text were written on (NULL = the default stream).  accepted: host array of
+ * n_hits bytes or NULL; 1 where the record was printed (reached the printer: with HOLD, was held).
+ * *n_printed = their number.  Every record is checked on the device before any text is read (entry inside
+ * the database, strand 0 or 1, every element and context inside its entry); a bad record fails the call,
+ * naming its index, and nothing is printed.  The replay's device and page-locked buffers are made on the
+ * first call, on the database's device, and freed by rma_replay_close(). */
+int	rma_replay_device( rma_replay_t *rp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *letters, const char *const *sids, const char *const *sdefs, void *stream,
+		int64_t *n_printed, uint8_t *accepted, char *err, size_t errlen );
 int	rma_replay_close( rma_replay_t *rp, char *err, size_t errlen );	/* runs the END program */
 
 #ifdef __cplusplus

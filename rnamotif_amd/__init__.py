@@ -123,6 +123,9 @@ def lib() -> C.CDLL:
     L.rma_db_mask_words.restype = C.c_int64
     L.rma_db_read_packed.argtypes = [vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_scan_records_to_device.argtypes = [vp, vp, C.c_int64, vp, C.c_char_p, C.c_size_t]
+    L.rma_replay_device.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, cpp, cpp, vp, i64p, vp, C.c_char_p, C.c_size_t]
+    L.rma_program_loose.argtypes = [vp]
+    L.rma_program_loose.restype = C.c_int
     _lib = L
     return L
 
@@ -166,6 +169,9 @@ class Descriptor:
          self.n_efn_sites, self.both_strands, self.windowsize) = list(info)
         self.minlen = L.rma_descr_minlen(h)
         self.maxlen = L.rma_descr_maxlen(h)
+        # elements whose seq= the scan tests loosely (back references, iupac = 0 letters): the records of a scan are
+        # then a superset of rnamotif's candidates until they are replayed (rma_program_loose)
+        self.loose = L.rma_program_loose(self.program)
 
     def search_order(self) -> List[int]:
         """Element index heading each search level (rm_searches[k]->s_descr->s_index)."""
@@ -338,6 +344,26 @@ def alphabet_table(alphabet: str) -> bytes:
     return bytes(tab)
 
 
+def reader_letter(b: int) -> int:
+    """The letter the readers make of a byte (dbutil.c:112-113): an ASCII letter in lower case, u as t; every
+    other byte is n here (the readers drop it; a device database keeps it, ambiguous)."""
+    if 65 <= b <= 90:
+        b += 32
+    if 97 <= b <= 122:
+        return ord("t") if b == ord("u") else b
+    return ord("n")
+
+
+def alphabet_letters(alphabet: str) -> bytes:
+    """The 256 letters Replay.device() reads a database_from_tensor(alphabet=...) text as: value i is
+    alphabet[i] as the readers take it, every other value n."""
+    alphabet_table(alphabet)        # (the same checks)
+    tab = bytearray(b"n" * 256)
+    for i, ch in enumerate(alphabet):
+        tab[i] = reader_letter(ord(ch))
+    return bytes(tab)
+
+
 class Scanner:
     """The motif program on one GPU (RM_fm_init + RM_find_motif)."""
 
@@ -366,7 +392,8 @@ class Scanner:
         database() makes of the same bytes.  text and the entries in it as text_entries() takes them; ranges as
         database(); alphabet: value i of the text is letter alphabet[i] (default: the bytes are letters).  The
         packing runs behind the work queued on torch's current stream; the database keeps the tensor until it is
-        closed.  Records of its scans are candidates as rma_scan returns them: there is no host text to replay."""
+        closed.  Records of its scans are candidates as rma_scan returns them; Replay.device() scores and prints
+        them from the text on the GPU."""
         import torch
         if not isinstance(text, torch.Tensor):
             raise TypeError(f"text is a {type(text).__name__}, not a torch.Tensor")
@@ -392,6 +419,7 @@ class Scanner:
                                           C.byref(h), err, _ERRLEN), err)
         db = Database.__new__(Database)
         db.scanner, db.n_seqs, db._h, db._text = self, n, h, text
+        db.start, db.slen, db.alphabet = start, slen, alphabet
         db.bases = lib().rma_db_bases(h)
         if wait:
             db.wait()
@@ -399,7 +427,8 @@ class Scanner:
 
     def scan_tensor(self, db: Database):
         """scan(db) with the records left on the GPU: an int32 tensor [n, hit_stride] on the scanner's device, the
-        same records in the same order, ready on torch's current stream."""
+        same records in the same order, ready on torch's current stream.  Candidates before the score section, a
+        superset of rnamotif's when descr.loose > 0, until Replay.device() replays them."""
         import torch
         self.scan_begin(db)
         n = self.scan_end_on_device()
@@ -460,7 +489,8 @@ class Scanner:
 
     def scan(self, db: Database, copy: bool = True) -> np.ndarray:
         """All candidates of db in reference order: int32 array [n, hit_stride].  With
-        copy=False the array is a view of the scanner's own buffer, valid until its next scan."""
+        copy=False the array is a view of the scanner's own buffer, valid until its next scan.
+        When descr.loose > 0 the records are a superset of rnamotif's candidates until replayed."""
         L = lib()
         hits = C.POINTER(C.c_int32)()
         n = C.c_int64()
@@ -505,6 +535,7 @@ class Replay:
         err = C.create_string_buffer(_ERRLEN)
         _check(L.rma_replay_open(descr._h, out_path.encode(), C.byref(h), err, _ERRLEN), err)
         self._h = h
+        self.descr = descr
 
     def batch(self, sids: Sequence[bytes], sdefs: Sequence[bytes], seqs: Sequence[bytes],
               hits: np.ndarray) -> int:
@@ -526,6 +557,52 @@ class Replay:
         err = C.create_string_buffer(_ERRLEN)
         _check(L.rma_replay_pack(self._h, pack._h, first, hits.ctypes.data_as(C.POINTER(C.c_int32)), hits.shape[0],
                                  C.byref(printed), err, _ERRLEN), err)
+        return printed.value
+
+    def device(self, db: Database, hits, sids: Optional[Sequence[bytes]] = None, sdefs: Optional[Sequence[bytes]] = None,
+               letters: Optional[bytes] = None, accepted: bool = False):
+        """Candidates of a database made by Scanner.database_from_tensor(), replayed from its text on the GPU
+        (rma_replay_device): only each record's window -- the bases its elements and contexts cover -- is cut out
+        on the device and copied to the host.  hits: int32 CUDA tensor [n, hit_stride] on the database's device,
+        scan_tensor()'s output or rows of it, printed in the order given.  sids / sdefs: one per entry (default:
+        the entry's number, "").  letters: 256 bytes, byte -> letter; default: the database's alphabet= (value i
+        -> alphabet[i] as the readers take it, anything else n), else the readers' letters.  Runs behind the work
+        queued on torch's current stream.  Returns the number printed, or (that number, np.bool_ mask of the
+        records printed) with accepted=True."""
+        import torch
+        if getattr(db, "_h", None) is None or not db._h:
+            raise ValueError("the database is closed")
+        if getattr(db, "_text", None) is None:
+            raise ValueError("the database was not made by database_from_tensor(): replay it with batch() or pack()")
+        if not isinstance(hits, torch.Tensor):
+            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
+        device = db.scanner.device
+        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != device:
+            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{device}")
+        if hits.dtype != torch.int32:
+            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
+        stride = self.descr.hit_stride
+        if hits.ndim != 2 or int(hits.shape[1]) != stride:
+            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this replay's descriptor are needed")
+        hits = hits.contiguous()
+        n = int(hits.shape[0])
+        if letters is None and db.alphabet is not None:
+            letters = alphabet_letters(db.alphabet)
+        if letters is not None and len(letters) != 256:
+            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
+        for what, names in (("sids", sids), ("sdefs", sdefs)):
+            if names is not None and len(names) != db.n_seqs:
+                raise ValueError(f"{what}: one per entry, {db.n_seqs}, not {len(names)}")
+        mask = np.zeros(max(n, 1), dtype=np.uint8)
+        printed = C.c_int64()
+        err = C.create_string_buffer(_ERRLEN)
+        stream = torch.cuda.current_stream(hits.device).cuda_stream
+        _check(lib().rma_replay_device(self._h, db._h, hits.data_ptr() if n else None, n, letters,
+                                       _cstr_array(sids) if sids is not None else None,
+                                       _cstr_array(sdefs) if sdefs is not None else None, stream, C.byref(printed),
+                                       mask.ctypes.data, err, _ERRLEN), err)
+        if accepted:
+            return printed.value, mask[:n].astype(np.bool_)
         return printed.value
 
     def close(self) -> None:

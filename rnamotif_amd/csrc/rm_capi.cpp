@@ -7,6 +7,7 @@
 #include "rm_pack.h"
 #include "rm_stream.h"
 #include "rm_hitsort.h"
+#include "rm_hitwin.h"
 #include <cctype>
 #include <cstddef>
 #include <cstring>
@@ -23,6 +24,7 @@ struct rma_replay {
 	bool	own_fp;
 	rma::Replayer	*rp;
 	rma::SearchStats	st;
+	rma::HitWindowScratch	*dev = nullptr;	// rma_replay_device's buffers (rm_scanner.cpp), made on its first call
 };
 
 static int set_err( char *err, size_t errlen, const char *msg )
@@ -76,6 +78,15 @@ extern "C" void rma_program_info( const rma_program_t *p, int32_t info[ 8 ] )
 	info[ 5 ] = p->n_efn_sites;
 	info[ 6 ] = p->chk_both_strs;
 	info[ 7 ] = p->windowsize;
+}
+
+extern "C" int rma_program_loose( const rma_program_t *p )
+{
+	int	n = 0;
+	for( int e = 0; e < p->n_elems; e++ )
+		if( p->elems[ e ].re >= 0 && p->regexes[ p->elems[ e ].re ].loose )
+			n++;
+	return n;
 }
 
 extern "C" int rma_replay_open( rma_descr_t *d, const char *path, rma_replay_t **out, char *err, size_t errlen )
@@ -160,6 +171,38 @@ extern "C" int rma_sort_hits( const int32_t *hits, int64_t n_hits, int32_t strid
 	}
 }
 
+extern "C" int rma_replay_device( rma_replay_t *rp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, const char *const *sids, const char *const *sdefs, void *stream,
+	int64_t *n_printed, uint8_t *accepted, char *err, size_t errlen )
+{
+	const int64_t	before = rp->st.n_hits;
+	if( n_printed )
+		*n_printed = 0;
+	try{
+		rma::Replayer	&r = *rp->rp;
+		rma::SearchStats	&st = rp->st;
+		// (records are checked on the device before the first piece comes: nothing is printed for a bad one)
+		if( rma_hit_windows( &rp->dev, db, *rp->d->pr.prog, d_hits, n_hits, letters, stream,
+			[ & ]( const rma::HitWindowPiece &p ){
+				r.replay_windows( p.records, p.n, p.windows, p.off, p.lo, p.slen, p.n_seq, sids, sdefs,
+					accepted != nullptr ? accepted + p.first : nullptr, st );
+			}, err, errlen ) ){
+			fflush( rp->fp );
+			return 1;
+		}
+		if( n_printed )
+			*n_printed = rp->st.n_hits - before;
+		fflush( rp->fp );
+		return 0;
+	}catch( rma::Error &e ){
+		fflush( rp->fp );
+		return set_err( err, errlen, e.what() );
+	}catch( std::exception &e ){
+		fflush( rp->fp );
+		return set_err( err, errlen, e.what() );
+	}
+}
+
 extern "C" int rma_replay_close( rma_replay_t *rp, char *err, size_t errlen )
 {
 	int	rv = 0;
@@ -171,6 +214,7 @@ extern "C" int rma_replay_close( rma_replay_t *rp, char *err, size_t errlen )
 	fflush( rp->fp );
 	if( rp->own_fp )
 		fclose( rp->fp );
+	rma::hitwin_scratch_free( rp->dev );
 	delete rp->rp;
 	delete rp;
 	return rv;

@@ -169,6 +169,38 @@ void Replayer::replay_packed( const PackFile &pk, int first, const int32_t *hits
 	}
 }
 
+void Replayer::replay_windows( const int32_t *hits, int64_t n, const char *windows, const int64_t *off, const int32_t *lo,
+	const int32_t *slen, int n_seq, const char *const *sids, const char *const *sdefs, uint8_t *accepted, SearchStats &st )
+{
+	const int	stride = rma_hit_stride( &prog_ );
+	char	num[ 16 ];
+	for( int64_t h = 0; h < n; h++ ){
+		const int32_t	*w = hits + h * stride;
+		const int	i = w[ 0 ];
+		if( i < 0 || i >= n_seq )
+			fail( "scanner returned a hit for sequence %d of a batch of %d.", i, n_seq );
+		const int	len = slen[ i ];
+		if( text_.size() < size_t( len ) + 1 )
+			text_.resize( size_t( len ) + 1 + size_t( len ) / 4 );
+		const int64_t	m = off[ h + 1 ] - off[ h ];
+		if( m > 0 ){
+			if( lo[ h ] < 0 || int64_t( lo[ h ] ) + m > len )
+				fail( "the window of record %lld lies outside its entry.", ( long long )h );
+			memcpy( text_.data() + lo[ h ], windows + off[ h ], size_t( m ) );
+		}
+		const char	*sid = sids != nullptr ? sids[ i ] : nullptr;
+		if( sid == nullptr ){
+			snprintf( num, sizeof( num ), "%d", i );
+			sid = num;
+		}
+		const char	*sdef = sdefs != nullptr && sdefs[ i ] != nullptr ? sdefs[ i ] : "";
+		const int64_t	before = st.n_hits;
+		one_hit( w, sid, sdef, len, text_.data(), st );
+		if( accepted != nullptr )
+			accepted[ h ] = st.n_hits > before ? 1 : 0;
+	}
+}
+
 // ---------------------------------------------------------------- the pipelined search
 // Packed batches go through two more threads: one hands them to the scanner (upload, kernels,
 // copy back of the candidate records), one replays the candidates through the score program

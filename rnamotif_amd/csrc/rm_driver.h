@@ -47,6 +47,13 @@ public:
 	// the text of an entry is rebuilt for the span of each hit only (PackFile::window), so a batch
 	// of a hundred million bases with a few thousand hits costs a few thousand small windows
 	void	replay_packed( const PackFile &pk, int first, const int32_t *hits, int64_t n, SearchStats &st );
+	// the same over windows cut out elsewhere (rma_replay_device: on the device, rm_hitwin.h): record h's window is
+	// windows[ off[ h ], off[ h + 1 ] ), the letters of positions lo[ h ] .. of its strand; slen[ n_seq ] the
+	// entries' lengths; sids / sdefs per entry, or null (the entry's number in decimal, "").  accepted (may be
+	// null): accepted[ h ] = 1 where the record reached the printer -- st.n_hits counts the same
+	void	replay_windows( const int32_t *hits, int64_t n, const char *windows, const int64_t *off, const int32_t *lo,
+			const int32_t *slen, int n_seq, const char *const *sids, const char *const *sdefs, uint8_t *accepted,
+			SearchStats &st );
 	// parallel replay (rm_driver.cpp): a worker's replayer writes to a buffer of its own and never
 	// prints the "#RM" header
 	void	set_out( FILE *out, bool header );

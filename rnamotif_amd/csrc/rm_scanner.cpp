@@ -23,6 +23,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -37,6 +38,7 @@
 #include "rm_hitsort.h"
 #include "rm_hitsort_dev.h"
 #include "rm_dbpack_dev.h"
+#include "rm_hitwin_dev.h"
 #include "rnamotif_amd.h"
 
 #define HIPCHK( call )	do{ hipError_t e_ = ( call ); if( e_ != hipSuccess ){ \
@@ -204,6 +206,13 @@ struct rma_db {
 	std::vector<int64_t>	h_base_off;
 	std::vector<int64_t>	h_text_start;		// (rma_db_create_device: what the copies to the device read)
 	std::vector<uint8_t>	h_table;
+	// rma_db_create_device: the text (bytes [text_lo, text_hi) of it hold the entries), the entries' starts and
+	// the table on the device, and whether the table was the default one -- what rma_replay_device() reads
+	const uint8_t	*text = nullptr;
+	int64_t	text_bytes = 0, text_lo = 0, text_hi = 0;
+	const int64_t	*d_text_start = nullptr;
+	const uint8_t	*d_table = nullptr;
+	bool	default_table = true;
 	int32_t	n_seq = 0, max_slen = 0;
 	int64_t	total_bases = 0, sum_slen = 0;
 	int64_t	padded_bases = 0;	// bases the packed arrays hold, padding between the entries included
@@ -213,6 +222,11 @@ struct rma_db {
 	std::vector<std::unique_ptr<Layout>>	layouts;
 	std::vector<rma_scanner *>	busy;		// scanners with a scan of this database in flight
 };
+
+// the databases rma_db_create_device() has made and rma_db_destroy() has not yet destroyed (rma_replay_device
+// refuses any other)
+static std::mutex	g_device_dbs_mu;
+static std::set<const rma_db *>	g_device_dbs;
 
 extern "C" void rma_db_destroy( rma_db_t *db );
 extern "C" void rma_scanner_destroy( rma_scanner_t *sc );
@@ -762,6 +776,13 @@ extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_
 	// (host copies the database keeps until it is destroyed: the copies read them after this returns)
 	db->h_text_start.assign( start, start + n );
 	db->h_table = tab;
+	db->text = static_cast<const uint8_t *>( text );
+	db->text_bytes = text_bytes;
+	db->text_lo = lo;
+	db->text_hi = hi;
+	db->d_text_start = d_start;
+	db->d_table = d_table;
+	db->default_table = table == nullptr;
 	if( n > 0 )
 		HIPCHK( hipMemcpyAsync( d_start, db->h_text_start.data(), size_t( n ) * 8, hipMemcpyHostToDevice, up ) );
 	if( !table_on_device )
@@ -777,7 +798,11 @@ extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_
 	*out = db;
 	if( db_ready( out, false, err, errlen ) )
 		return 1;
-	return tile_at_creation( sc, out, err, errlen );
+	if( tile_at_creation( sc, out, err, errlen ) )
+		return 1;
+	std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+	g_device_dbs.insert( *out );
+	return 0;
 }
 
 extern "C" int64_t rma_db_mask_words( const rma_db_t *db ) { return db->padded_bases / 32; }
@@ -812,6 +837,10 @@ extern "C" void rma_db_destroy( rma_db_t *db )
 {
 	if( db == nullptr )
 		return;
+	{
+		std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+		g_device_dbs.erase( db );
+	}
 	( void )hipSetDevice( db->device );
 	// scans of this database that were begun and not ended: their kernels read it
 	std::vector<rma_scanner *>	busy;
@@ -839,6 +868,241 @@ extern "C" void rma_db_destroy( rma_db_t *db )
 }
 
 extern "C" int64_t rma_db_bases( const rma_db_t *db ) { return db->total_bases; }
+
+// ---------------------------------------------------------------- windows of hits of device databases
+// The device half of rma_replay_device() (rm_capi.cpp has the replay): the records are checked and their windows
+// cut out of the database's text on the device (rm_hitwin_dev.hip), in chunks of HW_CHUNK records, and come to
+// the host in pieces of at most HW_PIECE_WINDOW bytes of windows and HW_PIECE_RECORDS bytes of records (a longer
+// window comes alone).  One synchronisation learns a chunk's offsets (and, in the first chunk, whether some
+// record is bad), one per piece ends its copy.
+namespace {
+constexpr int64_t	HW_CHUNK = int64_t( 1 ) << 17;
+constexpr int64_t	HW_PIECE_WINDOW = int64_t( 16 ) << 20, HW_PIECE_RECORDS = int64_t( 8 ) << 20;
+
+hipError_t dev_room( void **p, size_t *cap, size_t want )
+{
+	if( *cap >= want )
+		return hipSuccess;
+	if( *p != nullptr )
+		( void )hipFree( *p );
+	*p = nullptr;
+	*cap = 0;
+	want += want / 4;
+	hipError_t	e = hipMalloc( p, want );
+	if( e == hipSuccess )
+		*cap = want;
+	return e;
+}
+
+hipError_t host_room( void **p, size_t *cap, size_t want )
+{
+	if( *cap >= want )
+		return hipSuccess;
+	if( *p != nullptr )
+		( void )hipHostFree( *p );
+	*p = nullptr;
+	*cap = 0;
+	want += want / 4;
+	hipError_t	e = hipHostMalloc( p, want, hipHostMallocDefault );
+	if( e == hipSuccess )
+		*cap = want;
+	return e;
+}
+}	// namespace
+
+struct rma::HitWindowScratch {
+	int	device = -1;
+	hipStream_t	stream = nullptr;
+	// device: lo[ HW_CHUNK ] | len[ HW_CHUNK + 1 ] | off[ HW_CHUNK + 1 ] | src[ HW_CHUNK ] | bad | letters[ 256 ], the scan's
+	// room, windows
+	void	*d_fixed = nullptr, *d_tmp = nullptr, *d_win = nullptr;
+	size_t	fixed_bytes = 0, tmp_bytes = 0, win_cap = 0;
+	int32_t	*d_lo = nullptr;
+	int64_t	*d_len = nullptr, *d_off = nullptr, *d_src = nullptr;
+	unsigned long long	*d_bad = nullptr;
+	uint8_t	*d_tab = nullptr;
+	// page-locked: off[ HW_CHUNK + 1 ] | lo[ HW_CHUNK ] | bad | letters[ 256 ], records, windows
+	void	*h_fixed = nullptr, *h_rec = nullptr, *h_win = nullptr;
+	size_t	h_fixed_bytes = 0, rec_cap = 0, h_win_cap = 0;
+	int64_t	*h_off = nullptr;
+	int32_t	*h_lo = nullptr;
+	unsigned long long	*h_bad = nullptr;
+	uint8_t	*h_tab = nullptr;
+	std::vector<int64_t>	piece_off;
+};
+
+void rma::hitwin_scratch_free( HitWindowScratch *s )
+{
+	if( s == nullptr )
+		return;
+	( void )hipSetDevice( s->device );
+	if( s->stream != nullptr )
+		( void )hipStreamSynchronize( s->stream );
+	for( void *p : { s->d_fixed, s->d_tmp, s->d_win } )
+		if( p != nullptr )
+			( void )hipFree( p );
+	for( void *p : { s->h_fixed, s->h_rec, s->h_win } )
+		if( p != nullptr )
+			( void )hipHostFree( p );
+	if( s->stream != nullptr )
+		( void )hipStreamDestroy( s->stream );
+	delete s;
+}
+
+static int scratch_on( rma::HitWindowScratch **scratch, int device, char *err, size_t errlen )
+{
+	if( *scratch != nullptr && ( *scratch )->device == device )
+		return 0;
+	rma::hitwin_scratch_free( *scratch );
+	*scratch = new rma::HitWindowScratch;
+	rma::HitWindowScratch	*s = *scratch;
+	s->device = device;
+	HIPCHK( hipStreamCreateWithFlags( &s->stream, hipStreamNonBlocking ) );
+	const size_t	o_len = align256( size_t( HW_CHUNK ) * 4 ), o_off = o_len + align256( size_t( HW_CHUNK + 1 ) * 8 );
+	const size_t	o_src = o_off + align256( size_t( HW_CHUNK + 1 ) * 8 ), o_bad = o_src + align256( size_t( HW_CHUNK ) * 8 ), o_tab = o_bad + 256;
+	HIPCHK( dev_room( &s->d_fixed, &s->fixed_bytes, o_tab + 256 ) );
+	char	*d = static_cast<char *>( s->d_fixed );
+	s->d_lo = reinterpret_cast<int32_t *>( d );
+	s->d_len = reinterpret_cast<int64_t *>( d + o_len );
+	s->d_off = reinterpret_cast<int64_t *>( d + o_off );
+	s->d_src = reinterpret_cast<int64_t *>( d + o_src );
+	s->d_bad = reinterpret_cast<unsigned long long *>( d + o_bad );
+	s->d_tab = reinterpret_cast<uint8_t *>( d + o_tab );
+	size_t	tmp = 0;
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, HW_CHUNK + 1, nullptr, &tmp, s->stream ) );
+	HIPCHK( dev_room( &s->d_tmp, &s->tmp_bytes, std::max<size_t>( tmp, 256 ) ) );
+	const size_t	h_lo = align256( size_t( HW_CHUNK + 1 ) * 8 ), h_bad = h_lo + align256( size_t( HW_CHUNK ) * 4 ), h_tab = h_bad + 256;
+	HIPCHK( host_room( &s->h_fixed, &s->h_fixed_bytes, h_tab + 256 ) );
+	char	*h = static_cast<char *>( s->h_fixed );
+	s->h_off = reinterpret_cast<int64_t *>( h );
+	s->h_lo = reinterpret_cast<int32_t *>( h + h_lo );
+	s->h_bad = reinterpret_cast<unsigned long long *>( h + h_bad );
+	s->h_tab = reinterpret_cast<uint8_t *>( h + h_tab );
+	return 0;
+}
+
+// the words of a bad record, why it is bad
+static int bad_record( rma::HitWindowScratch *s, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits, int64_t h,
+	char *err, size_t errlen )
+{
+	const int	stride = rma_hit_stride( &prog );
+	std::vector<int32_t>	w( static_cast<size_t>( stride ) );
+	HIPCHK( hipMemcpyAsync( w.data(), d_hits + h * stride, size_t( stride ) * 4, hipMemcpyDeviceToHost, s->stream ) );
+	HIPCHK( hipStreamSynchronize( s->stream ) );
+	int32_t	lo, hi;
+	int	which;
+	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
+	const int	r = rma::hitwin_span( w.data(), shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which );
+	if( r == rma::HW_ENTRY )
+		snprintf( err, errlen, "record %lld: entry %d outside [0, %d): nothing printed", ( long long )h, w[ 0 ], db->n_seq );
+	else if( r == rma::HW_STRAND )
+		snprintf( err, errlen, "record %lld: strand %d, not 0 or 1: nothing printed", ( long long )h, w[ 1 ] );
+	else if( r == rma::HW_EXTENT ){
+		const int	k = which < shape.n_elems ? RMA_HIT_HDR + 4 * which : which == shape.n_elems ? shape.ctx_off : shape.ctx_off + 2;
+		char	what[ 32 ];
+		if( which < shape.n_elems )
+			snprintf( what, sizeof( what ), "element %d", which );
+		else
+			snprintf( what, sizeof( what ), "the %s context", which == shape.n_elems ? "left" : "right" );
+		snprintf( err, errlen, "record %lld: %s at offset %d, length %d, outside entry %d's %d bases: nothing printed", ( long long )h,
+			what, w[ k ], w[ k + 1 ], w[ 0 ], db->h_slen[ size_t( w[ 0 ] ) ] );
+	}else
+		snprintf( err, errlen, "record %lld: refused on the device, not on the host (records changed during the call?)", ( long long )h );
+	return 1;
+}
+
+int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits,
+	int64_t n_hits, const uint8_t *letters, void *stream, const std::function<void( const rma::HitWindowPiece & )> &each,
+	char *err, size_t errlen )
+{
+	{
+		std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+		if( db == nullptr || g_device_dbs.count( db ) == 0 ){
+			snprintf( err, errlen, "rma_replay_device: the database (%p) was not made by rma_db_create_device() or has been destroyed",
+				static_cast<const void *>( db ) );
+			return 1;
+		}
+	}
+	const int	stride = rma_hit_stride( &prog );
+	if( n_hits < 0 || ( n_hits > 0 && d_hits == nullptr ) || n_hits > INT64_MAX / 4 / stride ){
+		snprintf( err, errlen, "rma_replay_device: %lld records: bad arguments", ( long long )n_hits );
+		return 1;
+	}
+	if( n_hits == 0 )
+		return 0;
+	HIPCHK( hipSetDevice( db->device ) );
+	// the records: n_hits records of the replay's program's stride, inside their allocation
+	if( check_device_bytes( d_hits, db->device, 0, n_hits * stride * 4, "the records", err, errlen ) )
+		return 1;
+	if( db->text_hi > db->text_lo && check_device_bytes( db->text, db->device, db->text_lo, db->text_hi, "the database's text", err, errlen ) )
+		return 1;
+	if( scratch_on( scratch, db->device, err, errlen ) )
+		return 1;
+	rma::HitWindowScratch	*s = *scratch;
+	hipStream_t	st = s->stream;
+	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
+	// the letters: the caller's, the readers', or the letters of the database's own codes
+	const uint8_t	*tab = s->d_tab;
+	int	codes = 0;
+	if( letters != nullptr )
+		memcpy( s->h_tab, letters, 256 );
+	else if( db->default_table )
+		for( int b = 0; b < 256; b++ )
+			s->h_tab[ b ] = rma::hitwin_reader_letter( static_cast<unsigned char>( b ) );
+	else{
+		tab = db->d_table;
+		codes = 1;
+	}
+	if( tab == s->d_tab )
+		HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, st ) );
+	// behind the caller's work on its stream (the records) and the database's tables
+	if( stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	// every record checked before any text is read: all of them here when there is more than one chunk, else
+	// the first chunk's spans do it
+	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
+	if( n_hits > HW_CHUNK )
+		HIPCHK( rma::hit_spans( d_hits, n_hits, stride, shape, db->d_slen, db->d_text_start, db->n_seq, nullptr, nullptr, nullptr,
+			s->d_bad, st ) );
+	const int64_t	piece_records = std::max<int64_t>( 1, HW_PIECE_RECORDS / ( 4 * stride ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		const int32_t	*ch = d_hits + c0 * stride;
+		HIPCHK( rma::hit_spans( ch, cn, stride, shape, db->d_slen, db->d_text_start, db->n_seq, s->d_lo, s->d_len, s->d_src,
+			s->d_bad, st ) );
+		size_t	tb = s->tmp_bytes;
+		HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, st ) );
+		HIPCHK( hipMemcpyAsync( s->h_off, s->d_off, size_t( cn + 1 ) * 8, hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipMemcpyAsync( s->h_lo, s->d_lo, size_t( cn ) * 4, hipMemcpyDeviceToHost, st ) );
+		if( c0 == 0 )
+			HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipStreamSynchronize( st ) );
+		if( c0 == 0 && *s->h_bad != ~0ull )
+			return bad_record( s, db, prog, d_hits, int64_t( *s->h_bad ), err, errlen );
+		for( int64_t a = 0; a < cn; ){
+			int64_t	b = a + 1;
+			while( b < cn && b - a < piece_records && s->h_off[ b + 1 ] - s->h_off[ a ] <= HW_PIECE_WINDOW )
+				b++;
+			const int64_t	bytes = s->h_off[ b ] - s->h_off[ a ];
+			HIPCHK( dev_room( &s->d_win, &s->win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
+			HIPCHK( host_room( &s->h_win, &s->h_win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
+			HIPCHK( host_room( &s->h_rec, &s->rec_cap, size_t( b - a ) * stride * 4 ) );
+			HIPCHK( rma::hit_gather( db->text, b - a, s->d_src + a, s->d_off + a, tab, codes, static_cast<uint8_t *>( s->d_win ), st ) );
+			HIPCHK( hipMemcpyAsync( s->h_rec, ch + a * stride, size_t( b - a ) * stride * 4, hipMemcpyDeviceToHost, st ) );
+			if( bytes > 0 )
+				HIPCHK( hipMemcpyAsync( s->h_win, s->d_win, size_t( bytes ), hipMemcpyDeviceToHost, st ) );
+			HIPCHK( hipStreamSynchronize( st ) );
+			s->piece_off.resize( size_t( b - a + 1 ) );
+			for( int64_t i = a; i <= b; i++ )
+				s->piece_off[ size_t( i - a ) ] = s->h_off[ i ] - s->h_off[ a ];
+			each( rma::HitWindowPiece{ static_cast<const int32_t *>( s->h_rec ), c0 + a, b - a, static_cast<const char *>( s->h_win ),
+				s->piece_off.data(), s->h_lo + a, db->h_slen.data(), db->n_seq } );
+			a = b;
+		}
+	}
+	return 0;
+}
 
 // ---------------------------------------------------------------- pinned host memory
 // A packed database in memory whose words are page-locked uploads by DMA, without a staging copy,
