@@ -4,8 +4,11 @@ the descriptor generators of tests/test_gpu_parity.py.
 
     python tests/fuzz_hostsim.py general 0 2000 [workers]
     python tests/fuzz_hostsim.py lean-as-general 0 2000    (lean descriptors through the general path)
+    FUZZ_REF=1 python tests/fuzz_hostsim.py general 0 2000  (the reference's own matcher as a third party)
 
-Needs tests/_build/hostsim_check (built by tests/test_hostsim.py).
+Needs tests/_build/hostsim_check (built by tests/test_hostsim.py).  FUZZ_REF=1 needs oracle/_ref/find_motif_drv
+(oracle/Makefile, where the reference's sources are; tests/_build/program_dump is built at the start): every descriptor's oracle records are then also compared, as the listing of
+tests/test_ref_matcher.py, with what the reference's find_motif.c finds.  No pins: campaigns run where the reference is.
 
 Round 3: `lean 0 1500` -- 1471 generated lean descriptors, each candidate's order word (the number of the walk's
 choices, as the kernels store it) checked to grow along the walk: no mismatch, no order word out of place."""
@@ -19,6 +22,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 BIN = os.path.join(ROOT, "tests", "_build", "hostsim_check")
+WITH_REF = os.environ.get("FUZZ_REF") == "1"
+
+
+def reference_differs(tmp, argv, d, seqs):
+    """the reference's matcher (oracle/_ref/find_motif_drv) against the oracle on these entries"""
+    import test_ref_matcher as M
+    from oracle_binding import oracle_scan
+    if d.loose:
+        return False
+    prog, db = os.path.join(tmp, "f.prog"), os.path.join(tmp, "f.seqs")
+    subprocess.run([M.DUMP, prog] + argv, check=True, timeout=300)
+    with open(db, "wb") as f:
+        f.write(b"".join(q + b"\n" for q in seqs))
+    p = subprocess.run([M.REF, prog, db], stdout=subprocess.PIPE, timeout=1800)
+    want = (M.md5(p.stdout), p.stdout.count(b"\n"))
+    return p.returncode != 0 or M._listing(oracle_scan(d, seqs), d.n_elems) != want
 
 
 def one(job):
@@ -42,6 +61,8 @@ def one(job):
         if d.maxlen > (400 if lean else 160):
             return seed, "skip", ""
         s = T._planted_sequence(rng, 6000)
+        if WITH_REF and reference_differs(tmp, argv, d, [s, s[:301], s[:d.maxlen], s[:d.minlen]]):
+            return seed, "BAD-REF", text + "\n" + " ".join(argv) + "\n"
         fa = os.path.join(tmp, "db.fastn")
         with open(fa, "wb") as f:
             for i, q in enumerate((s, s[:301], s[:d.maxlen], s[:d.minlen])):
@@ -64,6 +85,11 @@ def one(job):
 def main():
     kind, lo, hi = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
     workers = int(sys.argv[4]) if len(sys.argv) > 4 else 7
+    if WITH_REF:
+        import test_ref_matcher as M
+        M.build_program_dump()
+        if not os.path.exists(M.REF):
+            sys.exit("FUZZ_REF=1 needs oracle/_ref/find_motif_drv (make -C oracle ref, where the reference's sources are)")
     ran = bad = 0
     with ProcessPoolExecutor(workers) as ex:
         for seed, what, text in ex.map(one, [(kind, s) for s in range(lo, hi)], chunksize=4):

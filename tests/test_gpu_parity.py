@@ -602,12 +602,15 @@ def test_efn2_sites_equal_oracle(built, workdir, gbrna, name):
         assert np.all(np.abs(e2) < 100000)          # closed structures: always defined
 
 
-def test_helices_of_64_to_127_base_pairs(built, tmp_path):
-    """Helices longer than 63 base pairs (refused until round 3): the general instance whose sets of helix lengths are two
-    words (rm_scan_core.h rmd_lset_t, RMD_KIND_WIDE; the reference keeps a helix' candidates in h3[ 101 ], find_motif.c:406).
-    Planted hairpins of 63 to 127 base pairs in random sequence, with and without a mispair: records equal the oracle's."""
-    import rnamotif_amd as R
-    from oracle_binding import oracle_scan
+# (descriptor, fewest candidates expected); the last: a pseudoknot whose first helix may be that long
+WIDE_DESCRS = [("descr\n\th5(minlen=20,maxlen=110,mispair=1)\n\t\tss(minlen=3,maxlen=8)\n\th3\n", 1000),
+               ("parms\n\twc += gu;\ndescr\n\th5(minlen=60,maxlen=127)\n\t\tss(minlen=3,maxlen=8)\n\th3\n", 500),
+               ("descr\n\th5(tag='a',minlen=30,maxlen=80)\n\t\tss(minlen=1,maxlen=3)\n\th5(tag='b',minlen=3,maxlen=4)\n"
+                "\t\tss(minlen=0,maxlen=3)\n\th3(tag='a')\n\t\tss(minlen=1,maxlen=30)\n\th3(tag='b')\n", 500)]
+
+
+def _wide_sequences():
+    """planted hairpins of 63 to 127 base pairs in random sequence"""
     rng = np.random.default_rng(5)
     lut = np.frombuffer(b"acgt", dtype=np.uint8)
     comp = bytes.maketrans(b"acgt", b"tgca")
@@ -617,11 +620,17 @@ def test_helices_of_64_to_127_base_pairs(built, tmp_path):
         stem = rnd(hl)
         seqs.append(rnd(30) + stem + rnd(loop) + stem.translate(comp)[::-1] + rnd(25))
     seqs.append(rnd(3000))
-    for text, least in (("descr\n\th5(minlen=20,maxlen=110,mispair=1)\n\t\tss(minlen=3,maxlen=8)\n\th3\n", 1000),
-                        ("parms\n\twc += gu;\ndescr\n\th5(minlen=60,maxlen=127)\n\t\tss(minlen=3,maxlen=8)\n\th3\n", 500),
-                        # (a pseudoknot whose first helix may be that long)
-                        ("descr\n\th5(tag='a',minlen=30,maxlen=80)\n\t\tss(minlen=1,maxlen=3)\n\th5(tag='b',minlen=3,maxlen=4)\n"
-                         "\t\tss(minlen=0,maxlen=3)\n\th3(tag='a')\n\t\tss(minlen=1,maxlen=30)\n\th3(tag='b')\n", 500)):
+    return seqs
+
+
+def test_helices_of_64_to_127_base_pairs(built, tmp_path):
+    """Helices longer than 63 base pairs (refused until round 3): the general instance whose sets of helix lengths are two
+    words (rm_scan_core.h rmd_lset_t, RMD_KIND_WIDE; the reference keeps a helix' candidates in h3[ 101 ], find_motif.c:406).
+    Planted hairpins of 63 to 127 base pairs in random sequence, with and without a mispair: records equal the oracle's."""
+    import rnamotif_amd as R
+    from oracle_binding import oracle_scan
+    seqs = _wide_sequences()
+    for text, least in WIDE_DESCRS:
         (tmp_path / "wide.descr").write_text(text)
         d = R.Descriptor(["-descr", str(tmp_path / "wide.descr")])
         sc = R.Scanner(d)
@@ -867,6 +876,22 @@ def _random_descriptor(rng):
     return parms + "descr\n" + "\n".join(lines) + "\n"
 
 
+def _nested_sequence(rng):
+    """12 000 bases of biased composition with planted inverted repeats, so that helices actually form"""
+    lut = np.frombuffer(b"acgtn", dtype=np.uint8)
+    n = 12_000
+    v = rng.choice(5, size=n, p=[0.2, 0.3, 0.3, 0.19, 0.01])
+    s = bytearray(lut[v].tobytes())
+    comp = {ord("a"): ord("t"), ord("c"): ord("g"), ord("g"): ord("c"), ord("t"): ord("a"), ord("n"): ord("n")}
+    for _ in range(150):
+        a = int(rng.integers(0, n - 80))
+        k = int(rng.integers(4, 10))
+        gap = int(rng.integers(3, 50))
+        if a + 2 * k + gap < n:
+            s[a + k + gap:a + 2 * k + gap] = bytes(comp[c] for c in reversed(s[a:a + k]))
+    return bytes(s)
+
+
 @pytest.mark.parametrize("seed", range(160))
 def test_random_descriptors_equal_oracle(built, tmp_path, seed):
     """Differential test over generated descriptors: every pruning rule, tile choice and queue
@@ -888,19 +913,9 @@ def test_random_descriptors_equal_oracle(built, tmp_path, seed):
         sc = R.Scanner(d)
     except R.RnamotifError as e:
         pytest.skip("refused by the device build: " + str(e))
-    lut = np.frombuffer(b"acgtn", dtype=np.uint8)
-    # biased composition and planted inverted repeats so that helices actually form
-    n = 12_000
-    v = rng.choice(5, size=n, p=[0.2, 0.3, 0.3, 0.19, 0.01])
-    s = bytearray(lut[v].tobytes())
-    comp = {ord("a"): ord("t"), ord("c"): ord("g"), ord("g"): ord("c"), ord("t"): ord("a"), ord("n"): ord("n")}
-    for _ in range(150):
-        a = int(rng.integers(0, n - 80))
-        k = int(rng.integers(4, 10))
-        gap = int(rng.integers(3, 50))
-        if a + 2 * k + gap < n:
-            s[a + k + gap:a + 2 * k + gap] = bytes(comp[c] for c in reversed(s[a:a + k]))
-    seqs = [bytes(s), bytes(s[:257])]
+    s = _nested_sequence(rng)
+    n = len(s)
+    seqs = [s, s[:257]]
     want = oracle_scan(d, seqs)
     if want.shape[0] > 400_000:
         pytest.skip("too many candidates for a quick run")
@@ -1023,6 +1038,15 @@ def _planted_sequence(rng, n):
     return bytes(s)
 
 
+def _stress_entries(s, d):
+    """entries of awkward lengths: empty, shorter than the motif, of exactly its shortest and longest, one more"""
+    return [s, b"", s[:max(d.minlen - 1, 0)], s[:d.minlen], s[:d.maxlen], s[:d.maxlen + 1], s[100:100 + 255], s[7:7 + 513]]
+
+
+def _drain_entries(s, d, rng):
+    return [s, b"", s[:d.minlen], s[:d.maxlen + 1], s[100:100 + 2047], _planted_sequence(rng, 3_000)]
+
+
 @pytest.mark.parametrize("strict", [False, True])
 @pytest.mark.parametrize("seed", range(40))
 def test_random_general_descriptors_equal_oracle(built, tmp_path, seed, strict):
@@ -1081,7 +1105,7 @@ def test_random_descriptors_under_stress_settings(built, tmp_path, seed, gen):
     if d.maxlen > 160:
         pytest.skip("window too large for a quick differential run")
     s = _planted_sequence(rng, 5_000)
-    seqs = [s, b"", s[:max(d.minlen - 1, 0)], s[:d.minlen], s[:d.maxlen], s[:d.maxlen + 1], s[100:100 + 255], s[7:7 + 513]]
+    seqs = _stress_entries(s, d)
     want = oracle_scan(d, seqs)
     if want.shape[0] > 300_000:
         pytest.skip("too many candidates for a quick run")
@@ -1107,13 +1131,8 @@ def test_random_descriptors_under_stress_settings(built, tmp_path, seed, gen):
     assert np.array_equal(got, want), text
 
 
-@pytest.mark.parametrize("variant", ["anchored", "floating", "mismatch", "helix", "ranges"])
-def test_long_seq_expressions(built, tmp_path, variant):
-    """seq= expressions of 64 to 127 positions (the device's position automaton takes two words a set
-    of states since round 3; round 2 refused them): planted occurrences, exact and with mismatches,
-    anchored and not, on a single strand and on a helix strand, with repeat ranges -- records equal to the oracle's."""
-    import rnamotif_amd as R
-    from oracle_binding import oracle_scan
+def _long_seq_case(variant):
+    """descriptor text and entries of test_long_seq_expressions"""
     rng = np.random.default_rng(404)
     lut = np.frombuffer(b"acgt", dtype=np.uint8)
     word = lut[rng.integers(0, 4, size=80)].tobytes().decode()
@@ -1128,9 +1147,6 @@ def test_long_seq_expressions(built, tmp_path, variant):
     else:
         stem = lut[rng.integers(0, 4, size=12)].tobytes().decode()
         text = 'descr\n\tss(minlen=66,maxlen=70,seq="^%s")\n\th5(len=6)\n\t\tss(minlen=4,maxlen=8)\n\th3\n' % word[:66]
-    path = tmp_path / "long.descr"
-    path.write_text(text)
-    d = R.Descriptor(["-descr", str(path)])
     comp = bytes.maketrans(b"acgt", b"tgca")
     seqs = []
     for k in range(6):
@@ -1150,6 +1166,20 @@ def test_long_seq_expressions(built, tmp_path, variant):
                 bg[pos:pos + len(w)] = w
         s_ = bytes(bg)
         seqs.append(s_ if k % 2 == 0 else s_.translate(comp)[::-1])
+    return text, seqs
+
+
+@pytest.mark.parametrize("variant", ["anchored", "floating", "mismatch", "helix", "ranges"])
+def test_long_seq_expressions(built, tmp_path, variant):
+    """seq= expressions of 64 to 127 positions (the device's position automaton takes two words a set
+    of states since round 3; round 2 refused them): planted occurrences, exact and with mismatches,
+    anchored and not, on a single strand and on a helix strand, with repeat ranges -- records equal to the oracle's."""
+    import rnamotif_amd as R
+    from oracle_binding import oracle_scan
+    text, seqs = _long_seq_case(variant)
+    path = tmp_path / "long.descr"
+    path.write_text(text)
+    d = R.Descriptor(["-descr", str(path)])
     want = oracle_scan(d, seqs)
     assert want.shape[0] > 0
     sc = R.Scanner(d)
@@ -1177,7 +1207,7 @@ def test_random_lean_descriptors_through_the_drain_kernel(built, tmp_path, seed)
     if d.maxlen > 200:
         pytest.skip("window too large for a quick differential run")
     s = _planted_sequence(rng, 20_000)
-    seqs = [s, b"", s[:d.minlen], s[:d.maxlen + 1], s[100:100 + 2047], _planted_sequence(rng, 3_000)]
+    seqs = _drain_entries(s, d, rng)
     want = oracle_scan(d, seqs)
     if want.shape[0] > 300_000:
         pytest.skip("too many candidates for a quick run")
@@ -1266,6 +1296,18 @@ Q1_VARIANTS = [
 ]
 
 
+def _q1_case(variant):
+    """descriptor text and G-rich entries of test_leading_4plex_strand_filter"""
+    attrs, after = Q1_VARIANTS[variant]
+    text = ("descr\n\tq1( tag='1', %s )\n\t\tss( minlen=2, maxlen=6 )\n\tq2( tag='1' )\n\t\tss( minlen=2, maxlen=6 )\n"
+            "\tq3( tag='1' )\n\t\tss( minlen=2, maxlen=6 )\n\tq4( tag='1' )\n" % attrs) + after
+    rng = np.random.default_rng(40 + variant)
+    lut = np.frombuffer(b"acgtn", dtype=np.uint8)
+    seqs = [lut[rng.choice(5, size=n, p=pr)].tobytes()
+            for n, pr in ((60_000, [.15, .1, .55, .2, 0]), (20_003, [.3, .1, .3, .3, 0]), (9_000, [.1, .1, .5, .28, .02]), (70, [.1, .1, .6, .2, 0]))]
+    return text, seqs
+
+
 @pytest.mark.parametrize("variant", range(len(Q1_VARIANTS)))
 def test_leading_4plex_strand_filter(built, tmp_path, variant):
     """A 4-plex at the head of the search list takes the pre-filter's strand filter (rmd_q1filter_t),
@@ -1273,16 +1315,10 @@ def test_leading_4plex_strand_filter(built, tmp_path, variant):
     on G-rich sequence (where 4-plexes and triplexes do occur), for several shapes of the two."""
     import rnamotif_amd as R
     from oracle_binding import oracle_scan
-    attrs, after = Q1_VARIANTS[variant]
-    text = ("descr\n\tq1( tag='1', %s )\n\t\tss( minlen=2, maxlen=6 )\n\tq2( tag='1' )\n\t\tss( minlen=2, maxlen=6 )\n"
-            "\tq3( tag='1' )\n\t\tss( minlen=2, maxlen=6 )\n\tq4( tag='1' )\n" % attrs) + after
+    text, seqs = _q1_case(variant)
     p = tmp_path / "q.descr"
     p.write_text(text)
     d = R.Descriptor(["-descr", str(p)])
-    rng = np.random.default_rng(40 + variant)
-    lut = np.frombuffer(b"acgtn", dtype=np.uint8)
-    seqs = [lut[rng.choice(5, size=n, p=pr)].tobytes()
-            for n, pr in ((60_000, [.15, .1, .55, .2, 0]), (20_003, [.3, .1, .3, .3, 0]), (9_000, [.1, .1, .5, .28, .02]), (70, [.1, .1, .6, .2, 0]))]
     want = oracle_scan(d, seqs)
     sc = R.Scanner(d)
     got = sc.scan(sc.database(seqs))
