@@ -41,7 +41,7 @@ def main():
         sc = R.Scanner(d, device=0)
         db = sc.database(seqs)
         out = {"descr": os.path.basename(path), "bases": db.bases, "env": args.env}
-        for name, dbg in (("all", None), ("pass_a_only", "1")):
+        for name, dbg in (("all", None), ("pass_a_only", R.DBG["NO_PASS_B"])):
             if dbg is not None and args.quick:
                 continue
             sc.set_option("dbg", int(dbg or 0) | args.dbg_or)
@@ -55,7 +55,7 @@ def main():
                 out["candidates"] = n
                 out["efn_ms"] = round(e_ms, 3)
         if not args.quick:
-            sc.set_option("dbg", 34 | args.dbg_or)     # 2: count queued items, 32: wave cycles per phase
+            sc.set_option("dbg", R.DBG["COUNT_QUEUED"] | R.DBG["CYCLES"] | args.dbg_or)
             sys.stderr.flush()
             sc.scan_device(db)      # prints "[dbg] queued items" on stderr
         sc.set_option("dbg", 0)

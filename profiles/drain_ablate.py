@@ -15,7 +15,7 @@ for what, seqs in (("synthetic", R.synthetic_records(100)), ("gbrna x 44", one *
     db = sc.database(seqs)
     sc.scan_device(db)
     out = []
-    for name, bits in (("items taken and dropped", 268435456), ("no hand-overs", 4194304), ("whole", 0)):
+    for name, bits in (("items taken and dropped", R.DBG["DRAIN_DROP"]), ("no hand-overs", R.DBG["NO_FORKS"]), ("whole", 0)):
         sc.set_option("dbg", bits)
         ks = []
         for _ in range(5):
@@ -24,7 +24,7 @@ for what, seqs in (("synthetic", R.synthetic_records(100)), ("gbrna x 44", one *
         out.append("%s %.3f ms (%d candidates)" % (name, min(ks), n))
     sc.set_option("dbg", 0)
     print("==", what, "drain kernel:", ", ".join(out), flush=True)
-    sc.set_option("dbg", 536870912)
+    sc.set_option("dbg", R.DBG["DRAIN_DONE"])
     sc.scan_device(db)
     sc.set_option("dbg", 0)
     sys.stderr.flush()

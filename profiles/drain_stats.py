@@ -18,7 +18,7 @@ for what, seqs in (("synthetic", R.synthetic_records(100)), ("gbrna x 44", one *
     k = sc.last_kernel_ms()
     print(f"== {what}: search {k[0]:.3f} + drain {k[1]:.3f} ms", flush=True)
     sys.stderr.flush()
-    sc.set_option("dbg", 32)
+    sc.set_option("dbg", R.DBG["CYCLES"])
     sc.scan_device(db)
     sc.set_option("dbg", 0)
     sys.stderr.flush()

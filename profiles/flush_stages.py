@@ -18,7 +18,7 @@ for name in names:
     db = sc.database(seqs)
     sc.scan_device(db)
     out = []
-    for what, bits in (("decode+rows", 65536), ("+chain", 131072), ("+pre-filter", 1), ("whole", 0)):
+    for what, bits in (("decode+rows", R.DBG["STOP_ROWS"]), ("+chain", R.DBG["STOP_CHAIN"]), ("+pre-filter", R.DBG["NO_PASS_B"]), ("whole", 0)):
         sc.set_option("dbg", bits)
         ks = []
         for _ in range(5):
@@ -27,7 +27,7 @@ for name in names:
         out.append("%s %.3f (+ %.3f)" % (what, min(k[0] for k in ks), min(k[1] for k in ks)))
     sc.set_option("dbg", 0)
     print("==", name, "(search kernel ms, cumulative; drain kernel):", ", ".join(out), flush=True)
-    sc.set_option("dbg", 32)
+    sc.set_option("dbg", R.DBG["CYCLES"])
     sc.scan_device(db)
     sc.set_option("dbg", 0)
     db.close()

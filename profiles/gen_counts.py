@@ -17,7 +17,7 @@ for name in names:
     db = sc.database(seqs)
     sc.scan_device(db)
     print("==", name, "search %.3f ms" % min(sc.scan_device(db)[1] for _ in range(3)), flush=True)
-    sc.set_option("dbg", 34)
+    sc.set_option("dbg", R.DBG["COUNT_QUEUED"] | R.DBG["CYCLES"])
     sc.scan_device(db)
     sys.stderr.flush()
     db.close()

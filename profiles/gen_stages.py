@@ -17,7 +17,7 @@ for name in names:
     db = sc.database(seqs)
     sc.scan_device(db)
     out = []
-    for what, bits in (("decode+rows", 65536), ("+vectors", 131072), ("+pre-filter", 1), ("whole", 0)):
+    for what, bits in (("decode+rows", R.DBG["STOP_ROWS"]), ("+vectors", R.DBG["STOP_CHAIN"]), ("+pre-filter", R.DBG["NO_PASS_B"]), ("whole", 0)):
         sc.set_option("dbg", bits)
         ks = []
         for _ in range(4):

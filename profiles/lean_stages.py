@@ -19,7 +19,7 @@ for name in names:
     db = sc.database(seqs)
     sc.scan_device(db)
     out = []
-    for what, bits in (("decode+rows", 65536), ("+chain", 131072), ("+pre-filter", 1), ("+stem-loop tests", 2048), ("whole", 0)):
+    for what, bits in (("decode+rows", R.DBG["STOP_ROWS"]), ("+chain", R.DBG["STOP_CHAIN"]), ("+pre-filter", R.DBG["NO_PASS_B"]), ("+stem-loop tests", R.DBG["POOL_DROP"]), ("whole", 0)):
         sc.set_option("dbg", bits)
         out.append("%s %.3f" % (what, min(sc.scan_device(db)[1] for _ in range(5))))
     sc.set_option("dbg", 0)

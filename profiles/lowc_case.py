@@ -36,7 +36,7 @@ s = b"".join(parts)[:6000]
 seqs = [s]
 sc = R.Scanner(d)
 db = sc.database(seqs)
-sc.set_option("dbg", 2 + 32)
+sc.set_option("dbg", R.DBG["COUNT_QUEUED"] | R.DBG["CYCLES"])
 t0 = time.time()
 n = sc.scan_device(db)[0]
 dt = time.time() - t0

@@ -19,16 +19,16 @@ for name in names:
     sc.scan_device(db)
     best = lambda: min(sc.scan_device(db)[1] for _ in range(5))
     print("==", name, "search %.3f ms" % best(), flush=True)
-    sc.set_option("dbg", 2097152)
+    sc.set_option("dbg", R.DBG["WHOLE_ITEMS"])
     print("   items whole in the drain kernel's list: %.3f ms" % best(), flush=True)
     sc.set_option("dbg", 0)
     sc.set_option("drain", 0)
     print("   no drain kernel: %.3f ms" % best(), flush=True)
     sc.set_option("drain", 1)
-    sc.set_option("dbg", 2 + 1048576)
+    sc.set_option("dbg", R.DBG["COUNT_QUEUED"] | R.DBG["TIMELINE"])
     sc.scan_device(db)
     sys.stderr.flush()
-    sc.set_option("dbg", 34)
+    sc.set_option("dbg", R.DBG["COUNT_QUEUED"] | R.DBG["CYCLES"])
     sc.scan_device(db)
     sys.stderr.flush()
     sc.set_option("dbg", 0)

@@ -28,6 +28,20 @@ CLI_PATH = os.path.join(_HERE, "bin", "rnamotif")
 RMA_HIT_HDR = 5
 _ERRLEN = 4096
 
+# The bits of Scanner.set_option("dbg", ...) and RNAMOTIF_DBG: RMK_DBG_* of csrc/rm_diag.h, which says what each does
+# (tests/test_diag_names.py holds the two together).
+DBG = {
+    # path selectors
+    "GENERAL": 16, "POOL_DROP": 2048, "WHOLE_ITEMS": 2097152, "NO_FORKS": 4194304, "LIST_ALL": 8388608,
+    # ablation switches
+    "NO_PASS_B": 1, "NO_BITPAR": 4, "NO_LITERAL": 8, "NO_ROWS": 64, "NO_VOTE": 128, "NO_SPLIT": 256,
+    "NO_STEP_CHAIN": 512, "NO_HEAD_TEST": 4096, "NO_Q1_FILTER": 8192, "NO_TRI_FILTER": 16384, "NO_CHAIN": 32768,
+    "STOP_ROWS": 65536, "STOP_CHAIN": 131072, "NO_HEAD_NEXT": 262144, "NO_START_VEC": 33554432,
+    "TICKET_PER_TILE": 67108864, "HEAD_ALL_ENDS": 134217728, "DRAIN_DROP": 268435456,
+    # instrumentation
+    "COUNT_QUEUED": 2, "CYCLES": 32, "TIMELINE": 1048576, "DRAIN_DONE": 536870912,
+}
+
 
 class RnamotifError(RuntimeError):
     pass

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
 #include "rm_dev_program.h"
+#include "rm_diag.h"		// the bits of rmk_search_args::dbg, the words behind HitBuf::count (RMK_N_COUNTERS of them)
 
 // ---------------------------------------------------------------- device views
 struct DbView {
@@ -33,8 +34,8 @@ struct HitBuf {
 	int	pool_cap, pool_min;	// ... searched once pool_min of them have come together
 	int	pool_refill;		// idle lanes of a wave that pop together
 	// pooled instance with a drain kernel (glist_cap > 0): the device-wide list the workgroups' pools are flushed to
-	// is the first glist_cap items at `pool`, the workgroups' own areas come after it; ticket[ RMK_GCTL - 1 ] counts
-	// the items reserved in it (may exceed glist_cap), ticket[ RMK_GCTL ] those taken (rma_drain_kernel)
+	// is the first glist_cap items at `pool`, the workgroups' own areas come after it; RMK_C_LIST_RESERVED counts
+	// the items reserved in it (may exceed glist_cap), RMK_C_LIST_TAKEN those taken (rma_drain_kernel)
 	int	glist_cap;
 };
 
@@ -88,9 +89,7 @@ enum { RMK_META_SEQ = 0, RMK_META_COMP, RMK_META_Z0, RMK_META_SLEN, RMK_META_OFF
 #define SHORT_ENTRY_MEAN	4000	// ... which are those whose entries average less than this
 #define SPILL_ITEMS		8192	// queue items per workgroup that may overflow into HBM (32 KB each, 64 MB in all)
 #define RMK_POOL_WORDS		5	// entry, start, rank | strand, and the 3' ends the first helix of the interior may take (two outer lengths)
-#define RMK_N_COUNTERS		128	// 64-bit counters behind a launch: [0] candidates, [1] ticket, diagnostics, [RMK_GCTL] the list's two
-#define RMK_GCTL		100
-#define PIECE_ORDER_BITS	12	// candidates a piece of an item may find; more, and the search is repeated with whole items (ticket[ 2 ])
+#define PIECE_ORDER_BITS	12	// candidates a piece of an item may find; more, and the search is repeated with whole items (RMK_C_PIECE_OVERFLOW)
 #define GLIST_BELOW		128	// what a workgroup's pool holds at the end goes to the list when it is less than this
 #define SEARCH_BLOCK		256	// lanes of a search workgroup of the lean instances
 // ... and of the general instances: ONE wave.  The waves of a four-wave workgroup met at the end of

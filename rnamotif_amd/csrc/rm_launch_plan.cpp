@@ -216,7 +216,7 @@ ProgramPlan plan_program( const rma_program_t &prog, const rmd_program_t &dp, in
 // the pooled instance that walks nothing: where it can run (plan_program) and the options do not ask for the other one
 static bool use_flush( const ProgramPlan &pp, const Options &o )
 {
-	return pp.flush && o.drain != 0 && o.pool != 0 && !( o.dbg & ( 16 | 2048 | 8388608 ) ) &&
+	return pp.flush && o.drain != 0 && o.pool != 0 && !( o.dbg & ( RMK_DBG_GENERAL | RMK_DBG_POOL_DROP | RMK_DBG_LIST_ALL ) ) &&
 		( o.flush < 0 ? pp.dp->chain.on != 0 : o.flush != 0 );
 }
 
@@ -225,7 +225,7 @@ static bool use_flush( const ProgramPlan &pp, const Options &o )
 static bool pooled_fits( const ProgramPlan &pp, const Options &o, int tile_t, bool flush = false )
 {
 	const rmd_program_t	&dp = *pp.dp;
-	if( !dp.lean_ok || ( o.dbg & 16 ) )
+	if( !dp.lean_ok || ( o.dbg & RMK_DBG_GENERAL ) )
 		return false;
 	if( flush )		// (the instance that walks nothing lays out no window: plan_program asked what the drain kernel asks)
 		return use_flush( pp, o );
@@ -259,7 +259,7 @@ LayoutKey choose_layout( const ProgramPlan &pp, const Options &o, const DbShape 
 	// -- whole start positions only (no slices), entries in order in the packed arrays, positions within 30 bits.
 	k.concat = ( o.short_force < 0 ? short_db : o.short_force == 2 ) && n >= 1 &&
 		!db.ranges && db.ascending && db.padded_bases < ( int64_t( 1 ) << 30 ) &&
-		( pooled_fits( pp, o, k.tile_t ) || !dp.lean_ok || ( o.dbg & 16 ) ) && !dp.wide;		// (the pooled lean instance, or a general one)
+		( pooled_fits( pp, o, k.tile_t ) || !dp.lean_ok || ( o.dbg & RMK_DBG_GENERAL ) ) && !dp.wide;		// (the pooled lean instance, or a general one)
 	if( k.concat )
 		grouped = false;
 	// (long entries, a descriptor with a look-ahead chain: the instance that walks nothing, on tiles of its own size)
@@ -268,7 +268,7 @@ LayoutKey choose_layout( const ProgramPlan &pp, const Options &o, const DbShape 
 		k.tile_t = o.tile > 0 ? o.tile : pp.tile_t_flush;
 		k.qcap = pp.qcap_flush;
 	}
-	if( grouped && dp.lean_ok && !( o.dbg & 16 ) ){
+	if( grouped && dp.lean_ok && !( o.dbg & RMK_DBG_GENERAL ) ){
 		const size_t	budget = ( 160 * 1024 ) / SEARCH_WAVES_PER_SIMD - 64 - SHORT_GROUP * 32;
 		const int	q = o.qcap > 0 ? std::max( 64, o.qcap ) : 256;	// LDS goes to the slots; what a group queues beyond this spills (tests: force the overflow path)
 		// (tiles of 1024 positions measured slower than of 768 where both fit: mp.ends 1.56 / 1.40 ms)
@@ -367,7 +367,7 @@ int plan_launch( const LayoutKey &k, int64_t n_tiles, const ProgramPlan &pp, con
 	LaunchPlan	&p = *out;
 	p = LaunchPlan();
 	const int	grid_blocks = cus * 8;		// most workgroups of a launch of a lean instance (eight of four waves per CU)
-	p.lean = dp.lean_ok && !( o.dbg & 16 );
+	p.lean = dp.lean_ok && !( o.dbg & RMK_DBG_GENERAL );
 	p.grouped = p.lean && k.group > 1;
 	p.tile_bytes = k.tile_t + dp.w_winsize + dp.lmargin + dp.rmargin + 80;
 	p.lds = search_lds_bytes( pp.prog_bytes, dp, k.tile_t, p.lean, k.qcap, p.grouped ? SHORT_GROUP : 1, p.lean && k.flush );

@@ -45,6 +45,13 @@ __device__ inline int db_strand_code( const DbView &db, int64_t off, int slen, i
 	return ( comp && c < 4 ) ? 3 - c : c;
 }
 
+// Word SLOT of the counter block (RMK_C_*, rm_diag.h) from the pointer the kernels have: HitBuf::ticket is word RMK_C_TICKET.
+template< int SLOT > __device__ inline unsigned long long *rmk_ctr( const HitBuf &hb )
+{
+	static_assert( SLOT >= RMK_C_TICKET && SLOT < RMK_N_COUNTERS, "a slot of the counter block" );
+	return hb.ticket + ( SLOT - RMK_C_TICKET );
+}
+
 struct DevSink {
 	HitBuf	hb;
 	int	seq, comp, stride;
@@ -55,7 +62,6 @@ struct DevSink {
 			rmd_fill_hit( P, L, seq, comp, szero, hb.hits + slot * stride );
 	}
 };
-
 
 // Lean path records of one lane in LDS, 6 bytes per level: windows of lean descriptors are
 // shorter than 4096 (rmd_build), so window start and saved end take 12 bits each, the next
@@ -230,7 +236,7 @@ __device__ inline void wave_emit_pending( const rmd_program_t *P, const LdsRecs<
 		const int	l = __ffsll( em ) - 1;
 		const LdsRecs<BLOCK>	lrl{ lr.lo + ( l - lane_id ), lr.hi + ( l - lane_id ) };
 		if( lane_id == l && st.only_hl >= 0 && !P->ord_ok && st.order >= ( 1 << PIECE_ORDER_BITS ) )
-			atomicMax( hb.ticket + 2, 1ull );	// (the pieces' order words would run into each other)
+			atomicMax( rmk_ctr<RMK_C_PIECE_OVERFLOW>( hb ), 1ull );	// (the pieces' order words would run into each other)
 		bool	stored;
 		if constexpr( INLINE )
 			stored = wave_emit_body<BLOCK>( P, lrl, sq_of( l ), __shfl( st.szero, l ), __shfl( st.slen, l ), __shfl( st.rank, l ),
@@ -580,7 +586,7 @@ __device__ PASS_B_ATTR void general_pass_b( const GenTile gt, DevSink sink )
 			// every element type: 12 bytes of search state per level, in LDS (rmd_grec_t)
 			rmd_gen_t	st;
 			unsigned	cur_item = 0;
-			RowEnds<KINDS>	ends{ pb, tile, pb_words, p_lo, ( dbg & 64 ) ? 0 : vec_words * 64 };	// (bit 64: end by end, no rows)
+			RowEnds<KINDS>	ends{ pb, tile, pb_words, p_lo, ( dbg & RMK_DBG_NO_ROWS ) ? 0 : vec_words * 64 };	// (RMK_DBG_NO_ROWS: end by end)
 			// Tiles over a concatenation of entries (CONCAT): an item that is popped is brought to its entry's coordinates
 			// (super_convert) and walked there -- the tile's bytes and rows seen from the entry's first base, the entry's
 			// length and number; an item that belongs to no entry is dropped.  szero / r of the item at hand:
@@ -645,13 +651,13 @@ __device__ PASS_B_ATTR void general_pass_b( const GenTile gt, DevSink sink )
 							continue;
 						break;
 					}
-					if( dbg & 32 ){
+					if( dbg & RMK_DBG_CYCLES ){
 						// diagnostic: per search level, wave rounds with a lane on it and lanes served
 						for( int kk = 0; kk < P->n_searches; kk++ ){
 							const unsigned long long	mk = __ballot( k == kk );
 							if( mk && lane_id == 0 ){
-								atomicAdd( hb.ticket + 15 + 2 * kk, 1ull );
-								atomicAdd( hb.ticket + 16 + 2 * kk, ( unsigned long long )__popcll( mk ) );
+								atomicAdd( rmk_ctr<RMK_C_GEN_LEVEL>( hb ) + 2 * kk, 1ull );
+								atomicAdd( rmk_ctr<RMK_C_GEN_LEVEL + 1>( hb ) + 2 * kk, ( unsigned long long )__popcll( mk ) );
 							}
 						}
 					}
@@ -660,7 +666,7 @@ __device__ PASS_B_ATTR void general_pass_b( const GenTile gt, DevSink sink )
 					// lanes ahead of them have gone dry or caught up), instead of a round per level for a
 					// lane or two each.
 					int	serve = k;
-					if( !( dbg & 128 ) ){
+					if( !( dbg & RMK_DBG_NO_VOTE ) ){
 						int	most = 0;
 						for( int kk = 0; kk < P->n_searches; kk++ ){
 							const int	n = __popcll( __ballot( k == kk ) );
@@ -672,9 +678,9 @@ __device__ PASS_B_ATTR void general_pass_b( const GenTile gt, DevSink sink )
 					}
 					if( k >= 0 && k == serve ){
 						if( round == 0 )
-							k = rmd_gen_step( P, gr, st, sq, k, &lane, sink, ends, split, -1, !( dbg & 512 ) );
+							k = rmd_gen_step( P, gr, st, sq, k, &lane, sink, ends, split, -1, !( dbg & RMK_DBG_NO_STEP_CHAIN ) );
 						else{
-							k = rmd_gen_step( P, gr, st, sq, k, &lane, sink, ends, rmd_no_split_t(), split_s, !( dbg & 512 ) );
+							k = rmd_gen_step( P, gr, st, sq, k, &lane, sink, ends, rmd_no_split_t(), split_s, !( dbg & RMK_DBG_NO_STEP_CHAIN ) );
 							if( k <= split_s )
 								k = -1;		// back at the split level: this alternative is done
 						}
@@ -778,7 +784,7 @@ __device__ inline void pool_sub_piece( unsigned rc, unsigned h0, unsigned h1, in
 // in HBM (HitBuf::glist; a workgroup's pool is flushed there) instead of walking them itself: some twenty
 // per workgroup over trna.descr and 100 Mbases, each a walk of tens of microseconds with a heavy tail -- a
 // workgroup that walked its own kept the device waiting for 0.7 ms after the last tile was done
-// (RNAMOTIF_DBG bit 1048576).  This kernel comes after it on the same stream: workgroups of ONE wave (no
+// (RNAMOTIF_DBG bit RMK_DBG_TIMELINE).  This kernel comes after it on the same stream: workgroups of ONE wave (no
 // barrier anywhere), every wave taking its fair share of the list, then more as lanes come free.
 #define DRAIN_BLOCK	64
 template< int BLOCK >
@@ -797,7 +803,7 @@ rma_drain_kernel( const rmd_program_t *gP, int prog_bytes, DbView db, HitBuf hb,
 	uint16_t	*const lean_hi = reinterpret_cast<uint16_t *>( lean_lo + P->n_searches * BLOCK );
 	LdsRecs<BLOCK>	lr{ lean_lo + tid, lean_hi + tid };
 	const unsigned long long	lt_mask = ( 1ull << lane_id ) - 1;
-	const long long	reserved = ( long long )__hip_atomic_load( hb.ticket + ( RMK_GCTL - 1 ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+	const long long	reserved = ( long long )__hip_atomic_load( rmk_ctr<RMK_C_LIST_RESERVED>( hb ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
 	const long long	total = reserved < hb.glist_cap ? reserved : hb.glist_cap;
 	const long long	n_waves = ( long long )gridDim.x;
 	const long long	share = ( total + n_waves - 1 ) / n_waves;
@@ -811,30 +817,30 @@ rma_drain_kernel( const rmd_program_t *gP, int prog_bytes, DbView db, HitBuf hb,
 	DevSink	sink{ hb, 0, 0, P->hit_stride };
 	const rmd_no_accel_t	none;
 	int	k = -1, n_steps = 0, n_emit = 0, obase = 0, floor_ = 0;
-	const bool	forks = P->ord_ok && !( dbg & 4194304 );
+	const bool	forks = P->ord_ok && !( dbg & RMK_DBG_NO_FORKS );
 	unsigned long long	t_item = 0;
 	bool	dry = total == 0;
-	// (diagnostic, RNAMOTIF_DBG bit 536870912: when the waves are through, in bins of 16 us from the first wave's start)
-	if( ( dbg & 536870912 ) && lane_id == 0 )
-		atomicMax( hb.ticket + 55, ~( unsigned long long )wall_clock64() );
+	// (diagnostic, RMK_DBG_DRAIN_DONE: when the waves are through, in bins of 16 us from the first wave's start)
+	if( ( dbg & RMK_DBG_DRAIN_DONE ) && lane_id == 0 )
+		atomicMax( rmk_ctr<RMK_C_DRAIN_START>( hb ), ~( unsigned long long )wall_clock64() );
 	for( ; ; ){
 		const unsigned long long	want = __ballot( k < 0 && !dry );
 		const unsigned long long	busy = __ballot( k >= 0 );
 		// lanes that came free take items once enough of them have (a round costs the wave the same for one
 		// lane as for sixteen), and no more than leaves the other waves their share
 		const int	n = rmd_imin( __popcll( want ), fair - __popcll( busy ) );
-		// (diagnostic, RNAMOTIF_DBG bit 32: the wave's cycles by what it does -- taking items, stepping, complete matches, hand-overs)
-		unsigned long long	t_d0 = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
-#define DRAIN_LAP( slot_ )	do{ if( dbg & 32 ){ \
+		// (diagnostic, RMK_DBG_CYCLES: the wave's cycles by what it does -- taking items, stepping, complete matches, hand-overs)
+		unsigned long long	t_d0 = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
+#define DRAIN_LAP( lap_ )	do{ static_assert( ( lap_ ) >= 0 && ( lap_ ) < RMK_CN_DRAIN_LAPS, "a lap of the drain kernel" ); if( dbg & RMK_DBG_CYCLES ){ \
 			const unsigned long long	now_ = __builtin_amdgcn_s_memtime(); \
 			if( lane_id == 0 ) \
-				atomicAdd( hb.ticket + ( slot_ ), now_ - t_d0 ); \
+				atomicAdd( rmk_ctr<RMK_C_DRAIN_LAP + ( lap_ )>( hb ), now_ - t_d0 ); \
 			t_d0 = now_; \
 		} }while( 0 )
 		if( n > 0 && ( busy == 0 || n >= refill ) ){
 			unsigned long long	base = 0;
 			if( lane_id == __ffsll( want ) - 1 )
-				base = atomicAdd( hb.ticket + RMK_GCTL, ( unsigned long long )n );
+				base = atomicAdd( rmk_ctr<RMK_C_LIST_TAKEN>( hb ), ( unsigned long long )n );
 			base = __shfl( base, __ffsll( want ) - 1 );
 			if( k < 0 && !dry ){
 				const long long	i = ( long long )base + __popcll( want & lt_mask );
@@ -846,35 +852,35 @@ rma_drain_kernel( const rmd_program_t *gP, int prog_bytes, DbView db, HitBuf hb,
 						nsq.w = col;
 						wlane = lane_id;
 						floor_ = 0;
-						if( dbg & 268435456 )		// (ablation: the item's window is laid out and the item dropped)
+						if( dbg & RMK_DBG_DRAIN_DROP )		// (ablation: the item's window is laid out and the item dropped)
 							k = -1;
-						t_item = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
+						t_item = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
 						n_steps = n_emit = 0;
 					}
 				}else if( ( long long )base + n >= total )
 					dry = true;
 			}
-			DRAIN_LAP( 94 );
+			DRAIN_LAP( 0 );
 			continue;
 		}
 		if( busy == 0 )
 			break;
 		const bool	was = k >= 0;
 		const int	k_was = k;
-		if( ( dbg & 32 ) && lane_id == 0 ){
-			atomicAdd( hb.ticket + 98, 1ull );
-			atomicAdd( hb.ticket + 93, ( unsigned long long )__popcll( busy ) );
+		if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 ){
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_ROUNDS>( hb ), 1ull );
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_LANES>( hb ), ( unsigned long long )__popcll( busy ) );
 		}
 		if( k >= 0 ){
 			k = rmd_lean_step<LdsRecs<BLOCK>, DevSink, rmd_nibseq_t<BLOCK>, rmd_no_accel_t, true>( P, lr, st, nsq, k, nullptr, sink, none );
 			n_steps++;
 			n_emit += st.pending;
 		}
-		DRAIN_LAP( 95 );
+		DRAIN_LAP( 1 );
 		wave_emit_pending<BLOCK, true>( P, lr, st, k, [ & ]( int l ){
 			return rmd_nibseq_t<BLOCK>{ col0 + __shfl( wlane, l ), __shfl( nsq.flip, l ), __shfl( nsq.bias, l ) }; },
 			sink.seq, sink.comp, hb, lane_id, obase );
-		DRAIN_LAP( 96 );
+		DRAIN_LAP( 2 );
 		if( k >= 0 && k < floor_ )
 			k = -1;		// (the subtree this lane was given is done)
 		if( forks ){
@@ -940,32 +946,32 @@ rma_drain_kernel( const rmd_program_t *gP, int prog_bytes, DbView db, HitBuf hb,
 					st.pending = 0;
 					k = k_src;
 					floor_ = k_src;
-					t_item = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
+					t_item = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
 					n_steps = n_emit = 0;
 				}
 				if( giver )
 					k = k_was;	// (back at its own level, the subtree below as good as walked)
 			}
 		}
-		DRAIN_LAP( 97 );
-		if( ( dbg & 32 ) && was && k < 0 ){
+		DRAIN_LAP( 3 );
+		if( ( dbg & RMK_DBG_CYCLES ) && was && k < 0 ){
 			// (diagnostic: how long the items take, how many steps, how many complete matches)
 			const unsigned long long	dt = __builtin_amdgcn_s_memtime() - t_item;
-			atomicAdd( hb.ticket + 23 + ( 63 - __clzll( dt | 1ull ) ), 1ull );
-			atomicMax( hb.ticket + 21, dt );
-			atomicAdd( hb.ticket + 20, dt );
-			atomicAdd( hb.ticket + 17, 1ull );
-			atomicAdd( hb.ticket + 18, ( unsigned long long )n_steps );
-			atomicMax( hb.ticket + 22, ( unsigned long long )n_steps );
-			atomicAdd( hb.ticket + 60 + rmd_imin( 31 - __clz( n_emit | 1 ) + ( n_emit > 0 ), 15 ), 1ull );
-			atomicAdd( hb.ticket + 76 + rmd_imin( 31 - __clz( n_emit | 1 ) + ( n_emit > 0 ), 15 ), dt );
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_LOG2>( hb ) + ( 63 - __clzll( dt | 1ull ) ), 1ull );
+			atomicMax( rmk_ctr<RMK_C_DRAIN_LONGEST>( hb ), dt );
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_CYCLES>( hb ), dt );
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_ITEMS>( hb ), 1ull );
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_STEPS>( hb ), ( unsigned long long )n_steps );
+			atomicMax( rmk_ctr<RMK_C_DRAIN_MOST_STEPS>( hb ), ( unsigned long long )n_steps );
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_EMIT_ITEMS>( hb ) + rmd_imin( 31 - __clz( n_emit | 1 ) + ( n_emit > 0 ), 15 ), 1ull );
+			atomicAdd( rmk_ctr<RMK_C_DRAIN_EMIT_CYCLES>( hb ) + rmd_imin( 31 - __clz( n_emit | 1 ) + ( n_emit > 0 ), 15 ), dt );
 		}
 	}
 #undef DRAIN_LAP
-	if( ( dbg & 536870912 ) && lane_id == 0 ){
-		const unsigned long long	t0 = ~__hip_atomic_load( hb.ticket + 55, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+	if( ( dbg & RMK_DBG_DRAIN_DONE ) && lane_id == 0 ){
+		const unsigned long long	t0 = ~__hip_atomic_load( rmk_ctr<RMK_C_DRAIN_START>( hb ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
 		const unsigned long long	dt = wall_clock64() - t0;		// (100 MHz)
-		atomicAdd( hb.ticket + 23 + rmd_imin( int( dt / 1600 ), 31 ), 1ull );
+		atomicAdd( rmk_ctr<RMK_C_DRAIN_DONE>( hb ) + rmd_imin( int( dt / 1600 ), 31 ), 1ull );
 	}
 }
 
@@ -996,7 +1002,7 @@ rma_drain_kernel( const rmd_program_t *gP, int prog_bytes, DbView db, HitBuf hb,
 // (the headline kernel sits at its 128 registers: a dozen more live values in pass A' cost it a quarter of its speed).
 // WALK = false (pooled instance): the search kernel walks nothing.  What passes pass A' goes straight to the drain kernel's list,
 // cut into its pieces, a wave reserving its items' room with one atomic; queue overflow and a full list are REPORTED
-// (ticket[ RMK_GCTL + 1 ], ticket[ RMK_GCTL - 1 ] > glist_cap) and the host repeats the scan with larger areas, as the general
+// (RMK_C_FLUSH_QUEUE_NEED, RMK_C_LIST_RESERVED > glist_cap) and the host repeats the scan with larger areas, as the general
 // instances do -- no pool, no walk, no in-place search in the kernel: fewer registers, fewer barriers a tile.
 template< int BLOCK, bool LEAN, int G, int KINDS = 0, bool POOL = false, bool CONCAT = false, bool WALK = true >
 __global__ void __launch_bounds__( BLOCK, LEAN ? ( WALK ? SEARCH_WAVES_PER_SIMD : FLUSH_WAVES_PER_SIMD ) : GENERAL_WAVES( KINDS ) )
@@ -1048,9 +1054,9 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 	// helices that allow no mispair at all (find_motif.c:1010-1033 with mplim == 0) take
 	// the bit-parallel pre-filter
 	// first helix of a pseudoknot whose 5' strand starts at the start position
-	const bool	pk0 = e0.type == RMA_T_H5 && !e0.proper && e0.scope == 0 && !( dbg & 4 ) &&
+	const bool	pk0 = e0.type == RMA_T_H5 && !e0.proper && e0.scope == 0 && !( dbg & RMK_DBG_NO_BITPAR ) &&
 		e0.mplim <= 3 && e0.minlen >= 1;
-	const bool	bitpar = ( ( quick && !( dbg & 4 ) ) || pk0 ) && e0.mplim <= 3 && e0.minlen >= 1 && e0.rows == 0;
+	const bool	bitpar = ( ( quick && !( dbg & RMK_DBG_NO_BITPAR ) ) || pk0 ) && e0.mplim <= 3 && e0.minlen >= 1 && e0.rows == 0;
 	const unsigned	e0_mat2 = e0.pairset >= 0 ? rmd_pairsets( P )[ e0.pairset ].mat2 : 0;
 	const bool	e0_at_szero = e0.type == RMA_T_P5 || e0.type == RMA_T_T1 || e0.type == RMA_T_Q1 ||
 		( e0.type == RMA_T_H5 && ( e0.proper || e0.scope == 0 ) );
@@ -1060,7 +1066,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 	const int	n_rs = LEAN ? 1 : P->n_rowsets;
 	// (a 4-plex at the head of the search list: four more, rmd_q1filter_t)
 	const bool	q1f_vecs = !LEAN && ( KINDS & RMD_KIND_TQ ) != 0 && P->q1f.on;
-	const bool	q1f = q1f_vecs && !( dbg & 8192 );
+	const bool	q1f = q1f_vecs && !( dbg & RMK_DBG_NO_Q1_FILTER );
 	// (lean, one tile per pass, with a look-ahead chain: eight more, rmd_chain_t)
 	const bool	chain_on = LEAN && G == 1 && P->chain.on;
 	// (tiles over the concatenation of the entries: super_convert)
@@ -1086,11 +1092,11 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 	LdsRecs<BLOCK>	lr{ lean_lo + threadIdx.x, lean_hi + threadIdx.x };
 	// (the general instance's records take the same place; behind them the resume states of the
 	// levels up to the split level and the queue of continuations)
-	const int	split_s = LEAN || ( dbg & 256 ) ? -1 : P->split_s;
+	const int	split_s = LEAN || ( dbg & RMK_DBG_NO_SPLIT ) ? -1 : P->split_s;
 	uint32_t	*const g_before = lean_lo + ( LEAN ? 0 : P->n_rec_dwords ) * BLOCK;
 	uint32_t	*const g_deep = g_before + 2 * ( split_s + 1 ) * BLOCK;
 	LdsGRecs<BLOCK>	gr{ lean_lo + threadIdx.x, g_before + threadIdx.x, P->rec_off };
-	const bool	lit = P->lit_re >= 0 && !( dbg & 8 );
+	const bool	lit = P->lit_re >= 0 && !( dbg & RMK_DBG_NO_LITERAL );
 	const int	lit_n = lit ? rmd_regexes( P )[ P->lit_re ].n_states : 0;
 	const int	lit_hi = lit ? ( P->lit_hi < w - lit_n ? P->lit_hi : w - lit_n ) : 0;
 	const bool	split_ranks = !quick && lit && n_rank > 1 && n_rank < 0xffff;
@@ -1107,7 +1113,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 	}
 
 	// the same for the first helix of the first element's interior (pooled instance)
-	const bool	head_from_rows = POOL && bitpar && e0.head_s >= 0 && !( dbg & 4096 ) &&
+	const bool	head_from_rows = POOL && bitpar && e0.head_s >= 0 && !( dbg & RMK_DBG_NO_HEAD_TEST ) &&
 		P->elems[ P->searches[ e0.head_s >= 0 ? e0.head_s : 0 ] ].rows == 0;
 
 	// a slot belongs to one wave when G > 1: its phases are ordered within the wave (LDS
@@ -1128,13 +1134,12 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 	// the lane that found it.
 	unsigned	*const spill = hb.spill + size_t( blockIdx.x ) * hb.spill_cap;
 	const int	qtotal = qcap + hb.spill_cap;
-	// diagnostic (RNAMOTIF_DBG bit 32): wave cycles per phase, summed over all waves, into the counters behind
-	// the ticket: 0 ticket + decode, 1 literal vector, 2 pair rows, 3 pre-filter loop, 4 search, 5 waiting for the tile's end
-	unsigned long long	t_ph = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
-#define PHASE( i_ )	do{ if( dbg & 32 ){ \
+	// diagnostic (RMK_DBG_CYCLES): wave cycles by phase, all waves, into RMK_C_PHASE: 0 ticket + decode, 1 literal vector, 2 pair rows, 3 pre-filter loop, 4 search, 5 waiting for the tile's end
+	unsigned long long	t_ph = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
+#define PHASE( i_ )	do{ if( dbg & RMK_DBG_CYCLES ){ \
 			const unsigned long long	now_ = __builtin_amdgcn_s_memtime(); \
 			if( ( threadIdx.x & 63 ) == 0 ) \
-				atomicAdd( hb.ticket + 3 + ( i_ ), now_ - t_ph ); \
+				atomicAdd( rmk_ctr<RMK_C_PHASE>( hb ) + ( i_ ), now_ - t_ph ); \
 			t_ph = now_; \
 		} }while( 0 )
 	const long long	n_units = G > 1 ? ( db.n_tiles + G - 1 ) / G : db.n_tiles;
@@ -1153,7 +1158,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 	// them (trna.descr, 100 Mbase) took the device 0.35 ms to serve, one after the other -- what profiles/flush_stages.py showed
 	// as the kernel's "decode" stage (0.346 ms with nothing but decode in it, 0.14 with the tiles dealt out in advance; that,
 	// though, leaves a workgroup that starts late -- behind another scanner's kernels -- with all its tiles still to do).
-	const long long	n_big = ( G == 1 && !( dbg & 67108864 ) && n_units > ( long long )TICKET_TAIL * gridDim.x ) ?
+	const long long	n_big = ( G == 1 && !( dbg & RMK_DBG_TICKET_PER_TILE ) && n_units > ( long long )TICKET_TAIL * gridDim.x ) ?
 		( n_units - ( long long )TICKET_TAIL * gridDim.x ) / TICKET_TILES : 0ll;
 	long long	t_run = 0, t_run_end = 0;
 	auto	take_tile = [ & ]() -> long long {
@@ -1176,8 +1181,8 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		}
 	}
 	bool	had_tiles = false;
-	if( ( dbg & 1048576 ) && tid == 0 )
-		atomicMax( hb.ticket + 88, ~( unsigned long long )wall_clock64() );	// (the first workgroup's start)
+	if( ( dbg & RMK_DBG_TIMELINE ) && tid == 0 )
+		atomicMax( rmk_ctr<RMK_C_TL_START>( hb ), ~( unsigned long long )wall_clock64() );	// (the first workgroup's start)
 	for( int pass = 0; ; pass++ ){
 		if( tid == 0 ){
 			const long long	t = t_next;
@@ -1213,9 +1218,9 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				last = true;
 			else
 				break;
-			if( ( dbg & 1048576 ) && tid == 0 && had_tiles ){
-				atomicAdd( hb.ticket + 89, ( unsigned long long )wall_clock64() );	// (out of tiles)
-				atomicAdd( hb.ticket + 87, 1ull );
+			if( ( dbg & RMK_DBG_TIMELINE ) && tid == 0 && had_tiles ){
+				atomicAdd( rmk_ctr<RMK_C_TL_DRY_SUM>( hb ), ( unsigned long long )wall_clock64() );	// (out of tiles)
+				atomicAdd( rmk_ctr<RMK_C_TL_WGS>( hb ), 1ull );
 			}
 		}else
 			had_tiles = true;
@@ -1496,7 +1501,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		} }while( 0 )
 
 		if constexpr( G == 1 ){
-			if( dbg & 65536 )		// (ablation: the tile is decoded and its rows are built; nothing is queued)
+			if( dbg & RMK_DBG_STOP_ROWS )		// (ablation: the tile is decoded and its rows are built; nothing is queued)
 				continue;
 		}
 		// Strand filter of a leading 4-plex (rmd_q1filter_t): G2 / G3 -- where a base stands that some quad
@@ -1505,7 +1510,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		unsigned long long	*const xv = pb + 5 * n_rs * pb_words;
 		if( q1f ){
 			const rmd_q1filter_t	F = P->q1f;
-			const bool	tri = F.t_on && !( dbg & 16384 );
+			const bool	tri = F.t_on && !( dbg & RMK_DBG_NO_TRI_FILTER );
 			const int	n_valid = p_to - p_lo, vec_bits = vec_words * 64;
 			// 64 positions from bit x on: can a strand stand there?  dir +1: read from its start onwards;
 			// -1: from its end backwards.  Bits the vectors do not hold: undecided, kept.
@@ -1573,7 +1578,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		// tv[ 5 ], tv[ 6 ]: a group's vector and the next group's, in turns; tv[ 7 ], tv[ 8 ]: the cores of the
 		// first two shapes of stem-loop (kept for pass A'), tv[ 9 ]: those of any other; xv[ 0 ]: the start
 		// positions that remain.
-		const bool	chain = chain_vecs && bitpar && !( dbg & 32768 );
+		const bool	chain = chain_vecs && bitpar && !( dbg & RMK_DBG_NO_CHAIN );
 		if( chain ){
 			const rmd_chain_t	&C = P->chain;
 			const int	vec_bits = vec_words * 64;
@@ -1647,7 +1652,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			__syncthreads();
 		}
 		if constexpr( G == 1 ){
-			if( dbg & 131072 )		// (ablation: ... and the look-ahead chain; nothing is queued)
+			if( dbg & RMK_DBG_STOP_CHAIN )		// (ablation: ... and the look-ahead chain; nothing is queued)
 				continue;
 		}
 		if( bitpar ){
@@ -1702,7 +1707,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			bool	start_vec = chain;
 			const unsigned long long	*src = xv;		// the vector of start positions worth a look
 			if constexpr( !LEAN ){
-				if( q1f && !pk0 && !( dbg & 33554432 ) ){
+				if( q1f && !pk0 && !( dbg & RMK_DBG_NO_START_VEC ) ){
 					// a 4-plex at the head of the search list: the start positions from which its second strand can be
 					// reached (the strand filter's A), with the best literal within reach if there is one
 					src = xv + 2 * pb_words;
@@ -1716,7 +1721,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					start_vec = true;
 				}
 			}
-			if( LEAN && !chain && lit && ( G > 1 || sv_on ) && !( dbg & 33554432 ) ){
+			if( LEAN && !chain && lit && ( G > 1 || sv_on ) && !( dbg & RMK_DBG_NO_START_VEC ) ){
 				// no look-ahead chain, but a best literal: the start positions that have it within reach, as a vector
 				// (ire.descr, mp.ends.descr: one position in some hundred -- the same rounds saved)
 				for( int wi = utid; wi < vec_words; wi += UNIT )
@@ -1785,7 +1790,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			unsigned	pk_m = 0;
 			int	pk_q0 = 0, pk_lo = 0;
 			if constexpr( !LEAN ){
-			if( pk0 && lit && sv_on && !( dbg & 33554432 ) ){
+			if( pk0 && lit && sv_on && !( dbg & RMK_DBG_NO_START_VEC ) ){
 				unsigned long long	*const sv = occ + size_t( n_vec - 6 ) * pb_words;
 				const unsigned long long	*const lv = occ + size_t( n_vec - 5 ) * pb_words;
 				const bool	pre = e0.re >= 0 && e0.mismatch == 0;
@@ -1966,7 +1971,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		}else{
 		bool	by_words = false;
 		if constexpr( LEAN ){
-		if( lit && ( G > 1 || sv_on ) && !quick && !split_ranks && !( dbg & 33554432 ) ){
+		if( lit && ( G > 1 || sv_on ) && !quick && !split_ranks && !( dbg & RMK_DBG_NO_START_VEC ) ){
 			// whole start positions are queued, and only those with the best literal within reach (ire.descr: one in
 			// 170): taken from the words of that vector, as above, not position by position
 			by_words = true;
@@ -2055,15 +2060,15 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			// more items than queue and spill area hold: none is searched twice or dropped silently --
 			// the host repeats the launch with an area of the size asked for here
 			if( tid == 0 && s_qn > qtotal )
-				atomicMax( hb.ticket + 2, ( unsigned long long )s_qn );
+				atomicMax( rmk_ctr<RMK_C_QUEUE_NEED>( hb ), ( unsigned long long )s_qn );
 		}
 		if constexpr( !WALK ){
 			if( tid == 0 && s_qn > qtotal )
-				atomicMax( hb.ticket + ( RMK_GCTL + 1 ), ( unsigned long long )s_qn );
+				atomicMax( rmk_ctr<RMK_C_FLUSH_QUEUE_NEED>( hb ), ( unsigned long long )s_qn );
 		}
-		const int	nq = ( dbg & 1 ) ? 0 : ( s_qn < qtotal ? s_qn : qtotal );
-		if( ( dbg & 2 ) && tid == 0 )
-			atomicAdd( hb.ticket + 1, ( unsigned long long )s_qn );
+		const int	nq = ( dbg & RMK_DBG_NO_PASS_B ) ? 0 : ( s_qn < qtotal ? s_qn : qtotal );
+		if( ( dbg & RMK_DBG_COUNT_QUEUED ) && tid == 0 )
+			atomicAdd( rmk_ctr<RMK_C_QUEUED>( hb ), ( unsigned long long )s_qn );
 		int	k = -1;
 		bool	dry = false;
 		if constexpr( POOL ){
@@ -2074,7 +2079,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			{
 				TailAccel	ac{ P, pb, tile, pb_words, p_lo, vec_words * 64, 0 };
 				// (the chain's cores are where it left them unless the pre-filter had to search in place)
-				const bool	head_next = chain_vecs && bitpar && P->chain.hn_on && !( dbg & ( 32768 | 262144 ) ) && !last && s_inplace == 0;
+				const bool	head_next = chain_vecs && bitpar && P->chain.hn_on && !( dbg & ( RMK_DBG_NO_CHAIN | RMK_DBG_NO_HEAD_NEXT ) ) && !last && s_inplace == 0;
 				for( int c = 0; c < nq; c += BLOCK ){
 					const int	i = c + tid;
 					unsigned	item = 0, hm[ 2 ] = { ~0u, ~0u };	// (the 3' ends left to the first helix of the interior, per outer length)
@@ -2121,7 +2126,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 											ok = true;
 										else{
 											unsigned long long	Wd = rows_win( pb, pb_words, tile, p_lo, H.minlen, lim, ( H.ends & RMA_5PAIRED ) != 0, s5, w0, bot );
-											if( !( dbg & 134217728 ) ){
+											if( !( dbg & RMK_DBG_HEAD_ALL_ENDS ) ){
 												// ... of which the walk takes only those that leave the groups behind the helix their room and let
 												// them reach the interior's end (rmd_lean_open, rmd_lean_step: rem_min, rem_max): bit i = end w0 + i
 												const int	e_hi = rmd_imin( top, b - H.rem_min ) - w0, e_lo = ( H.rem_max >= 0 ? rmd_imax( bot, b - H.rem_max ) : bot ) - w0;
@@ -2173,7 +2178,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					if constexpr( !WALK ){
 						// straight to the drain kernel's list, piece by piece (pool_sub_count): the wave's items side by side
 						const unsigned	rc = unsigned( p_r ) | ( unsigned( sink.comp ) << 16 );
-						const bool	cut = !( dbg & 2097152 );		// (diagnostic: items go whole)
+						const bool	cut = !( dbg & RMK_DBG_WHOLE_ITEMS );		// (diagnostic: items go whole)
 						const int	n_p = !keep ? 0 : !cut ? 1 : pool_sub_count( rc, hm[ 0 ], hm[ 1 ] );
 						int	incl = n_p;
 						for( int o = 1; o < 64; o <<= 1 ){
@@ -2185,7 +2190,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 						if( tot > 0 ){
 							unsigned long long	g0 = 0;
 							if( lane_id == 0 )
-								g0 = atomicAdd( hb.ticket + ( RMK_GCTL - 1 ), ( unsigned long long )tot );
+								g0 = atomicAdd( rmk_ctr<RMK_C_LIST_RESERVED>( hb ), ( unsigned long long )tot );
 							g0 = __shfl( g0, 0 );
 							// (a full list: what has room is written -- every place below the list's end has one owner --, the
 							// host sees more reserved than there is and repeats the scan with a list that holds it)
@@ -2230,9 +2235,9 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			// items, as ire.descr and mp.ends.descr leave them -- some hundred per workgroup, a step or two each --
 			// are walked best where they are, 256 lanes on them while other workgroups still filter: 0.05 ms against
 			// 0.28 in the drain kernel.  trna.descr leaves some twenty per workgroup, walks of dozens of steps.)
-			if( hb.glist_cap > 0 && s_glist_full == 0 && s_pool_n > 0 && last && ( s_pool_n < GLIST_BELOW || ( dbg & 8388608 ) ) && !( dbg & 2048 ) ){
+			if( hb.glist_cap > 0 && s_glist_full == 0 && s_pool_n > 0 && last && ( s_pool_n < GLIST_BELOW || ( dbg & RMK_DBG_LIST_ALL ) ) && !( dbg & RMK_DBG_POOL_DROP ) ){
 				const int	n_fl = s_pool_n;
-				const bool	cut = !( dbg & 2097152 );		// (diagnostic: items go whole)
+				const bool	cut = !( dbg & RMK_DBG_WHOLE_ITEMS );		// (diagnostic: items go whole)
 				// how many list items the pool's make (pool_sub_count) ...
 				int	mine = 0;
 				for( int i = tid; i < n_fl; i += BLOCK ){
@@ -2245,7 +2250,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				__syncthreads();
 				// ... their place in the list, all or none ...
 				if( tid == 0 )
-					s_gstart = ( long long )atomicAdd( hb.ticket + ( RMK_GCTL - 1 ), ( unsigned long long )s_fl_total );
+					s_gstart = ( long long )atomicAdd( rmk_ctr<RMK_C_LIST_RESERVED>( hb ), ( unsigned long long )s_fl_total );
 				__syncthreads();
 				const long long	g0 = s_gstart;
 				const int	n_list = s_fl_total;
@@ -2289,7 +2294,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				__syncthreads();
 			}
 			const int	n_pool = s_pool_n;
-			if( n_pool > 0 && ( last || n_pool >= hb.pool_min ) && ( dbg & 2048 ) ){
+			if( n_pool > 0 && ( last || n_pool >= hb.pool_min ) && ( dbg & RMK_DBG_POOL_DROP ) ){
 				// (diagnostic: the pool is filled and thrown away)
 				__syncthreads();
 				if( tid == 0 )
@@ -2308,10 +2313,10 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					// idle lanes pop together: a window costs some hundred instructions to rebuild, and
 					// a round for one lane costs the wave as much as a round for sixteen
 					if( want && ( busy == 0 || __popcll( want ) >= hb.pool_refill ) ){
-						const unsigned long long	t_p0 = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
-						if( ( dbg & 32 ) && lane_id == 0 ){
-							atomicAdd( hb.ticket + 15, 1ull );
-							atomicAdd( hb.ticket + 16, ( unsigned long long )__popcll( want ) );
+						const unsigned long long	t_p0 = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
+						if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 ){
+							atomicAdd( rmk_ctr<RMK_C_POP_ROUNDS>( hb ), 1ull );
+							atomicAdd( rmk_ctr<RMK_C_POP_LANES>( hb ), ( unsigned long long )__popcll( want ) );
 						}
 						int	base = 0;
 						if( lane_id == __ffsll( want ) - 1 )
@@ -2325,20 +2330,20 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 							}else
 								dry = true;
 						}
-						if( ( dbg & 32 ) && lane_id == 0 )
-							atomicAdd( hb.ticket + 19, __builtin_amdgcn_s_memtime() - t_p0 );
+						if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 )
+							atomicAdd( rmk_ctr<RMK_C_POP_CYCLES>( hb ), __builtin_amdgcn_s_memtime() - t_p0 );
 						continue;
 					}
 					if( busy == 0 )
 						break;
-					const unsigned long long	t_s0 = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
-					if( ( dbg & 32 ) && lane_id == 0 ){
-						atomicAdd( hb.ticket + 17, 1ull );
-						atomicAdd( hb.ticket + 18, ( unsigned long long )__popcll( busy ) );
+					const unsigned long long	t_s0 = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
+					if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 ){
+						atomicAdd( rmk_ctr<RMK_C_STEPS>( hb ), 1ull );
+						atomicAdd( rmk_ctr<RMK_C_STEP_LANES>( hb ), ( unsigned long long )__popcll( busy ) );
 					}
 					// (diagnostic: the deepest level any lane of the wave steps at)
 					int	k_in_ = 0;
-					if( dbg & 32 ){
+					if( dbg & RMK_DBG_CYCLES ){
 						k_in_ = k;
 						for( int o = 32; o > 0; o >>= 1 )
 							k_in_ = rmd_imax( k_in_, __shfl_xor( k_in_, o ) );
@@ -2346,24 +2351,24 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					if( k >= 0 )
 						k = rmd_lean_step<LdsRecs<BLOCK>, DevSink, rmd_nibseq_t<BLOCK>, rmd_no_accel_t, true>( P, lr, st, nsq, k, &lane, sink, none );
 					// complete matches, one at a time, the whole wave on each
-					const unsigned long long	t_e0 = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
-					const int	n_em_ = ( dbg & 32 ) ? __popcll( __ballot( k >= 0 && st.pending ) ) : 0;
+					const unsigned long long	t_e0 = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
+					const int	n_em_ = ( dbg & RMK_DBG_CYCLES ) ? __popcll( __ballot( k >= 0 && st.pending ) ) : 0;
 					wave_emit_pending<BLOCK>( P, lr, st, k, [ & ]( int l ){
 						return rmd_nibseq_t<BLOCK>{ nsq.w + ( l - lane_id ), __shfl( nsq.flip, l ), __shfl( nsq.bias, l ) }; },
 						sink.seq, sink.comp, hb, lane_id );
-					if( ( dbg & 32 ) && lane_id == 0 && n_em_ ){
-						atomicAdd( hb.ticket + 92, __builtin_amdgcn_s_memtime() - t_e0 );
-						atomicAdd( hb.ticket + 93, ( unsigned long long )n_em_ );
+					if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 && n_em_ ){
+						atomicAdd( rmk_ctr<RMK_C_EMIT_CYCLES>( hb ), __builtin_amdgcn_s_memtime() - t_e0 );
+						atomicAdd( rmk_ctr<RMK_C_EMITTED>( hb ), ( unsigned long long )n_em_ );
 					}
-					if( ( dbg & 32 ) && lane_id == 0 ){
+					if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 ){
 						const unsigned long long	dt_ = __builtin_amdgcn_s_memtime() - t_s0;
-						atomicAdd( hb.ticket + 20, dt_ );
-						atomicMax( hb.ticket + 21, dt_ );		// the longest single step
-						atomicAdd( hb.ticket + 23 + ( 63 - __clzll( dt_ | 1ull ) ), 1ull );
-						atomicAdd( hb.ticket + 60 + rmd_imin( rmd_imax( k_in_, 0 ), 15 ), dt_ );
-						atomicAdd( hb.ticket + 76 + rmd_imin( rmd_imax( k_in_, 0 ), 15 ), 1ull );
+						atomicAdd( rmk_ctr<RMK_C_STEP_CYCLES>( hb ), dt_ );
+						atomicMax( rmk_ctr<RMK_C_STEP_LONGEST>( hb ), dt_ );		// the longest single step
+						atomicAdd( rmk_ctr<RMK_C_STEP_LOG2>( hb ) + ( 63 - __clzll( dt_ | 1ull ) ), 1ull );
+						atomicAdd( rmk_ctr<RMK_C_LEVEL_CYCLES>( hb ) + rmd_imin( rmd_imax( k_in_, 0 ), 15 ), dt_ );
+						atomicAdd( rmk_ctr<RMK_C_LEVEL_STEPS>( hb ) + rmd_imin( rmd_imax( k_in_, 0 ), 15 ), 1ull );
 						t_wave += dt_;
-						atomicMax( hb.ticket + 22, t_wave );	// the most any wave spent stepping
+						atomicMax( rmk_ctr<RMK_C_WAVE_MOST>( hb ), t_wave );	// the most any wave spent stepping
 					}
 				}
 				__syncthreads();
@@ -2374,9 +2379,9 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			}
 			if( last ){
 				PHASE( 4 );
-				if( ( dbg & 1048576 ) && tid == 0 && had_tiles ){
-					atomicMax( hb.ticket + 90, ( unsigned long long )wall_clock64() );
-					atomicAdd( hb.ticket + 91, ( unsigned long long )wall_clock64() );
+				if( ( dbg & RMK_DBG_TIMELINE ) && tid == 0 && had_tiles ){
+					atomicMax( rmk_ctr<RMK_C_TL_DONE_MAX>( hb ), ( unsigned long long )wall_clock64() );
+					atomicAdd( rmk_ctr<RMK_C_TL_DONE_SUM>( hb ), ( unsigned long long )wall_clock64() );
 				}
 				break;
 			}
@@ -2390,11 +2395,11 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			TailAccel	accel{ P, pb, tile, pb_words, p_lo, vec_words * 64, tail_from_rows ? 0 : -1 };
 			for( ; ; ){
 				// lanes without work pop until they hold an item that survives the tail test
-				unsigned long long	t_b0 = ( dbg & 32 ) ? __builtin_amdgcn_s_memtime() : 0;
+				unsigned long long	t_b0 = ( dbg & RMK_DBG_CYCLES ) ? __builtin_amdgcn_s_memtime() : 0;
 				for( unsigned long long want; ( want = __ballot( k < 0 && !dry ) ) != 0; ){
-					if( ( dbg & 32 ) && lane_id == 0 ){
-						atomicAdd( hb.ticket + 15, 1ull );
-						atomicAdd( hb.ticket + 16, ( unsigned long long )__popcll( want ) );
+					if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 ){
+						atomicAdd( rmk_ctr<RMK_C_POP_ROUNDS>( hb ), 1ull );
+						atomicAdd( rmk_ctr<RMK_C_POP_LANES>( hb ), ( unsigned long long )__popcll( want ) );
 					}
 					int	base = 0;
 					if( lane_id == __ffsll( want ) - 1 )
@@ -2450,12 +2455,12 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				}
 				const unsigned long long	busy = __ballot( k >= 0 );
 				unsigned long long	t_b1 = 0;
-				if( dbg & 32 ){
+				if( dbg & RMK_DBG_CYCLES ){
 					t_b1 = __builtin_amdgcn_s_memtime();
 					if( lane_id == 0 ){
-						atomicAdd( hb.ticket + 19, t_b1 - t_b0 );
-						atomicAdd( hb.ticket + 17, 1ull );
-						atomicAdd( hb.ticket + 18, ( unsigned long long )__popcll( busy ) );
+						atomicAdd( rmk_ctr<RMK_C_POP_CYCLES>( hb ), t_b1 - t_b0 );
+						atomicAdd( rmk_ctr<RMK_C_STEPS>( hb ), 1ull );
+						atomicAdd( rmk_ctr<RMK_C_STEP_LANES>( hb ), ( unsigned long long )__popcll( busy ) );
 					}
 				}
 				if( busy == 0 )
@@ -2465,8 +2470,8 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				wave_emit_pending<BLOCK>( P, lr, st, k, [ & ]( int l ){
 					return rmd_seq_t{ tile0 + __shfl( int( sq.sq - tile0 ), l ), __shfl( sq.sq0, l ) }; },
 					sink.seq, sink.comp, hb, lane_id );
-				if( ( dbg & 32 ) && lane_id == 0 )
-					atomicAdd( hb.ticket + 20, __builtin_amdgcn_s_memtime() - t_b1 );
+				if( ( dbg & RMK_DBG_CYCLES ) && lane_id == 0 )
+					atomicAdd( rmk_ctr<RMK_C_STEP_CYCLES>( hb ), __builtin_amdgcn_s_memtime() - t_b1 );
 			}
 		}else{
 			GenTile	gt{ P, lean_lo, g_before, g_deep, queue, spill, qcap, nq, &s_qhead, &s_dqn, &s_dqhead,

@@ -31,6 +31,7 @@
 #define RMD_FN_MEMBER	inline
 #include "rm_kernels.h"
 #include "rm_launch_plan.h"
+#include "rm_scan_report.h"
 #include "rm_efn_core.h"
 #include "rm_efndata.h"
 #include "rm_fasta.h"
@@ -166,7 +167,7 @@ struct rma_scanner {
 	bool	have_efn = false;
 	int32_t	*d_hits = nullptr;
 	int64_t	hit_cap = 0;
-	unsigned long long	*d_counters = nullptr;	// [0] count, [1] ticket
+	unsigned long long	*d_counters = nullptr;	// [RMK_N_COUNTERS], rm_diag.h: RMK_C_*
 	unsigned	*d_spill = nullptr;		// [grid_blocks][spill_cap] queue overflow of every workgroup
 	int	spill_cap = 0;
 	bool	whole_items = false;		// ... which takes the items whole, not in pieces (see search_finish)
@@ -179,7 +180,7 @@ struct rma_scanner {
 	std::vector<int32_t>	h_sorted;
 	std::vector<rma::HitKey>	keys, keys_tmp;
 	rma::DevHitSort	dsort;		// ordering on the device (rm_hitsort_dev.h)
-	unsigned long long	*h_ctr = nullptr;	// pinned: the counters a launch leaves
+	unsigned long long	*h_ctr = nullptr;	// pinned: the first RMK_C_COPIED counters as a launch leaves them
 	int	grid_blocks = 0;		// most workgroups of a launch of a lean instance (eight of four waves per CU)
 	int	spill_blocks = 0;		// workgroups d_spill has areas for
 	// the scan between rma_scan_begin() and rma_scan_end()
@@ -335,7 +336,7 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 	// size (count-then-emit, rma_scan_end)
 	sc->hit_cap = 1 << 17;
 	HIPCHK( hipMalloc( &sc->d_hits, size_t( sc->hit_cap ) * sc->dprog.hit_stride * sizeof( int32_t ) ) );
-	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_ctr ), ( RMK_GCTL + 3 ) * sizeof( unsigned long long ), hipHostMallocDefault ) );
+	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_ctr ), RMK_C_COPIED * sizeof( unsigned long long ), hipHostMallocDefault ) );
 	// page-locked room for the records of a usual batch (16 K of them) now, not in the first scan
 	sc->h_raw_cap = size_t( 16384 ) * sc->dprog.hit_stride;
 	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_raw ), sc->h_raw_cap * sizeof( int32_t ), hipHostMallocDefault ) );
@@ -1257,10 +1258,10 @@ static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
 	a.qcap = f.lay->qcap;
 	a.db = view_of( f.db, f.lay );
 	const bool	listed = f.plan.listed, drain = listed && sc->glist_cap > 0;
-	a.hb = HitBuf{ sc->d_hits, sc->d_counters, sc->d_counters + 1, sc->hit_cap, sc->d_spill, sc->spill_cap, sc->d_pool, sc->pool_cap,
+	a.hb = HitBuf{ sc->d_hits, sc->d_counters + RMK_C_COUNT, sc->d_counters + RMK_C_TICKET, sc->hit_cap, sc->d_spill, sc->spill_cap, sc->d_pool, sc->pool_cap,
 		sc->opt.pool_min, sc->opt.pool_refill, listed ? sc->glist_cap : 0 };
 	a.tile_bytes = f.plan.tile_bytes;
-	a.dbg = sc->opt.dbg | ( sc->whole_items ? 2097152 : 0 );
+	a.dbg = sc->opt.dbg | ( sc->whole_items ? RMK_DBG_WHOLE_ITEMS : 0 );
 	HIPCHK( hipEventRecord( sc->ev[ 0 ], sc->stream ) );
 	HIPCHK( rmk_launch_search( f.plan.inst, f.plan.grid, f.plan.lds, sc->stream, a ) );
 	sc->drained = drain;
@@ -1272,95 +1273,19 @@ static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
 		HIPCHK( rmk_launch_lean_drain( f.plan.drain_grid, f.plan.drain_lds, sc->stream, a ) );
 	}
 	HIPCHK( hipEventRecord( sc->ev[ 1 ], sc->stream ) );
-	// [0] candidates, [3] queue overflow of the general instance, [RMK_GCTL] items reserved in the drain kernel's list,
-	// [RMK_GCTL + 2] queue overflow of the lean instance that walks nothing: one copy, one wait
-	HIPCHK( hipMemcpyAsync( sc->h_ctr, sc->d_counters, ( RMK_GCTL + 3 ) * sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream ) );
+	// RMK_C_COUNT, RMK_C_QUEUE_NEED / RMK_C_PIECE_OVERFLOW, RMK_C_LIST_RESERVED, RMK_C_FLUSH_QUEUE_NEED: one copy, one wait
+	HIPCHK( hipMemcpyAsync( sc->h_ctr, sc->d_counters, RMK_C_COPIED * sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream ) );
 	return 0;
 }
 
-static void debug_report( rma_scanner_t *sc, unsigned long long count )
+// The [dbg] lines of the launch that has just ended (rm_scan_report.cpp), from a copy of the whole counter block.
+static void debug_report( rma_scanner_t *sc )
 {
 	const rma_scanner::InFlight	&f = sc->fly;
-	const rmd_program_t	&dp = sc->dprog;
-	const int	dbg = sc->opt.dbg;
-	unsigned long long	q = 0;
-	( void )hipMemcpy( &q, sc->d_counters + 2, sizeof( q ), hipMemcpyDeviceToHost );
-	fprintf( stderr, "[dbg] queued items: %llu, candidates %llu (tile %d x %d, queue %d, LDS %zu, %lld tiles)\n", q, count,
-		f.lay->tile_t, f.plan.grouped ? f.lay->group : 1, f.lay->qcap, f.plan.lds, ( long long )f.lay->n_tiles );
-	if( ( dbg & 1048576 ) && f.plan.lean ){
-		unsigned long long	tl[ 5 ];
-		( void )hipMemcpy( tl, sc->d_counters + 1 + 87, sizeof( tl ), hipMemcpyDeviceToHost );
-		const double	t0 = double( ~tl[ 1 ] ), g = double( tl[ 0 ] );
-		fprintf( stderr, "[dbg] workgroups that had tiles (%.0f of %d): out of tiles after %.1f us (mean), done after %.1f us (mean), %.1f us (last)\n", g, f.plan.grid,
-			( double( tl[ 2 ] ) / g - t0 ) * 0.01, ( double( tl[ 4 ] ) / g - t0 ) * 0.01, ( double( tl[ 3 ] ) - t0 ) * 0.01 );
-	}
-	if( ( dbg & 536870912 ) && sc->drained ){
-		unsigned long long	bins[ 32 ];
-		( void )hipMemcpy( bins, sc->d_counters + 1 + 23, sizeof( bins ), hipMemcpyDeviceToHost );
-		fprintf( stderr, "[dbg] drain: waves through by 16 us from the first wave's start:" );
-		for( int b = 0; b < 32; b++ )
-			if( bins[ b ] )
-				fprintf( stderr, " %d:%llu", b, bins[ b ] );
-		fprintf( stderr, "\n" );
-	}
-	if( dbg & 32 ){
-		unsigned long long	ph[ 6 ];
-		( void )hipMemcpy( ph, sc->d_counters + 4, sizeof( ph ), hipMemcpyDeviceToHost );
-		double	tot = 0;
-		for( int i = 0; i < 6; i++ )
-			tot += double( ph[ i ] );
-		unsigned long long	lv[ 80 ];
-		( void )hipMemcpy( lv, sc->d_counters + 16, sizeof( lv ), hipMemcpyDeviceToHost );
-		const bool	lean = f.plan.lean, drained = f.plan.listed && sc->glist_cap > 0;
-		if( lean && !drained )
-			fprintf( stderr, "[dbg] pool sessions: %.3g wave cycles popping (%.0f per round), %.3g stepping (%.0f per step)\n",
-				double( lv[ 4 ] ), lv[ 0 ] ? double( lv[ 4 ] ) / lv[ 0 ] : 0.0, double( lv[ 5 ] ), lv[ 2 ] ? double( lv[ 5 ] ) / lv[ 2 ] : 0.0 ),
-			fprintf( stderr, "[dbg] longest step %.3g cycles, most stepping in one wave (one session) %.3g cycles\n", double( lv[ 6 ] ), double( lv[ 7 ] ) );
-		if( drained ){
-			// (the drain kernel's items)
-			unsigned long long	g[ 2 ];
-			( void )hipMemcpy( g, sc->d_counters + RMK_GCTL, sizeof( g ), hipMemcpyDeviceToHost );
-			fprintf( stderr, "[dbg] drain: %llu items in the list (%llu taken), %llu walked: %.0f cycles and %.1f steps each; longest %.3g cycles, most steps %llu\n",
-				g[ 0 ], g[ 1 ], lv[ 2 ], lv[ 2 ] ? double( lv[ 5 ] ) / lv[ 2 ] : 0.0, lv[ 2 ] ? double( lv[ 3 ] ) / lv[ 2 ] : 0.0, double( lv[ 6 ] ), lv[ 7 ] );
-			{
-				unsigned long long	lap[ 6 ];
-				( void )hipMemcpy( lap, sc->d_counters + 1 + 93, sizeof( lap ), hipMemcpyDeviceToHost );
-				const double	all = double( lap[ 1 ] + lap[ 2 ] + lap[ 3 ] + lap[ 4 ] ) + 1;
-				fprintf( stderr, "[dbg] drain: %llu wave rounds of %.1f lanes; wave cycles taking items %.1f%%, stepping %.1f%%, complete matches %.1f%%, hand-overs %.1f%%; %.0f cycles a round\n",
-					lap[ 5 ], lap[ 5 ] ? double( lap[ 0 ] ) / lap[ 5 ] : 0.0, 100 * lap[ 1 ] / all, 100 * lap[ 2 ] / all, 100 * lap[ 3 ] / all, 100 * lap[ 4 ] / all,
-					lap[ 5 ] ? all / lap[ 5 ] : 0.0 );
-			}
-			fprintf( stderr, "[dbg] drain: items by log2( cycles ):" );
-			for( int b = 8; b < 32; b++ )
-				if( lv[ 8 + b ] )
-					fprintf( stderr, " %d:%llu", b, lv[ 8 + b ] );
-			fprintf( stderr, "\n[dbg] drain: items by complete matches (0, 1, 2-3, 4-7, ...: count, mean cycles):" );
-			for( int kk = 0; kk < 16; kk++ )
-				if( lv[ 45 + kk ] )
-					fprintf( stderr, " %llu,%.0f", lv[ 45 + kk ], double( lv[ 61 + kk ] ) / lv[ 45 + kk ] );
-			fprintf( stderr, "\n" );
-		}else if( lean ){
-			fprintf( stderr, "[dbg] steps by log2( cycles ):" );
-			for( int b = 8; b < 32; b++ )
-				if( lv[ 8 + b ] )
-					fprintf( stderr, " %d:%llu", b, lv[ 8 + b ] );
-			fprintf( stderr, "\n[dbg] complete matches: %llu, %.0f cycles each", lv[ 78 ], lv[ 78 ] ? double( lv[ 77 ] ) / lv[ 78 ] : 0.0 );
-			fprintf( stderr, "\n[dbg] steps by deepest level (count, mean cycles):" );
-			for( int kk = 0; kk < 16; kk++ )
-				if( lv[ 61 + kk ] )
-					fprintf( stderr, " %d:%llu,%.0f", kk, lv[ 61 + kk ], double( lv[ 45 + kk ] ) / lv[ 61 + kk ] );
-			fprintf( stderr, "\n" );
-		}
-		if( lean && !drained )
-			fprintf( stderr, "[dbg] pass B: %llu pop rounds of %.1f lanes, %llu steps of %.1f lanes; wave cycles popping %.1f%%, stepping %.1f%%\n",
-				lv[ 0 ], lv[ 0 ] ? double( lv[ 1 ] ) / lv[ 0 ] : 0.0, lv[ 2 ], lv[ 2 ] ? double( lv[ 3 ] ) / lv[ 2 ] : 0.0,
-				100.0 * lv[ 4 ] / double( lv[ 4 ] + lv[ 5 ] + 1 ), 100.0 * lv[ 5 ] / double( lv[ 4 ] + lv[ 5 ] + 1 ) );
-		for( int kk = 0; kk < dp.n_searches && kk < 32 && !lean; kk++ )
-			fprintf( stderr, "[dbg] level %2d (element %2d, type %d): %llu wave rounds, %.1f lanes each\n", kk, dp.searches[ kk ],
-				dp.elems[ dp.searches[ kk ] ].type, lv[ 2 * kk ], lv[ 2 * kk ] ? double( lv[ 2 * kk + 1 ] ) / lv[ 2 * kk ] : 0.0 );
-		fprintf( stderr, "[dbg] wave cycles: decode %.1f%%, literal %.1f%%, rows %.1f%%, pre-filter %.1f%%, search %.1f%%, waiting %.1f%%\n",
-			100 * ph[ 0 ] / tot, 100 * ph[ 1 ] / tot, 100 * ph[ 2 ] / tot, 100 * ph[ 3 ] / tot, 100 * ph[ 4 ] / tot, 100 * ph[ 5 ] / tot );
-	}
+	unsigned long long	ctr[ RMK_N_COUNTERS ] = { 0 };
+	( void )hipMemcpy( ctr, sc->d_counters, sizeof( ctr ), hipMemcpyDeviceToHost );
+	rma::debug_report( ctr, rma::ScanShape{ sc->opt.dbg, f.lay->tile_t, f.plan.grouped ? f.lay->group : 1, f.lay->qcap, f.plan.grid, f.plan.lds,
+		( long long )f.lay->n_tiles, f.plan.lean, sc->drained }, sc->dprog );
 }
 
 // The search kernel of a scan is on its way when this returns; rma_scan_end() (or search_finish())
@@ -1443,13 +1368,13 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 	unsigned long long	count = 0;
 	for( int attempt = 0; ; attempt++ ){
 		HIPCHK( hipStreamSynchronize( sc->stream ) );
-		count = sc->h_ctr[ 0 ];
+		count = sc->h_ctr[ RMK_C_COUNT ];
 		if( sc->opt.dbg )
-			debug_report( sc, count );
+			debug_report( sc );
 		bool	again = false;
 		if( !f.plan.lean ){
 			// the general instance does not search queue overflow in place: a larger spill area, and again
-			const unsigned long long	need = sc->h_ctr[ 3 ];
+			const unsigned long long	need = sc->h_ctr[ RMK_C_QUEUE_NEED ];
 			if( need > 0 ){
 				if( attempt == 3 ){
 					snprintf( err, errlen, "work queue overflow after regrow (%llu items in a tile)", need );
@@ -1463,7 +1388,7 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 		if( f.plan.walks_nothing ){
 			// the instance that walks nothing reports what it had no room for -- a tile's items beyond queue and spill area, the
 			// list's items beyond its end -- and the scan is repeated with room for them
-			const unsigned long long	q_need = sc->h_ctr[ RMK_GCTL + 2 ], l_need = sc->h_ctr[ RMK_GCTL ];
+			const unsigned long long	q_need = sc->h_ctr[ RMK_C_FLUSH_QUEUE_NEED ], l_need = sc->h_ctr[ RMK_C_LIST_RESERVED ];
 			if( ( q_need > 0 || l_need > ( unsigned long long )sc->glist_cap ) && attempt == 3 ){
 				snprintf( err, errlen, "work queue or item list overflow after regrow (%llu items in a tile, %llu in the list)", q_need, l_need );
 				return 1;
@@ -1484,7 +1409,7 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 				again = true;
 			}
 		}
-		if( f.plan.lean && sc->h_ctr[ 3 ] != 0 && !sc->whole_items ){
+		if( f.plan.lean && sc->h_ctr[ RMK_C_PIECE_OVERFLOW ] != 0 && !sc->whole_items ){
 			// a piece of an item found more candidates than the order words of the pieces leave room for
 			// (PIECE_ORDER_BITS): once more, and from now on, with whole items
 			sc->whole_items = true;

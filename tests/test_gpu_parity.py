@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import pins
+from rnamotif_amd import DBG
 from large_db import sorted_unique as _sorted_unique
 
 pytestmark = pytest.mark.gpu
@@ -170,11 +171,11 @@ def test_synthetic_records_equal_oracle(built, workdir, name):
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("dbg", [4, 8, 16, 28])
+@pytest.mark.parametrize("dbg", [DBG["NO_BITPAR"], DBG["NO_LITERAL"], DBG["GENERAL"], DBG["NO_BITPAR"] | DBG["NO_LITERAL"] | DBG["GENERAL"]])
 @pytest.mark.parametrize("name", ["trna.descr", "pk1.descr", "qu+tr.descr"])
 def test_search_paths_agree(built, workdir, name, dbg):
-    """The kernel's optional stages (4: bit-parallel pre-filter off, 8: literal
-    filter off, 16: LDS-record search off -> general state machine) are output
+    """The kernel's optional stages (4, NO_BITPAR: bit-parallel pre-filter off, 8, NO_LITERAL: literal
+    filter off, 16, GENERAL: LDS-record search off -> general state machine) are output
     neutral: every combination gives the oracle's records."""
     import rnamotif_amd as R
     from oracle_binding import oracle_scan
@@ -207,13 +208,14 @@ def test_pooled_and_tile_by_tile_pass_b_agree(built, workdir, gbrna, name):
     want = oracle_scan(d, seqs)
     sc = R.Scanner(d)
     db = sc.database(seqs)
-    # drain 0: every workgroup walks its own items; dbg 2097152: the drain kernel's items stay whole (no pieces);
-    # 4194304: no subtrees handed to idle lanes; 8388608: everything a workgroup holds at the end goes to the list
+    # drain 0: every workgroup walks its own items; dbg 2097152, WHOLE_ITEMS: the drain kernel's items stay whole (no pieces);
+    # 4194304, NO_FORKS: no subtrees handed to idle lanes; 8388608, LIST_ALL: everything a workgroup holds at the end goes to the list
     # glist: items of the drain kernel's list (7: it overflows at once and the workgroups that find no room walk their own items)
     base = {"pool": -1, "pool_min": 1024, "pool_refill": 48, "drain": 1, "dbg": 0, "glist": 0}
-    for opts in ({}, {"pool": 0}, {"pool_min": 8, "pool_refill": 1}, {"pool_min": 100000}, {"drain": 0}, {"dbg": 2097152},
-                 {"dbg": 4194304}, {"dbg": 8388608}, {"dbg": 8388608 + 4194304 + 2097152}, {"dbg": 8388608, "pool_refill": 1},
-                 {"dbg": 8388608, "glist": 7}, {"glist": 1}, {"dbg": 8388608, "glist": 300}):
+    for opts in ({}, {"pool": 0}, {"pool_min": 8, "pool_refill": 1}, {"pool_min": 100000}, {"drain": 0}, {"dbg": DBG["WHOLE_ITEMS"]},
+                 {"dbg": DBG["NO_FORKS"]}, {"dbg": DBG["LIST_ALL"]}, {"dbg": DBG["WHOLE_ITEMS"] | DBG["NO_FORKS"] | DBG["LIST_ALL"]},
+                 {"dbg": DBG["LIST_ALL"], "pool_refill": 1}, {"dbg": DBG["LIST_ALL"], "glist": 7}, {"glist": 1},
+                 {"dbg": DBG["LIST_ALL"], "glist": 300}):
         for k, v in dict(base, **opts).items():
             sc.set_option(k, v)
         got = sc.scan(db)
@@ -254,7 +256,7 @@ def test_search_kernel_that_walks_nothing(built, workdir, gbrna, name):
             sc = R.Scanner(d)
             db = sc.database(seqs)
             for opts in ({"flush": 1}, {"flush": 0}, {"flush": -1}, {"flush": 1, "glist": 1}, {"flush": 1, "efn_light": 0},
-                         {"flush": 0, "efn_light": 1}, {"flush": 1, "dbg": 2097152}, {"flush": 1, "dbg": 4194304}):
+                         {"flush": 0, "efn_light": 1}, {"flush": 1, "dbg": DBG["WHOLE_ITEMS"]}, {"flush": 1, "dbg": DBG["NO_FORKS"]}):
                 for k, v in dict({"flush": -1, "glist": 0, "efn_light": -1, "dbg": 0}, **opts).items():
                     sc.set_option(k, v)
                 got = sc.scan(db)
@@ -1216,7 +1218,8 @@ def test_random_lean_descriptors_through_the_drain_kernel(built, tmp_path, seed)
     except R.RnamotifError as e:
         pytest.skip("refused by the device build: " + str(e))
     db = sc.database(seqs)
-    for opts in ({"dbg": 8388608}, {"dbg": 8388608 + 2097152}, {"dbg": 8388608 + 4194304}, {"drain": 0, "dbg": 0}):
+    for opts in ({"dbg": DBG["LIST_ALL"]}, {"dbg": DBG["WHOLE_ITEMS"] | DBG["LIST_ALL"]}, {"dbg": DBG["NO_FORKS"] | DBG["LIST_ALL"]},
+                 {"drain": 0, "dbg": 0}):
         for k, v in dict({"drain": 1}, **opts).items():
             sc.set_option(k, v)
         got = sc.scan(db)
@@ -1324,8 +1327,8 @@ def test_leading_4plex_strand_filter(built, tmp_path, variant):
     got = sc.scan(sc.database(seqs))
     assert want.shape[0] > 0 or variant == 1, "the sequence should hold some of these"
     assert got.shape == want.shape and np.array_equal(got, want)
-    # ... and with the filter switched off (dbg bits 8192, 16384: the launch shape stays)
-    for bits in (8192, 16384):
+    # ... and with the filter switched off (dbg bits 8192 NO_Q1_FILTER, 16384 NO_TRI_FILTER: the launch shape stays)
+    for bits in (DBG["NO_Q1_FILTER"], DBG["NO_TRI_FILTER"]):
         sc.set_option("dbg", bits)
         again = sc.scan(sc.database(seqs))
         assert np.array_equal(again, want)

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from rnamotif_amd import DBG
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = os.path.join(ROOT, "rnamotif_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -57,8 +59,8 @@ def databases():
 OPTS = {"base": ({}, {}), "pool0": ({}, {"pool": 0}), "drain0": ({}, {"drain": 0}),
         "flush0": ({}, {"flush": 0}), "flush1": ({}, {"flush": 1}), "flush-1": ({}, {"flush": -1}),
         "short0": ({}, {"short": 0}), "short1": ({}, {"short": 1}), "short2": ({}, {"short": 2}),
-        "dbg16": ({}, {"dbg": 16}), "dbg2048": ({}, {"dbg": 2048}), "dbg8388608": ({}, {"dbg": 8388608}),
-        "dbg2097152": ({}, {"dbg": 2097152}), "glist7": ({}, {"glist": 7}),
+        "dbg16": ({}, {"dbg": DBG["GENERAL"]}), "dbg2048": ({}, {"dbg": DBG["POOL_DROP"]}), "dbg8388608": ({}, {"dbg": DBG["LIST_ALL"]}),
+        "dbg2097152": ({}, {"dbg": DBG["WHOLE_ITEMS"]}), "glist7": ({}, {"glist": 7}),
         "qcap64": ({"RNAMOTIF_QCAP": "64"}, {}), "tile4096": ({"RNAMOTIF_TILE": "4096"}, {}),
         "efn0": ({}, {"efn_light": 0}), "efn1": ({}, {"efn_light": 1})}
 
@@ -79,7 +81,7 @@ def checker():
     srcs += [os.path.join(H, f) for f in ("rm_launch_plan.cpp", "rm_regex.cpp", "rm_compile.cpp", "rm_parse.cpp", "rm_score.cpp",
                                           "rm_efndata.cpp", "rm_efn2data.cpp", "rm_fasta.cpp", "rm_driver.cpp", "rm_cli.cpp",
                                           "rm_dump.cpp", "rm_pack.cpp", "rm_stream.cpp", "rm_dev_program.cpp")]
-    newest = max(os.path.getmtime(s) for s in srcs + [os.path.join(H, f) for f in ("rm_launch_plan.h", "rm_kernels.h", "rm_dev_program.h")])
+    newest = max(os.path.getmtime(s) for s in srcs + [os.path.join(H, f) for f in ("rm_launch_plan.h", "rm_kernels.h", "rm_diag.h", "rm_dev_program.h")])
     if not os.path.exists(BIN) or os.path.getmtime(BIN) < newest:
         # (rm_launch_plan.cpp compiles like rm_scanner.cpp: g++ with the ROCm headers, for rm_kernels.h)
         subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
