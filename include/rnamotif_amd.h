@@ -168,6 +168,30 @@ int	rma_db_create_packed_ranges( rma_scanner_t *sc, const rma_pack_t *pk, const 
 int	rma_db_create_device( rma_scanner_t *sc, const void *text, int64_t text_bytes, const int64_t *start, const int32_t *slen,
 		const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, const uint8_t *table, void *stream,
 		rma_db_t **out, char *err, size_t errlen );
+/* A database of FASTA text in device memory: text_bytes bytes as a file holds them -- '>' lines, line breaks,
+ * digits, blanks.  The entries and their letters are found on the device as the readers find them (FN_fgetseq:
+ * an entry starts at a '>' outside a definition line, its letters are the isalpha() bytes up to the next start)
+ * and written to a clean text the database owns: 1 byte per base of device memory until rma_db_destroy(), which
+ * returns it to the cache.  From there on it is a rma_db_create_device() database of the readers' letters over
+ * that text (rma_replay_device works on it).  maxslen as rma_pack_read (0 = the readers' default).  The work
+ * runs on the device's upload stream behind what is queued on `stream` now.  Unlike rma_db_create_device this
+ * call synchronises -- it learns the number of entries and letters before it can allocate, and the definition
+ * lines before it can return; in return the caller's text is no longer needed once it has returned.  Refused,
+ * with the entry's number, the byte offset of its '>' and the reason, and nothing made: what the parallel reader
+ * hands to the serial reader's diagnostics -- text that does not begin with '>', an unnamed entry, a definition
+ * line of 19999 bytes or more or with a NUL in it (any line of more than 20256 bytes counts as too long), an
+ * entry of more than maxslen letters -- and more than INT32_MAX entries.  Empty text is a database of no entries. */
+int	rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, int64_t text_bytes, int32_t maxslen,
+		void *stream, rma_db_t **out, char *err, size_t errlen );
+/* entry i's name and definition as the readers deliver them (the name cut at 99 bytes); valid until rma_db_destroy.
+ * Non-zero for a database that was not made by rma_db_create_device_fasta, or an entry it does not have. */
+int	rma_db_entry_name( const rma_db_t *db, int32_t i, const char **sid, const char **sdef );
+/* the number of entries of a database */
+int32_t	rma_db_entries( const rma_db_t *db );
+/* how rma_db_create_device_fasta cuts its text (for tests that place bytes at the seams): shape[ 0 ] bytes per
+ * chunk, counted from the aligned dword the text begins in; shape[ 1 ] chunks per block of the scan; shape[ 2 ]
+ * bytes of a definition line that are looked at */
+void	rma_fasta_device_shape( int32_t shape[ 3 ] );
 /* the default table of rma_db_create_device: byte -> code (0-3) or 4, the readers' letters */
 void	rma_letter_codes( uint8_t codes[ 256 ] );
 /* a database's packed words read back (for verification; whichever path made them): codes[ 2 * w ],

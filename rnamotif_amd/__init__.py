@@ -131,6 +131,12 @@ def lib() -> C.CDLL:
     L.rma_replay_close.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.rma_db_create_device.argtypes = [vp, vp, C.c_int64, i64p, i32p, i32p, i32p, C.c_int32, C.c_char_p, vp,
                                        C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.rma_db_create_device_fasta.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.rma_db_entry_name.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
+    L.rma_db_entries.argtypes = [vp]
+    L.rma_db_entries.restype = C.c_int32
+    L.rma_fasta_device_shape.argtypes = [i32p]
+    L.rma_fasta_device_shape.restype = None
     L.rma_letter_codes.argtypes = [C.c_char_p]
     L.rma_letter_codes.restype = None
     L.rma_db_mask_words.argtypes = [vp]
@@ -147,6 +153,13 @@ def lib() -> C.CDLL:
 def _check(rc: int, err) -> None:
     if rc != 0:
         raise RnamotifError(err.value.decode("utf-8", "replace").rstrip())
+
+
+def fasta_device_shape() -> Tuple[int, int, int]:
+    """(bytes per chunk, chunks per scan block, bytes of a definition line looked at) of database_from_fasta_tensor."""
+    a = (C.c_int32 * 3)()
+    lib().rma_fasta_device_shape(a)
+    return int(a[0]), int(a[1]), int(a[2])
 
 
 def _cstr_array(items: Sequence[bytes]):
@@ -437,6 +450,47 @@ class Scanner:
         db.bases = lib().rma_db_bases(h)
         if wait:
             db.wait()
+        return db
+
+    def database_from_fasta_tensor(self, text, maxslen: int = 0) -> Database:
+        """A database of FASTA text already on this scanner's GPU -- the bytes of a file, '>' lines and line breaks
+        included -- cut into entries and packed there (rma_db_create_device_fasta): the entries, names and words
+        Pack.read() + database_from_pack() make of the same file.  text: a 1-D contiguous uint8 / int8 tensor on the
+        scanner's device (a view with a storage offset will do); maxslen as Pack.read().  The call synchronises
+        and the tensor is free once it returns: the database keeps the letters (1 byte per base of HBM until it is
+        closed).  .sids / .sdefs are the entries' names and definitions, ready for
+        Replay.device(db, hits, sids=db.sids, sdefs=db.sdefs).  Text the readers have a diagnostic for is refused
+        (RnamotifError naming the entry)."""
+        import torch
+        if not isinstance(text, torch.Tensor):
+            raise TypeError(f"text is a {type(text).__name__}, not a torch.Tensor")
+        if text.dtype not in (torch.uint8, torch.int8):
+            raise TypeError(f"text is {text.dtype}: the bytes of a FASTA file are uint8 or int8")
+        if text.dim() != 1:
+            raise ValueError(f"text has {text.dim()} dimensions: the bytes of a FASTA file are a 1-D tensor")
+        if not text.is_contiguous():
+            raise ValueError(f"text has stride {text.stride(0)}: a contiguous tensor is needed")
+        if text.device.type != "cuda" or (text.device.index if text.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"text is on {text.device}: the scanner is on cuda:{self.device}")
+        if int(maxslen) < 0:
+            raise ValueError(f"maxslen is {maxslen}")
+        L = lib()
+        stream = torch.cuda.current_stream(text.device).cuda_stream
+        h = C.c_void_p()
+        err = C.create_string_buffer(_ERRLEN)
+        _check(L.rma_db_create_device_fasta(self._h, text.data_ptr() if text.numel() else None, text.numel(), int(maxslen),
+                                            stream, C.byref(h), err, _ERRLEN), err)
+        db = Database.__new__(Database)
+        db.scanner, db._h, db.alphabet = self, h, None
+        db._text = "owned"      # (Replay.device asks for a database with text on the device: this one owns its text)
+        db.n_seqs = int(L.rma_db_entries(h))
+        db.bases = L.rma_db_bases(h)
+        db.sids, db.sdefs = [], []
+        sid, sdef = C.c_char_p(), C.c_char_p()
+        for i in range(db.n_seqs):
+            L.rma_db_entry_name(h, i, C.byref(sid), C.byref(sdef))
+            db.sids.append(sid.value)
+            db.sdefs.append(sdef.value)
         return db
 
     def scan_tensor(self, db: Database):

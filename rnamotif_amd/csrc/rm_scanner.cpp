@@ -40,6 +40,8 @@
 #include "rm_hitsort_dev.h"
 #include "rm_dbpack_dev.h"
 #include "rm_hitwin_dev.h"
+#include "rm_fasta_dev_kernels.h"
+#include "rm_stream.h"
 #include "rnamotif_amd.h"
 
 #define HIPCHK( call )	do{ hipError_t e_ = ( call ); if( e_ != hipSuccess ){ \
@@ -214,6 +216,9 @@ struct rma_db {
 	const int64_t	*d_text_start = nullptr;
 	const uint8_t	*d_table = nullptr;
 	bool	default_table = true;
+	// rma_db_create_device_fasta: the clean text is the database's own, and the entries have names
+	Block	text_blk;
+	std::vector<std::string>	sids, sdefs;
 	int32_t	n_seq = 0, max_slen = 0;
 	int64_t	total_bases = 0, sum_slen = 0;
 	int64_t	padded_bases = 0;	// bases the packed arrays hold, padding between the entries included
@@ -705,6 +710,10 @@ static int stream_after( hipStream_t on, hipStream_t caller, char *err, size_t e
 	return 0;
 }
 
+static int db_from_device_text( rma_scanner_t *sc, const void *text, int64_t text_bytes, int64_t lo, int64_t hi, const int64_t *start,
+	const int32_t *slen, const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, const uint8_t *table, const std::vector<uint8_t> &tab,
+	bool default_table, void *stream, rma_db_t **out, char *err, size_t errlen );
+
 extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_t text_bytes, const int64_t *start, const int32_t *slen,
 	const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, const uint8_t *table, void *stream, rma_db_t **out, char *err, size_t errlen )
 {
@@ -757,6 +766,18 @@ extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_
 			tab.assign( table, table + 256 );
 		}
 	}
+	return db_from_device_text( sc, text, text_bytes, lo, hi, start, slen, pos_lo, pos_hi, n, table_on_device ? table : nullptr, tab,
+		table == nullptr, stream, out, err, errlen );
+}
+
+// rma_db_create_device() after its checks: the entries' words packed from text (bytes [lo, hi) of it hold them) behind
+// the caller's stream, the tiling, the registration for rma_replay_device().  d_table: a table on the device, else tab.
+static int db_from_device_text( rma_scanner_t *sc, const void *text, int64_t text_bytes, int64_t lo, int64_t hi, const int64_t *start,
+	const int32_t *slen, const int32_t *pos_lo, const int32_t *pos_hi, int32_t n, const uint8_t *table, const std::vector<uint8_t> &tab,
+	bool default_table, void *stream, rma_db_t **out, char *err, size_t errlen )
+{
+	const int	device = device_of( sc );
+	const bool	table_on_device = table != nullptr;
 	// the layout PackedDb::add() makes: every entry on a 32-base boundary, one after the other
 	std::vector<int64_t>	base_off( static_cast<size_t>( n ) );
 	int64_t	padded = 0;
@@ -783,7 +804,7 @@ extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_
 	db->text_hi = hi;
 	db->d_text_start = d_start;
 	db->d_table = d_table;
-	db->default_table = table == nullptr;
+	db->default_table = default_table;
 	if( n > 0 )
 		HIPCHK( hipMemcpyAsync( d_start, db->h_text_start.data(), size_t( n ) * 8, hipMemcpyHostToDevice, up ) );
 	if( !table_on_device )
@@ -803,6 +824,173 @@ extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_
 		return 1;
 	std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
 	g_device_dbs.insert( *out );
+	return 0;
+}
+
+// ---------------------------------------------------------------- databases from FASTA text in device memory
+// The entries and their letters are found on the device (rm_fasta_dev.hip): summaries of the chunks, a scan of them,
+// then the letters into a clean text the database owns.  Two synchronisations of the upload stream teach the host
+// what it cannot go on without -- the totals (to allocate), then the entries' offsets and definition lines (to name
+// the entries and to refuse what the readers have a diagnostic for).  From there on the database is
+// db_from_device_text()'s over the clean text.
+extern "C" int rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, int64_t text_bytes, int32_t maxslen, void *stream,
+	rma_db_t **out, char *err, size_t errlen )
+{
+	*out = nullptr;
+	const int	device = device_of( sc );
+	if( text_bytes < 0 || maxslen < 0 || ( text_bytes > 0 && text == nullptr ) ){
+		snprintf( err, errlen, "rma_db_create_device_fasta: %lld bytes of text, maxslen %d: bad arguments", ( long long )text_bytes, maxslen );
+		return 1;
+	}
+	const int64_t	lim = maxslen > 0 ? int64_t( maxslen ) + 1 : 30000000 + 1;	// as rma_pack_read: -N n reads n letters
+	HIPCHK( hipSetDevice( device ) );
+	if( text_bytes > 0 && check_device_bytes( text, device, 0, text_bytes, "the text", err, errlen ) )
+		return 1;
+	DevCtx	*ctx = dev_ctx( device, err, errlen );
+	if( ctx == nullptr )
+		return 1;
+	hipStream_t	up = ctx->upload;
+	const std::vector<uint8_t>	tab( rma::letter_codes(), rma::letter_codes() + 256 );
+	// device blocks of this call: back to the cache on every way out, once the upload stream is done with them; the
+	// clean text goes to the database instead
+	struct Blocks {
+		DevCtx	*ctx;
+		Block	work, entries, headers, clean;
+		bool	idle = false;		// nothing on the upload stream uses them any more
+		~Blocks()
+		{
+			if( !idle )
+				( void )hipStreamSynchronize( ctx->upload );
+			ctx->give( work ); ctx->give( entries ); ctx->give( headers ); ctx->give( clean );
+		}
+	}	b{ ctx, {}, {}, {}, {} };
+	const uint8_t	*t8 = static_cast<const uint8_t *>( text );
+	rma::FdPrefix	totals{ 0, 0, 0, 0 };
+	const rma::FdSummary	*d_local = nullptr;
+	const rma::FdPrefix	*d_block_pre = nullptr, *d_totals = nullptr;
+	if( text_bytes > 0 ){
+		const int64_t	chunks = rma::fasta_chunks( text, text_bytes ), blocks = rma::fasta_blocks( chunks );
+		if( chunks > 0x7fffffffll ){
+			snprintf( err, errlen, "rma_db_create_device_fasta: %lld bytes of text are more than 2^31 chunks", ( long long )text_bytes );
+			return 1;
+		}
+		const size_t	o_sum = 0, o_local = o_sum + align256( size_t( chunks ) * sizeof( rma::FdSummary ) );
+		const size_t	o_bsum = o_local + align256( size_t( chunks ) * sizeof( rma::FdSummary ) );
+		const size_t	o_bpre = o_bsum + align256( size_t( blocks ) * sizeof( rma::FdSummary ) );
+		const size_t	o_tot = o_bpre + align256( size_t( blocks ) * sizeof( rma::FdPrefix ) );
+		HIPCHK( ctx->take( o_tot + 256, &b.work ) );
+		char	*w = static_cast<char *>( b.work.p );
+		d_local = reinterpret_cast<rma::FdSummary *>( w + o_local );
+		d_block_pre = reinterpret_cast<rma::FdPrefix *>( w + o_bpre );
+		d_totals = reinterpret_cast<rma::FdPrefix *>( w + o_tot );
+		// the text as the caller's stream leaves it
+		if( stream_after( up, static_cast<hipStream_t>( stream ), err, errlen ) )
+			return 1;
+		HIPCHK( rma::fasta_index( t8, text_bytes, reinterpret_cast<rma::FdSummary *>( w + o_sum ), reinterpret_cast<rma::FdSummary *>( w + o_local ),
+			reinterpret_cast<rma::FdSummary *>( w + o_bsum ), reinterpret_cast<rma::FdPrefix *>( w + o_bpre ),
+			reinterpret_cast<rma::FdPrefix *>( w + o_tot ), up ) );
+		unsigned char	first_byte = 0;
+		HIPCHK( hipMemcpyAsync( &totals, d_totals, sizeof( totals ), hipMemcpyDeviceToHost, up ) );
+		HIPCHK( hipMemcpyAsync( &first_byte, t8, 1, hipMemcpyDeviceToHost, up ) );
+		HIPCHK( hipStreamSynchronize( up ) );
+		if( first_byte != '>' ){
+			snprintf( err, errlen, "entry 0 at byte 0: the text does not begin with '>'" );
+			return 1;
+		}
+		if( totals.starts > 0x7fffffffll ){
+			snprintf( err, errlen, "the text holds %lld entries: more than a database's %d", ( long long )totals.starts, 0x7fffffff );
+			return 1;
+		}
+	}
+	const int32_t	n = int32_t( totals.starts );
+	const size_t	nn = size_t( n );
+	std::vector<int64_t>	gt_off( nn ), def_end( nn ), first( nn );
+	std::vector<int32_t>	slen( nn );
+	std::vector<std::string>	sids( nn ), sdefs( nn );
+	if( n > 0 ){
+		HIPCHK( ctx->take( size_t( std::max<int64_t>( totals.letters, 1 ) ), &b.clean ) );
+		const size_t	o_end = align256( nn * 8 ), o_first = 2 * o_end;
+		HIPCHK( ctx->take( 3 * o_end, &b.entries ) );
+		char	*e = static_cast<char *>( b.entries.p );
+		int64_t	*d_gt = reinterpret_cast<int64_t *>( e ), *d_end = reinterpret_cast<int64_t *>( e + o_end );
+		int64_t	*d_first = reinterpret_cast<int64_t *>( e + o_first );
+		HIPCHK( rma::fasta_apply( t8, text_bytes, d_local, d_block_pre, d_totals, static_cast<uint8_t *>( b.clean.p ), d_gt, d_end, d_first, up ) );
+		HIPCHK( hipMemcpyAsync( gt_off.data(), d_gt, nn * 8, hipMemcpyDeviceToHost, up ) );
+		HIPCHK( hipMemcpyAsync( def_end.data(), d_end, nn * 8, hipMemcpyDeviceToHost, up ) );
+		HIPCHK( hipMemcpyAsync( first.data(), d_first, nn * 8, hipMemcpyDeviceToHost, up ) );
+		HIPCHK( hipStreamSynchronize( up ) );
+		// the definition lines, one after the other, each capped (a longer one is refused below without its bytes)
+		std::vector<int64_t>	hdr_off( nn + 1 );
+		hdr_off[ 0 ] = 0;
+		for( size_t i = 0; i < nn; i++ ){
+			if( gt_off[ i ] < 0 || def_end[ i ] <= gt_off[ i ] || def_end[ i ] > text_bytes || first[ i ] < 0 || first[ i ] > totals.letters ||
+				( i > 0 && ( gt_off[ i ] <= gt_off[ i - 1 ] || first[ i ] < first[ i - 1 ] ) ) ){
+				snprintf( err, errlen, "entry %zu: the text changed while it was being read", i );
+				return 1;
+			}
+			hdr_off[ i + 1 ] = hdr_off[ i ] + std::min<int64_t>( def_end[ i ] - gt_off[ i ], rma::FD_HEADER_CAP );
+		}
+		HIPCHK( ctx->take( size_t( hdr_off[ nn ] ), &b.headers ) );
+		// (the entries' first letters are on the host by now: their array takes the header offsets)
+		HIPCHK( hipMemcpyAsync( d_first, hdr_off.data(), nn * 8, hipMemcpyHostToDevice, up ) );
+		HIPCHK( rma::fasta_headers( t8, text_bytes, d_gt, d_end, d_first, n, static_cast<uint8_t *>( b.headers.p ), up ) );
+		std::vector<char>	hdr( size_t( hdr_off[ nn ] ) );
+		HIPCHK( hipMemcpyAsync( hdr.data(), b.headers.p, hdr.size(), hipMemcpyDeviceToHost, up ) );
+		HIPCHK( hipStreamSynchronize( up ) );
+		// names and refusals, entry by entry in the text's order: FastaStream::parse's verdicts
+		for( size_t i = 0; i < nn; i++ ){
+			const char	*h = hdr.data() + hdr_off[ i ], *rest = nullptr;
+			const int64_t	line = def_end[ i ] - gt_off[ i ], letters = ( i + 1 < nn ? first[ i + 1 ] : totals.letters ) - first[ i ];
+			int	why = line > rma::FD_HEADER_CAP ? int( rma::DEFLINE_LONG ) :
+				rma::parse_defline( h, h + ( hdr_off[ i + 1 ] - hdr_off[ i ] ), sids[ i ], sdefs[ i ], &rest );
+			const char	*reason = why == rma::DEFLINE_NOT_GT ? "does not begin with '>'" : why == rma::DEFLINE_UNNAMED ? "unnamed entry" :
+				why == rma::DEFLINE_LONG ? "definition line too long (19999 bytes or more)" :
+				why == rma::DEFLINE_NUL ? "NUL in the definition line" : nullptr;
+			if( reason == nullptr && letters >= lim )
+				reason = "sequence too long";
+			if( reason != nullptr ){
+				if( why == rma::DEFLINE_LONG )
+					snprintf( err, errlen, "entry %zu at byte %lld: %s: a line of %lld bytes", i, ( long long )gt_off[ i ], reason, ( long long )line );
+				else if( why == rma::DEFLINE_OK )
+					snprintf( err, errlen, "entry %zu at byte %lld: %s: %lld letters, the limit is %lld", i, ( long long )gt_off[ i ], reason,
+						( long long )letters, ( long long )lim - 1 );
+				else
+					snprintf( err, errlen, "entry %zu at byte %lld: %s", i, ( long long )gt_off[ i ], reason );
+				return 1;
+			}
+			slen[ i ] = int32_t( letters );
+			sids[ i ].resize( strlen( sids[ i ].c_str() ) );	// (as the readers deliver it: a C string)
+		}
+	}
+	if( db_from_device_text( sc, b.clean.p, totals.letters, 0, totals.letters, first.data(), slen.data(), nullptr, nullptr, n, nullptr, tab, true,
+		stream, out, err, errlen ) )
+		return 1;
+	b.idle = true;
+	// (the pack kernel follows the apply kernel on the upload stream; the caller's text is not read again)
+	( *out )->text_blk = b.clean;
+	b.clean = Block{};
+	( *out )->sids = std::move( sids );
+	( *out )->sdefs = std::move( sdefs );
+	return 0;
+}
+
+extern "C" int32_t rma_db_entries( const rma_db_t *db ) { return db->n_seq; }
+
+extern "C" void rma_fasta_device_shape( int32_t shape[ 3 ] )
+{
+	shape[ 0 ] = rma::FD_CHUNK;
+	shape[ 1 ] = rma::FD_SCAN_BLOCK;
+	shape[ 2 ] = rma::FD_HEADER_CAP;
+}
+
+extern "C" int rma_db_entry_name( const rma_db_t *db, int32_t i, const char **sid, const char **sdef )
+{
+	if( db == nullptr || i < 0 || size_t( i ) >= db->sids.size() )
+		return 1;
+	if( sid != nullptr )
+		*sid = db->sids[ size_t( i ) ].c_str();
+	if( sdef != nullptr )
+		*sdef = db->sdefs[ size_t( i ) ].c_str();
 	return 0;
 }
 
@@ -862,6 +1050,7 @@ extern "C" void rma_db_destroy( rma_db_t *db )
 			( void )hipEventSynchronize( l->ready );
 	if( db->ctx != nullptr ){
 		db->ctx->give( db->blk );
+		db->ctx->give( db->text_blk );
 		for( auto &l : db->layouts )
 			db->ctx->give( l->blk );
 	}

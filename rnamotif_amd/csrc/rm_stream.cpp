@@ -31,6 +31,42 @@ inline bool is_space( int c ) { return c == ' ' || ( c >= '\t' && c <= '\r' ); }
 
 }	// namespace
 
+// FN_fgetseq(), dbutil.c:52-102, on an entry's definition line
+int parse_defline( const char *p, const char *end, std::string &sid, std::string &sdef, const char **rest )
+{
+	sid.clear();
+	sdef.clear();
+	*rest = p;
+	if( p == end || *p != '>' )
+		return DEFLINE_NOT_GT;		// "fastn file does not begin with '>'"
+	p++;
+	while( p < end && is_space( ( unsigned char )*p ) && *p != '\n' )	// skipbl2nl
+		p++;
+	if( p == end || *p == '\n' )
+		return DEFLINE_UNNAMED;		// "unnamed entry"
+	while( p < end && !is_space( ( unsigned char )*p ) ){
+		if( sid.size() < 99 )
+			sid.push_back( *p );
+		p++;
+	}
+	if( p < end && *p != '\n' ){
+		while( p < end && is_space( ( unsigned char )*p ) && *p != '\n' )
+			p++;
+	}
+	if( p < end && *p != '\n' ){
+		const char	*nl = static_cast<const char *>( memchr( p, '\n', size_t( end - p ) ) );
+		const char	*stop = nl ? nl : end;
+		if( stop - p >= 20000 - 1 )
+			return DEFLINE_LONG;		// definition line to be truncated
+		if( memchr( p, '\0', size_t( stop - p ) ) != nullptr )
+			return DEFLINE_NUL;		// ... or cut at a NUL
+		sdef.assign( p, size_t( stop - p ) );
+		p = stop;
+	}
+	*rest = p;
+	return DEFLINE_OK;
+}
+
 FastaStream::~FastaStream()
 {
 	{
@@ -213,35 +249,9 @@ void FastaStream::parse( size_t i, Meta &e, uint32_t *cw, uint32_t *mw ) const
 	e.slen = 0;
 	e.anomaly = false;
 	const char	*p = map_ + starts_[ i ], *const end = map_ + starts_[ i + 1 ];
-	if( *p != '>' ){
-		e.anomaly = true;		// "fastn file does not begin with '>'"
+	if( parse_defline( p, end, e.sid, e.sdef, &p ) != DEFLINE_OK ){
+		e.anomaly = true;
 		return;
-	}
-	p++;
-	while( p < end && is_space( ( unsigned char )*p ) && *p != '\n' )	// skipbl2nl
-		p++;
-	if( p == end || *p == '\n' ){
-		e.anomaly = true;		// "unnamed entry"
-		return;
-	}
-	while( p < end && !is_space( ( unsigned char )*p ) ){
-		if( e.sid.size() < 99 )
-			e.sid.push_back( *p );
-		p++;
-	}
-	if( p < end && *p != '\n' ){
-		while( p < end && is_space( ( unsigned char )*p ) && *p != '\n' )
-			p++;
-	}
-	if( p < end && *p != '\n' ){
-		const char	*nl = static_cast<const char *>( memchr( p, '\n', size_t( end - p ) ) );
-		const char	*stop = nl ? nl : end;
-		if( stop - p >= 20000 - 1 || memchr( p, '\0', size_t( stop - p ) ) != nullptr ){
-			e.anomaly = true;	// definition line to be truncated, or cut at a NUL
-			return;
-		}
-		e.sdef.assign( p, size_t( stop - p ) );
-		p = stop;
 	}
 	// the letters: sixteen to a code word, thirty-two to a mask word, each word stored once
 	const unsigned char	*cls = CLASSES.cls;

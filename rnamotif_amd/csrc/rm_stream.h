@@ -27,6 +27,13 @@ namespace rma {
 // the packed words of a batch that is done with, for the next batch to take (see rm_stream.cpp)
 void	recycle_words( PackWords &&w );
 
+// An entry's definition line as FN_fgetseq() reads it (dbutil.c:52-102): [p, end) begins at the entry's '>' and
+// reaches at least to the line's '\n' (or the end of the input).  sid (at most 99 bytes) and sdef are filled and
+// *rest is where the sequence begins (the '\n' or end); anything but DEFLINE_OK is an entry the serial reader has a
+// diagnostic for.  Shared by FastaStream and the device route (rma_db_create_device_fasta).
+enum { DEFLINE_OK = 0, DEFLINE_NOT_GT, DEFLINE_UNNAMED, DEFLINE_LONG, DEFLINE_NUL };
+int	parse_defline( const char *p, const char *end, std::string &sid, std::string &sdef, const char **rest );
+
 class FastaStream {
 public:
 	FastaStream() = default;
