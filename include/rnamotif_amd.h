@@ -321,6 +321,31 @@ int	rma_replay_device( rma_replay_t *rp, const rma_db_t *db, const int32_t *d_hi
 		int64_t *n_printed, uint8_t *accepted, char *err, size_t errlen );
 int	rma_replay_close( rma_replay_t *rp, char *err, size_t errlen );	/* runs the END program */
 
+/* ---- hit structures as device tensors: the records of a database made by rma_db_create_device() or
+ * rma_db_create_device_fasta() expanded base by base, on the device (csrc/rm_hitstruct.h has the rule, shared by
+ * the host and the kernel).  The unit is a record's window as rma_replay_device() cuts it: the bases its elements
+ * and contexts cover, window h at [ off[ h ], off[ h + 1 ] ) of the per-base arrays, lo[ h ] its first position on
+ * the hit's strand.  Per base: base, its letter as rma_replay_device() reads it (letters as there); elem, the
+ * descriptor element it belongs to (n_elems / n_elems + 1: the left / right context, -1: none); mate[ 3 ], the
+ * window indices of the bases it is matched with in the other strands of its helix, in descriptor order, padded
+ * with -1 -- one for h5/h3 and p5/p3, two for a triplex, three for a 4-plex, whether or not the matcher counted
+ * the position as a mispair.  d_hits: n_hits records of the scanner's program in memory of its device, any rows
+ * in any order.  Every record is checked on the device before anything is written: rma_replay_device()'s checks,
+ * and the strands of a helix having one length; a bad record fails the call, naming its index.
+ * rma_hit_structures_size() returns the window bytes of all records in *total and synchronises once.
+ * rma_hit_structures() checks and counts again (it keeps nothing from the first call; one wait for two words),
+ * refuses a total that is not what it finds, then queues the kernels that fill the outputs and returns without
+ * waiting for them: they run behind what is queued on `stream` (the caller's hipStream_t, NULL = the default
+ * stream) now and ahead of what is queued there next.  The outputs are device memory of the scanner's device,
+ * checked as rma_db_create_device's text.  Scratch is the scanner's, made on the first call. */
+int	rma_hit_structures_size( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		void *stream, int64_t *total, char *err, size_t errlen );
+int	rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *letters, int64_t total,
+		int64_t *d_off /* n_hits+1 */, int32_t *d_lo /* n_hits */, uint8_t *d_base /* total */,
+		int16_t *d_elem /* total */, int32_t *d_mate /* 3*total */,
+		void *stream, char *err, size_t errlen );
+
 #ifdef __cplusplus
 }
 #endif

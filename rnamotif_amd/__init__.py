@@ -144,6 +144,8 @@ def lib() -> C.CDLL:
     L.rma_db_read_packed.argtypes = [vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_scan_records_to_device.argtypes = [vp, vp, C.c_int64, vp, C.c_char_p, C.c_size_t]
     L.rma_replay_device.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, cpp, cpp, vp, i64p, vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_structures_size.argtypes = [vp, vp, vp, C.c_int64, vp, i64p, C.c_char_p, C.c_size_t]
+    L.rma_hit_structures.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_program_loose.argtypes = [vp]
     L.rma_program_loose.restype = C.c_int
     _lib = L
@@ -391,6 +393,37 @@ def alphabet_letters(alphabet: str) -> bytes:
     return bytes(tab)
 
 
+class HitStructures:
+    """Scanner.hit_structures()'s result: the windows of n records, base by base, as tensors on the scanner's device.
+
+    off   int64 [n+1]  window h is [off[h], off[h+1]) of the per-base tensors
+    lo    int32 [n]    its first position on the hit's strand
+    base  uint8 [T]    the letters as Replay.device() reads them
+    elem  int16 [T]    the descriptor element of each base (n_elems / n_elems + 1: left / right context, -1: none)
+    mate  int32 [T, 3] window-relative indices of the bases it is matched with, -1 padding"""
+
+    def __init__(self, off, lo, base, elem, mate):
+        self.off, self.lo, self.base, self.elem, self.mate = off, lo, base, elem, mate
+
+    def padded(self, fill=(ord("n"), -1, -1)):
+        """([n, Lmax] base, elem, [n, Lmax, 3] mate, bool mask) with Lmax the longest window; fill: the values of
+        (base, elem, mate) past a window's end.  Plain torch operations, no kernel of this package."""
+        import torch
+        n = int(self.lo.shape[0])
+        lens = self.off[1:] - self.off[:-1]
+        width = int(lens.max()) if n else 0
+        col = torch.arange(width, device=self.off.device, dtype=torch.int64)
+        mask = col[None, :] < lens[:, None]
+        at = (self.off[:-1, None] + col[None, :])[mask]
+        base = torch.full((n, width), int(fill[0]), dtype=self.base.dtype, device=self.base.device)
+        elem = torch.full((n, width), int(fill[1]), dtype=self.elem.dtype, device=self.elem.device)
+        mate = torch.full((n, width, 3), int(fill[2]), dtype=self.mate.dtype, device=self.mate.device)
+        base[mask] = self.base[at]
+        elem[mask] = self.elem[at]
+        mate[mask] = self.mate[at]
+        return base, elem, mate, mask
+
+
 class Scanner:
     """The motif program on one GPU (RM_fm_init + RM_find_motif)."""
 
@@ -507,6 +540,53 @@ class Scanner:
             _check(lib().rma_scan_records_to_device(self._h, out.data_ptr(), out.numel(),
                                                     torch.cuda.current_stream(dev).cuda_stream, err, _ERRLEN), err)
         return out
+
+    def hit_structures(self, db: Database, hits, letters: Optional[bytes] = None) -> HitStructures:
+        """The secondary structure of records of a database made by database_from_tensor() or
+        database_from_fasta_tensor(), as tensors on the GPU (rma_hit_structures; the rule is csrc/rm_hitstruct.h's):
+        per base of each record's window -- the bases its elements and contexts cover, what Replay.device() reads --
+        its letter, its descriptor element and the bases it is matched with.  hits: int32 CUDA tensor [n, hit_stride]
+        on the scanner's device, scan_tensor()'s output or any rows of it in any order (hits[mask] of
+        Replay.device(..., accepted=True) for the accepted ones).  letters as Replay.device().  The tensors are torch's
+        and ready on torch's current stream; the call waits once, for the total length.  A malformed record is refused
+        (RnamotifError naming its index) before anything is written."""
+        import torch
+        if getattr(db, "_h", None) is None or not db._h:
+            raise ValueError("the database is closed")
+        if getattr(db, "_text", None) is None:
+            raise ValueError("the database was not made by database_from_tensor(): replay it with batch() or pack()")
+        if not isinstance(hits, torch.Tensor):
+            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
+        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{self.device}")
+        if hits.dtype != torch.int32:
+            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
+        stride = self.descr.hit_stride
+        if hits.ndim != 2 or int(hits.shape[1]) != stride:
+            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this scanner's descriptor are needed")
+        if letters is None and db.alphabet is not None:
+            letters = alphabet_letters(db.alphabet)
+        if letters is not None and len(letters) != 256:
+            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
+        hits = hits.contiguous()
+        n = int(hits.shape[0])
+        dev = torch.device("cuda", self.device)
+        L = lib()
+        err = C.create_string_buffer(_ERRLEN)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        total = C.c_int64(0)
+        if n:
+            _check(L.rma_hit_structures_size(self._h, db._h, hits.data_ptr(), n, stream, C.byref(total), err, _ERRLEN), err)
+        t = int(total.value)
+        st = HitStructures(torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                           torch.empty(t, dtype=torch.uint8, device=dev), torch.empty(t, dtype=torch.int16, device=dev),
+                           torch.empty((t, 3), dtype=torch.int32, device=dev))
+        _check(L.rma_hit_structures(self._h, db._h, hits.data_ptr() if n else None, n, letters, t, st.off.data_ptr(),
+                                    st.lo.data_ptr() if n else None, st.base.data_ptr() if t else None,
+                                    st.elem.data_ptr() if t else None, st.mate.data_ptr() if t else None, stream, err, _ERRLEN), err)
+        # (the records are read by kernels queued behind this stream: torch keeps their memory until those have run)
+        hits.record_stream(torch.cuda.current_stream(dev))
+        return st
 
     def set_option(self, name: str, value: int) -> None:
         """A launch-shape / diagnostic switch between scans (rma_scanner_set_option); the RNAMOTIF_*

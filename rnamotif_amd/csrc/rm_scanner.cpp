@@ -40,6 +40,7 @@
 #include "rm_hitsort_dev.h"
 #include "rm_dbpack_dev.h"
 #include "rm_hitwin_dev.h"
+#include "rm_hitstruct_dev.h"
 #include "rm_fasta_dev_kernels.h"
 #include "rm_stream.h"
 #include "rnamotif_amd.h"
@@ -196,6 +197,10 @@ struct rma_scanner {
 	int64_t	n_last = 0;
 	int	last_state = 0;			// (rma_scanner_last_state)
 	bool	last_relabelled = false;	// rma_gather_hits has put database-wide entry numbers into d_last's records
+	// rma_hit_structures: the span scratch and stream (made on its first call), the program's table and the running total
+	rma::HitWindowScratch	*hs_win = nullptr;
+	rma::HitStructTable	*d_hs_table = nullptr;
+	int64_t	*d_hs_carry = nullptr;
 };
 
 struct rma_db {
@@ -410,6 +415,8 @@ extern "C" void rma_scanner_destroy( rma_scanner_t *sc )
 	( void )hipFree( sc->d_counters );
 	( void )hipFree( sc->d_spill );
 	( void )hipFree( sc->d_pool );
+	rma::hitwin_scratch_free( sc->hs_win );
+	( void )hipFree( sc->d_hs_table );		// (the running total lies behind the table)
 	for( int i = 0; i < 5; i++ )
 		if( sc->ev[ i ] )
 			( void )hipEventDestroy( sc->ev[ i ] );
@@ -1171,9 +1178,9 @@ static int scratch_on( rma::HitWindowScratch **scratch, int device, char *err, s
 	return 0;
 }
 
-// the words of a bad record, why it is bad
+// the words of a bad record, why it is bad; tab: the helix check as well (rma_hit_structures); nothing: "printed" or "written"
 static int bad_record( rma::HitWindowScratch *s, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits, int64_t h,
-	char *err, size_t errlen )
+	const rma::HitStructTable *tab, const char *nothing, char *err, size_t errlen )
 {
 	const int	stride = rma_hit_stride( &prog );
 	std::vector<int32_t>	w( static_cast<size_t>( stride ) );
@@ -1182,11 +1189,17 @@ static int bad_record( rma::HitWindowScratch *s, const rma_db *db, const rma_pro
 	int32_t	lo, hi;
 	int	which;
 	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
-	const int	r = rma::hitwin_span( w.data(), shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which );
+	const int	r = tab != nullptr ? rma::hitstruct_check( w.data(), *tab, shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which ) :
+		rma::hitwin_span( w.data(), shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which );
 	if( r == rma::HW_ENTRY )
-		snprintf( err, errlen, "record %lld: entry %d outside [0, %d): nothing printed", ( long long )h, w[ 0 ], db->n_seq );
+		snprintf( err, errlen, "record %lld: entry %d outside [0, %d): nothing %s", ( long long )h, w[ 0 ], db->n_seq, nothing );
 	else if( r == rma::HW_STRAND )
-		snprintf( err, errlen, "record %lld: strand %d, not 0 or 1: nothing printed", ( long long )h, w[ 1 ] );
+		snprintf( err, errlen, "record %lld: strand %d, not 0 or 1: nothing %s", ( long long )h, w[ 1 ], nothing );
+	else if( r == rma::HS_HELIX ){
+		const int	first = tab->e[ which ].strand[ 0 ];
+		snprintf( err, errlen, "record %lld: element %d has length %d, element %d of the same helix length %d: nothing %s", ( long long )h,
+			which, w[ RMA_HIT_HDR + 4 * which + 1 ], first, w[ RMA_HIT_HDR + 4 * first + 1 ], nothing );
+	}
 	else if( r == rma::HW_EXTENT ){
 		const int	k = which < shape.n_elems ? RMA_HIT_HDR + 4 * which : which == shape.n_elems ? shape.ctx_off : shape.ctx_off + 2;
 		char	what[ 32 ];
@@ -1194,8 +1207,8 @@ static int bad_record( rma::HitWindowScratch *s, const rma_db *db, const rma_pro
 			snprintf( what, sizeof( what ), "element %d", which );
 		else
 			snprintf( what, sizeof( what ), "the %s context", which == shape.n_elems ? "left" : "right" );
-		snprintf( err, errlen, "record %lld: %s at offset %d, length %d, outside entry %d's %d bases: nothing printed", ( long long )h,
-			what, w[ k ], w[ k + 1 ], w[ 0 ], db->h_slen[ size_t( w[ 0 ] ) ] );
+		snprintf( err, errlen, "record %lld: %s at offset %d, length %d, outside entry %d's %d bases: nothing %s", ( long long )h,
+			what, w[ k ], w[ k + 1 ], w[ 0 ], db->h_slen[ size_t( w[ 0 ] ) ], nothing );
 	}else
 		snprintf( err, errlen, "record %lld: refused on the device, not on the host (records changed during the call?)", ( long long )h );
 	return 1;
@@ -1269,7 +1282,7 @@ int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rm
 			HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
 		HIPCHK( hipStreamSynchronize( st ) );
 		if( c0 == 0 && *s->h_bad != ~0ull )
-			return bad_record( s, db, prog, d_hits, int64_t( *s->h_bad ), err, errlen );
+			return bad_record( s, db, prog, d_hits, int64_t( *s->h_bad ), nullptr, "printed", err, errlen );
 		for( int64_t a = 0; a < cn; ){
 			int64_t	b = a + 1;
 			while( b < cn && b - a < piece_records && s->h_off[ b + 1 ] - s->h_off[ a ] <= HW_PIECE_WINDOW )
@@ -1292,6 +1305,186 @@ int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rm
 		}
 	}
 	return 0;
+}
+
+// ---------------------------------------------------------------- hit structures as device tensors
+// rma_hit_structures_size() / rma_hit_structures(): the spans, sources and offsets of rm_hitwin_dev.hip in chunks of
+// HW_CHUNK records, the helix check and the fill kernel of rm_hitstruct_dev.hip.  The outputs are the caller's and are
+// written in place: a chunk's offsets count from its first record (the scan's), the window bytes of the chunks
+// before it wait in a word on the device (*d_hs_carry), so no chunk needs the host.  The work runs on a stream of the
+// scanner's own, behind the caller's stream and, when something was written, ahead of what the caller queues next.
+namespace {
+
+// What both calls do first: the database, the records and the scanner's scratch (made on first use).  n_hits == 0
+// needs none of it.
+int hit_structures_args( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, const char *who, char *err, size_t errlen )
+{
+	{
+		std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+		if( db == nullptr || g_device_dbs.count( db ) == 0 ){
+			snprintf( err, errlen, "%s: the database (%p) was not made by rma_db_create_device() or has been destroyed", who,
+				static_cast<const void *>( db ) );
+			return 1;
+		}
+	}
+	const int	stride = rma_hit_stride( &sc->prog );
+	if( n_hits < 0 || ( n_hits > 0 && d_hits == nullptr ) || n_hits > INT64_MAX / 16 / stride ){
+		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )n_hits );
+		return 1;
+	}
+	if( db->device != sc->device ){
+		snprintf( err, errlen, "%s: the database is on device %d, the scanner on device %d", who, db->device, sc->device );
+		return 1;
+	}
+	HIPCHK( hipSetDevice( sc->device ) );
+	if( n_hits == 0 )
+		return 0;
+	if( check_device_bytes( d_hits, sc->device, 0, n_hits * stride * 4, "the records", err, errlen ) )
+		return 1;
+	if( db->text_hi > db->text_lo && check_device_bytes( db->text, db->device, db->text_lo, db->text_hi, "the database's text", err, errlen ) )
+		return 1;
+	if( scratch_on( &sc->hs_win, sc->device, err, errlen ) )
+		return 1;
+	if( sc->d_hs_table == nullptr ){
+		// the program's table and, behind it, the running total
+		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
+		const size_t	at = ( sizeof( rma::HitStructTable ) + 7 ) & ~size_t( 7 );
+		void	*p = nullptr;
+		HIPCHK( hipMalloc( &p, at + sizeof( int64_t ) ) );
+		sc->d_hs_table = static_cast<rma::HitStructTable *>( p );
+		sc->d_hs_carry = reinterpret_cast<int64_t *>( static_cast<char *>( p ) + at );
+		HIPCHK( hipMemcpy( sc->d_hs_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
+	}
+	return 0;
+}
+
+// One chunk's spans, sources and offsets into the scratch; *bad as hit_spans
+int hit_structures_spans( rma_scanner_t *sc, const rma_db *db, const int32_t *ch, int64_t cn, unsigned long long *bad, char *err, size_t errlen )
+{
+	rma::HitWindowScratch	*s = sc->hs_win;
+	HIPCHK( rma::hit_spans( ch, cn, rma_hit_stride( &sc->prog ), rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq,
+		s->d_lo, s->d_len, s->d_src, bad, s->stream ) );
+	size_t	tb = s->tmp_bytes;
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, s->stream ) );
+	return 0;
+}
+
+// Every record checked on the device and the window bytes counted (n_hits > 0, hit_structures_args has passed): one
+// synchronisation.  A call of one chunk leaves that chunk's spans in the scratch.
+int hit_structures_count( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, void *stream, int64_t *total,
+	char *err, size_t errlen )
+{
+	rma::HitWindowScratch	*s = sc->hs_win;
+	hipStream_t	st = s->stream;
+	const int	stride = rma_hit_stride( &sc->prog );
+	// behind the caller's work on its stream (the records) and the database's tables
+	if( stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	// d_bad[ 0 ]: the least index of a bad record, counted over the call; d_bad[ 2 ]: where the spans of a later chunk,
+	// which count from the chunk's first record, put theirs (the same records, already judged)
+	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( sc->d_hs_carry, 0, sizeof( int64_t ), st ) );
+	const bool	chunks = n_hits > HW_CHUNK;
+	if( chunks )
+		HIPCHK( rma::hit_spans( d_hits, n_hits, stride, rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq, nullptr, nullptr,
+			nullptr, s->d_bad, st ) );
+	HIPCHK( rma::hit_helix_check( d_hits, n_hits, stride, sc->d_hs_table, s->d_bad, st ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		if( hit_structures_spans( sc, db, d_hits + c0 * stride, cn, chunks ? s->d_bad + 2 : s->d_bad, err, errlen ) )
+			return 1;
+		HIPCHK( rma::hit_carry_add( sc->d_hs_carry, s->d_off + cn, st ) );
+	}
+	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + 1, sc->d_hs_carry, sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( s->h_bad[ 0 ] != ~0ull ){
+		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
+		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), &tab, "written", err, errlen );
+	}
+	*total = int64_t( s->h_bad[ 1 ] );
+	return 0;
+}
+
+}	// namespace
+
+extern "C" int rma_hit_structures_size( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	void *stream, int64_t *total, char *err, size_t errlen )
+{
+	*total = 0;
+	if( hit_structures_args( sc, db, d_hits, n_hits, "rma_hit_structures_size", err, errlen ) )
+		return 1;
+	return n_hits == 0 ? 0 : hit_structures_count( sc, db, d_hits, n_hits, stream, total, err, errlen );
+}
+
+extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, int64_t total, int64_t *d_off, int32_t *d_lo, uint8_t *d_base, int16_t *d_elem, int32_t *d_mate,
+	void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_structures";
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	if( total < 0 || total > INT64_MAX / 16 || d_off == nullptr || ( n_hits > 0 && d_lo == nullptr ) ||
+		( total > 0 && ( d_base == nullptr || d_elem == nullptr || d_mate == nullptr ) ) ){
+		snprintf( err, errlen, "%s: %lld window bytes: bad arguments", who, ( long long )total );
+		return 1;
+	}
+	// the outputs: the caller's, each inside its allocation on the scanner's device
+	if( check_device_bytes( d_off, sc->device, 0, ( n_hits + 1 ) * 8, "the offsets", err, errlen ) ||
+		( n_hits > 0 && check_device_bytes( d_lo, sc->device, 0, n_hits * 4, "the first positions", err, errlen ) ) ||
+		( total > 0 && ( check_device_bytes( d_base, sc->device, 0, total, "the bases", err, errlen ) ||
+			check_device_bytes( d_elem, sc->device, 0, total * 2, "the elements", err, errlen ) ||
+			check_device_bytes( d_mate, sc->device, 0, total * 12, "the mates", err, errlen ) ) ) )
+		return 1;
+	hipStream_t	caller = static_cast<hipStream_t>( stream );
+	int64_t	found = 0;
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	if( n_hits > 0 ){
+		rma::HitWindowScratch	*s = sc->hs_win;
+		// the letters: the caller's, the readers', or the letters of the database's own codes (as rma_replay_device);
+		// on their way ahead of the count, whose synchronisation leaves the page-locked copy free for the next call
+		tab = s->d_tab;
+		if( letters != nullptr )
+			memcpy( s->h_tab, letters, 256 );
+		else if( db->default_table )
+			for( int b = 0; b < 256; b++ )
+				s->h_tab[ b ] = rma::hitwin_reader_letter( static_cast<unsigned char>( b ) );
+		else{
+			tab = db->d_table;
+			codes = 1;
+		}
+		if( tab == s->d_tab )
+			HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, s->stream ) );
+		if( hit_structures_count( sc, db, d_hits, n_hits, stream, &found, err, errlen ) )
+			return 1;
+	}
+	if( found != total ){
+		snprintf( err, errlen, "%s: the windows of the %lld records have %lld bytes, not the %lld of `total`: nothing written", who,
+			( long long )n_hits, ( long long )found, ( long long )total );
+		return 1;
+	}
+	if( n_hits == 0 ){
+		HIPCHK( hipMemsetAsync( d_off, 0, sizeof( int64_t ), caller ) );
+		return 0;
+	}
+	rma::HitWindowScratch	*s = sc->hs_win;
+	hipStream_t	st = s->stream;
+	const int	stride = rma_hit_stride( &sc->prog );
+	HIPCHK( hipMemsetAsync( sc->d_hs_carry, 0, sizeof( int64_t ), st ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		const int32_t	*ch = d_hits + c0 * stride;
+		// (a call of one chunk: the count's spans are still there)
+		if( n_hits > HW_CHUNK && hit_structures_spans( sc, db, ch, cn, s->d_bad + 2, err, errlen ) )
+			return 1;
+		const rma::HitStructOut	out{ d_off + c0, d_lo + c0, d_base, d_elem, d_mate };
+		HIPCHK( rma::hit_struct_fill( db->text, ch, cn, stride, rma::hitwin_shape( sc->prog ), sc->d_hs_table, s->d_lo, s->d_src, s->d_off,
+			sc->d_hs_carry, tab, codes, out, c0 + cn == n_hits, st ) );
+		HIPCHK( rma::hit_carry_add( sc->d_hs_carry, s->d_off + cn, st ) );
+	}
+	return stream_after( caller, st, err, errlen );
 }
 
 // ---------------------------------------------------------------- pinned host memory
