@@ -346,6 +346,28 @@ int	rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_
 		int16_t *d_elem /* total */, int32_t *d_mate /* 3*total */,
 		void *stream, char *err, size_t errlen );
 
+/* ---- rmprune's rule over records, on the device: d_keep[ h ] = 1 where the rmprune tool would keep record h of the
+ * n_hits records at d_hits, 0 where it would drop it as an "unzipped" version of another -- the decisions the tool
+ * makes on the printed form of the same records in the same order (csrc/rm_prune.h has the rule, shared by the host
+ * and the kernels; csrc/tools/rmprune.cpp is the tool).  In a paragraph: consecutive records whose entries have
+ * the same name group are a run, cut into blocks of 1000; inside a block the records in front of the first one on
+ * strand 1 and those from it on are split into groups, a new group wherever a record leaves the span of its group's
+ * first record; inside a group of two or more every kept record b, from the last to the second, is compared with
+ * the kept records b1 in front of it, nearest first, by the printed spans of their helix strands: where b1 is b
+ * with base pairs opened at the inside end of helices b1 is dropped, where b is b1 so unzipped b is dropped and its
+ * pass ends.  db: any database of the scanner's device; only its entry lengths are read, no text is needed.
+ * group_of_entry: host array of one id per entry of db, equal ids for entries the tool takes as one name (a sid up
+ * to its first '.' or blank), or NULL: every entry its own.  d_hits / d_keep: device memory of the scanner's
+ * device, checked as rma_hit_structures checks its outputs; any rows in any order, and the order given is the order
+ * judged.  Every record is checked on the device first (rma_replay_device()'s checks); a bad record fails the call,
+ * naming its index, and d_keep is not written.  n_hits == 0 does nothing.  The kernels are queued on `stream` (the
+ * caller's hipStream_t, NULL = the default stream); the call waits once, for the check's result and the number of
+ * blocks, then queues the last kernel and returns without waiting for it.  Scratch (16 + 8 bytes per helix strand
+ * + 9 bytes per record) is the scanner's, made on the first call and grown. */
+int	rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		const int32_t *group_of_entry /* host, n_seq, or NULL */, uint8_t *d_keep /* n_hits */,
+		void *stream, char *err, size_t errlen );
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,7 @@ def lib() -> C.CDLL:
     L.rma_replay_device.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, cpp, cpp, vp, i64p, vp, C.c_char_p, C.c_size_t]
     L.rma_hit_structures_size.argtypes = [vp, vp, vp, C.c_int64, vp, i64p, C.c_char_p, C.c_size_t]
     L.rma_hit_structures.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_prune_hits.argtypes = [vp, vp, vp, C.c_int64, i32p, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_program_loose.argtypes = [vp]
     L.rma_program_loose.restype = C.c_int
     _lib = L
@@ -393,6 +394,23 @@ def alphabet_letters(alphabet: str) -> bytes:
     return bytes(tab)
 
 
+def prune_groups(sids) -> np.ndarray:
+    """One id per entry for Scanner.prune(groups=...): int32, two ids equal iff the entries' names are equal as the
+    rmprune tool takes them from a hit's '>' line (getname): leading blanks skipped, the name up to the first '.'
+    or blank.  sids: the entries' names, bytes or str (db.sids of database_from_fasta_tensor())."""
+    ids, seen = [], {}
+    for sid in sids:
+        b = sid.encode() if isinstance(sid, str) else bytes(sid)
+        q = 0
+        while q < len(b) and b[q:q + 1].isspace():
+            q += 1
+        e = q
+        while e < len(b) and b[e:e + 1] != b"." and not b[e:e + 1].isspace():
+            e += 1
+        ids.append(seen.setdefault(b[q:e], len(seen)))
+    return np.asarray(ids, dtype=np.int32)
+
+
 class HitStructures:
     """Scanner.hit_structures()'s result: the windows of n records, base by base, as tensors on the scanner's device.
 
@@ -587,6 +605,47 @@ class Scanner:
         # (the records are read by kernels queued behind this stream: torch keeps their memory until those have run)
         hits.record_stream(torch.cuda.current_stream(dev))
         return st
+
+    def prune(self, db: Database, hits, groups=None):
+        """Which of these records the rmprune tool would keep, decided on the GPU (rma_prune_hits; the rule is
+        csrc/rm_prune.h's): a torch.bool tensor [n] on the scanner's device, ready on torch's current stream, False
+        where a record is only an "unzipped" version of another -- the tool's decisions on the printed form of the
+        same records in the same order.  The order given is the order judged: pass hits[accepted] of
+        Replay.device(..., accepted=True) to prune what would be printed, then hit_structures(db, hits[keep]).
+        hits: int32 CUDA tensor [n, hit_stride] on the scanner's device; db: the database the records are of (only
+        its entry lengths are read); groups: an int per entry, equal for entries the tool takes as one name
+        (prune_groups(db.sids)), default: every entry its own.  The call waits once, for the record check.  A
+        malformed record is refused (RnamotifError naming its index)."""
+        import torch
+        if getattr(db, "_h", None) is None or not db._h:
+            raise ValueError("the database is closed")
+        if not isinstance(hits, torch.Tensor):
+            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
+        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{self.device}")
+        if hits.dtype != torch.int32:
+            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
+        stride = self.descr.hit_stride
+        if hits.ndim != 2 or int(hits.shape[1]) != stride:
+            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this scanner's descriptor are needed")
+        g = None
+        if groups is not None:
+            g = np.ascontiguousarray(np.asarray(groups), dtype=np.int32)
+            if g.ndim != 1 or g.size != db.n_seqs:
+                raise ValueError(f"groups: one per entry, {db.n_seqs}, not {g.size if g.ndim == 1 else tuple(g.shape)}")
+        hits = hits.contiguous()
+        n = int(hits.shape[0])
+        dev = torch.device("cuda", self.device)
+        keep = torch.empty(n, dtype=torch.bool, device=dev)
+        if n:
+            err = C.create_string_buffer(_ERRLEN)
+            stream = torch.cuda.current_stream(dev)
+            _check(lib().rma_prune_hits(self._h, db._h, hits.data_ptr(), n,
+                                        g.ctypes.data_as(C.POINTER(C.c_int32)) if g is not None else None,
+                                        keep.data_ptr(), stream.cuda_stream, err, _ERRLEN), err)
+            # (the records are read by a kernel queued on this stream: torch keeps their memory until it has run)
+            hits.record_stream(stream)
+        return keep
 
     def set_option(self, name: str, value: int) -> None:
         """A launch-shape / diagnostic switch between scans (rma_scanner_set_option); the RNAMOTIF_*

@@ -41,6 +41,7 @@
 #include "rm_dbpack_dev.h"
 #include "rm_hitwin_dev.h"
 #include "rm_hitstruct_dev.h"
+#include "rm_prune_dev.h"
 #include "rm_fasta_dev_kernels.h"
 #include "rm_stream.h"
 #include "rnamotif_amd.h"
@@ -201,6 +202,12 @@ struct rma_scanner {
 	rma::HitWindowScratch	*hs_win = nullptr;
 	rma::HitStructTable	*d_hs_table = nullptr;
 	int64_t	*d_hs_carry = nullptr;
+	// rma_prune_hits: the program's table (two result words behind it), the keys, flags and block list of a call, the
+	// entries' name groups, two page-locked words, and the event behind the last call's kernels
+	rma::PruneTable	*d_pr_table = nullptr;
+	void	*d_pr = nullptr, *d_pr_groups = nullptr, *h_pr = nullptr;
+	size_t	pr_bytes = 0, pr_groups_bytes = 0, h_pr_bytes = 0;
+	hipEvent_t	pr_done = nullptr;
 };
 
 struct rma_db {
@@ -417,6 +424,12 @@ extern "C" void rma_scanner_destroy( rma_scanner_t *sc )
 	( void )hipFree( sc->d_pool );
 	rma::hitwin_scratch_free( sc->hs_win );
 	( void )hipFree( sc->d_hs_table );		// (the running total lies behind the table)
+	( void )hipFree( sc->d_pr_table );
+	( void )hipFree( sc->d_pr );
+	( void )hipFree( sc->d_pr_groups );
+	( void )hipHostFree( sc->h_pr );
+	if( sc->pr_done )
+		( void )hipEventDestroy( sc->pr_done );
 	for( int i = 0; i < 5; i++ )
 		if( sc->ev[ i ] )
 			( void )hipEventDestroy( sc->ev[ i ] );
@@ -1485,6 +1498,93 @@ extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const 
 		HIPCHK( rma::hit_carry_add( sc->d_hs_carry, s->d_off + cn, st ) );
 	}
 	return stream_after( caller, st, err, errlen );
+}
+
+// ---------------------------------------------------------------- rmprune's rule over records on the device
+// rma_prune_hits(): the kernels of rm_prune_dev.hip on the caller's stream.  The scratch -- the program's table, a
+// call's keys, flags and list of blocks, the entries' name groups -- is the scanner's, made on the first call and
+// grown; a later call on another stream waits for the kernels of the one before it (pr_done).  One wait, for two
+// words: the least index of a refused record and the number of blocks, which sizes the last launch.
+extern "C" int rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const int32_t *group_of_entry, uint8_t *d_keep, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_prune_hits";
+	if( sc == nullptr || db == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "database" );
+		return 1;
+	}
+	const int	stride = rma_hit_stride( &sc->prog );
+	const rma::PruneTable	tab = rma::prune_table( sc->prog );
+	const int	row = rma::prune_row_words( tab );
+	if( n_hits < 0 || ( n_hits > 0 && ( d_hits == nullptr || d_keep == nullptr ) ) || n_hits > INT64_MAX / 16 / std::max( stride, row ) ){
+		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )n_hits );
+		return 1;
+	}
+	if( db->device != sc->device ){
+		snprintf( err, errlen, "%s: the database is on device %d, the scanner on device %d", who, db->device, sc->device );
+		return 1;
+	}
+	HIPCHK( hipSetDevice( sc->device ) );
+	if( n_hits == 0 )
+		return 0;
+	if( check_device_bytes( d_hits, sc->device, 0, n_hits * stride * 4, "the records", err, errlen ) ||
+		check_device_bytes( d_keep, sc->device, 0, n_hits, "the keep flags", err, errlen ) )
+		return 1;
+	hipStream_t	st = static_cast<hipStream_t>( stream );
+	if( sc->d_pr_table == nullptr ){
+		const size_t	at = align256( sizeof( rma::PruneTable ) );
+		void	*p = nullptr;
+		HIPCHK( hipMalloc( &p, at + 256 ) );
+		sc->d_pr_table = static_cast<rma::PruneTable *>( p );
+		HIPCHK( hipMemcpy( sc->d_pr_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
+		HIPCHK( hipEventCreateWithFlags( &sc->pr_done, hipEventDisableTiming ) );
+		HIPCHK( hipEventRecord( sc->pr_done, st ) );
+	}
+	// behind the kernels of the call before this one (they read the scratch) and the database's tables
+	HIPCHK( hipStreamWaitEvent( st, sc->pr_done, 0 ) );
+	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	const size_t	n = size_t( n_hits ), parts = size_t( rma::prune_parts( n_hits ) );
+	const size_t	o_rows = align256( n * 16 ), o_bflag = o_rows + align256( n * size_t( row ) * 4 ), o_part = o_bflag + align256( n ),
+		o_part_x = o_part + align256( parts * 8 ), o_blocks = o_part_x + align256( parts * 8 ), total = o_blocks + align256( n * 8 );
+	HIPCHK( dev_room( &sc->d_pr, &sc->pr_bytes, total ) );
+	HIPCHK( host_room( &sc->h_pr, &sc->h_pr_bytes, 256 ) );
+	char	*d = static_cast<char *>( sc->d_pr ), *dt = reinterpret_cast<char *>( sc->d_pr_table ) + align256( sizeof( rma::PruneTable ) );
+	rma::PruneDev	pd;
+	pd.tab = sc->d_pr_table;
+	pd.groups = nullptr;
+	pd.hdr = reinterpret_cast<int32_t *>( d );
+	pd.rows = reinterpret_cast<int32_t *>( d + o_rows );
+	pd.bflag = reinterpret_cast<uint8_t *>( d + o_bflag );
+	pd.part = reinterpret_cast<long long *>( d + o_part );
+	pd.part_x = reinterpret_cast<long long *>( d + o_part_x );
+	pd.blocks = reinterpret_cast<long long *>( d + o_blocks );
+	pd.bad = reinterpret_cast<unsigned long long *>( dt );
+	pd.n_blocks = reinterpret_cast<long long *>( dt + 8 );
+	if( group_of_entry != nullptr && db->n_seq > 0 ){
+		// (pageable memory: the copy has left the caller's array when the call returns)
+		HIPCHK( dev_room( &sc->d_pr_groups, &sc->pr_groups_bytes, size_t( db->n_seq ) * 4 ) );
+		HIPCHK( hipMemcpyAsync( sc->d_pr_groups, group_of_entry, size_t( db->n_seq ) * 4, hipMemcpyHostToDevice, st ) );
+		pd.groups = static_cast<const int32_t *>( sc->d_pr_groups );
+	}
+	HIPCHK( hipMemsetAsync( pd.bad, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( pd.n_blocks, 0, sizeof( long long ), st ) );
+	HIPCHK( rma::prune_blocks( d_hits, n_hits, stride, rma::hitwin_shape( sc->prog ), row, db->d_slen, db->n_seq, pd, st ) );
+	unsigned long long	*h = static_cast<unsigned long long *>( sc->h_pr );
+	HIPCHK( hipMemcpyAsync( h, pd.bad, 16, hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( h[ 0 ] != ~0ull ){
+		if( scratch_on( &sc->hs_win, sc->device, err, errlen ) )
+			return 1;
+		return bad_record( sc->hs_win, db, sc->prog, d_hits, int64_t( h[ 0 ] ), nullptr, "judged", err, errlen );
+	}
+	const int64_t	n_blocks = int64_t( h[ 1 ] );
+	if( n_blocks < 1 || n_blocks > n_hits ){
+		snprintf( err, errlen, "%s: %lld blocks of %lld records (records changed during the call?)", who, ( long long )n_blocks, ( long long )n_hits );
+		return 1;
+	}
+	HIPCHK( rma::prune_rezip( n_hits, row, pd, n_blocks, d_keep, st ) );
+	HIPCHK( hipEventRecord( sc->pr_done, st ) );
+	return 0;
 }
 
 // ---------------------------------------------------------------- pinned host memory
