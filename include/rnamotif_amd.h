@@ -46,6 +46,9 @@ const rma_efndata_t	*rma_descr_efndata( const rma_descr_t *d );	/* NULL: no efn(
 const rma_efn2data_t	*rma_descr_efn2data( const rma_descr_t *d );	/* NULL: no efn2() in the score section */
 int	rma_descr_minlen( const rma_descr_t *d );			/* rm_dminlen */
 int	rma_descr_maxlen( const rma_descr_t *d );			/* rm_dmaxlen, RMA_UNBOUNDED if open */
+/* the fields of the "#RM descr" line the printer writes for this descriptor, one per printed column, separated by
+ * blanks (e.g. "h5(tag='1') ss h3(tag='1')"), into buf (NUL-terminated, cut at buflen); returns their length */
+size_t	rma_descr_names( const rma_descr_t *d, char *buf, size_t buflen );
 /* for bindings that do not want to mirror the struct: n_elems, n_searches, hit stride,
  * ctx offset, efn offset, n_efn_sites, chk_both_strs, windowsize */
 void	rma_program_info( const rma_program_t *prog, int32_t info[ 8 ] );
@@ -344,6 +347,36 @@ int	rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_
 		const uint8_t *letters, int64_t total,
 		int64_t *d_off /* n_hits+1 */, int32_t *d_lo /* n_hits */, uint8_t *d_base /* total */,
 		int16_t *d_elem /* total */, int32_t *d_mate /* 3*total */,
+		void *stream, char *err, size_t errlen );
+
+/* ---- hit records as an alignment, on the device: the byte matrix whose row h, cut into lines of 70 bytes, is what
+ * `rmfmt -a` writes as the sequence lines of record h's printed form (csrc/rm_hitalign.h has the rule, shared by the
+ * host and the kernels).  Columns stand in the order the fields are printed: the left context when the descriptor
+ * has one, the elements, the right context when it has one (at most 102).  A field is as wide as it is printed (an
+ * empty element 1, the "."); a column as wide as its widest field over the records given; h3, t2, q2 and q4 columns
+ * are right-aligned, all others left-aligned.  A row has W = sum of the widths + n_cols - 1 bytes: every field padded
+ * to its column's width with the gap byte, one separator byte between columns.  The letters are those of
+ * rma_hit_structures() (letters as there).  d_pos, where given, receives for every letter byte the position on the
+ * hit's strand it came from (the coordinate of rma_hit_structures' lo), -1 for every other byte.  d_hits: n_hits
+ * records of the scanner's program in memory of its device, any rows in any order; pointers are checked as
+ * rma_hit_structures checks them.  Every record is checked on the device first (rma_replay_device()'s checks; strands
+ * of unequal length are not refused, as rmfmt does not refuse them); a bad record fails the call, naming its index.
+ * rma_hit_alignment_shape() checks the records, reduces the widths and waits once: *n_cols, widths[ c ] for
+ * c < *n_cols (0 behind them), right[ c ] = 1 for a right-aligned column, *row_bytes = W.  With n_hits == 0 the widths
+ * are 0 and *row_bytes is n_cols - 1.
+ * rma_hit_alignment() checks and reduces again (it keeps nothing from the first call; one wait), refuses a bad record
+ * and any given width below what the records need, naming the column, then queues the fill and returns without
+ * waiting for it: it runs behind what is queued on `stream` (the caller's hipStream_t, NULL = the default stream) now
+ * and ahead of what is queued there next.  Given widths may be larger than needed: that is how several batches share
+ * one set of columns.  fill: the gap, separator and empty-field bytes, NULL for rmfmt's "-|.".  n_hits == 0 writes
+ * nothing.  Scratch is the scanner's, made on the first call and freed by rma_scanner_destroy(). */
+int	rma_hit_alignment_shape( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		int32_t *n_cols, int32_t *widths /* host, room for 102 */, uint8_t *right /* host, 102, may be NULL */,
+		int64_t *row_bytes, void *stream, char *err, size_t errlen );
+int	rma_hit_alignment( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		const int32_t *widths /* host, n_cols */, const uint8_t *letters /* 256 or NULL */,
+		const uint8_t fill[ 3 ] /* gap, separator, empty; NULL: "-|." */,
+		uint8_t *d_rows /* n_hits * W */, int32_t *d_pos /* n_hits * W or NULL */,
 		void *stream, char *err, size_t errlen );
 
 /* ---- rmprune's rule over records, on the device: d_keep[ h ] = 1 where the rmprune tool would keep record h of the

@@ -146,6 +146,10 @@ def lib() -> C.CDLL:
     L.rma_replay_device.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, cpp, cpp, vp, i64p, vp, C.c_char_p, C.c_size_t]
     L.rma_hit_structures_size.argtypes = [vp, vp, vp, C.c_int64, vp, i64p, C.c_char_p, C.c_size_t]
     L.rma_hit_structures.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_alignment_shape.argtypes = [vp, vp, vp, C.c_int64, i32p, i32p, vp, i64p, vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_alignment.argtypes = [vp, vp, vp, C.c_int64, i32p, C.c_char_p, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_descr_names.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.rma_descr_names.restype = C.c_size_t
     L.rma_prune_hits.argtypes = [vp, vp, vp, C.c_int64, i32p, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_program_loose.argtypes = [vp]
     L.rma_program_loose.restype = C.c_int
@@ -202,6 +206,14 @@ class Descriptor:
         # elements whose seq= the scan tests loosely (back references, iupac = 0 letters): the records of a scan are
         # then a superset of rnamotif's candidates until they are replayed (rma_program_loose)
         self.loose = L.rma_program_loose(self.program)
+
+    def names(self) -> List[str]:
+        """The fields of the '#RM descr' line, one per printed column: "h5(tag='1')", "ss", ... (contexts included)."""
+        L = lib()
+        n = L.rma_descr_names(self._h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        L.rma_descr_names(self._h, buf, n + 1)
+        return buf.value.decode().split()
 
     def search_order(self) -> List[int]:
         """Element index heading each search level (rm_searches[k]->s_descr->s_index)."""
@@ -442,6 +454,38 @@ class HitStructures:
         return base, elem, mate, mask
 
 
+class HitAlignment:
+    """Scanner.align()'s result: n records laid into the columns of an alignment, as `rmfmt -a` lays their printed form.
+
+    rows     uint8 [n, W] on the scanner's device: the fields in column order, each padded to its column's width
+             with the gap byte, one separator byte between columns
+    pos      int32 [n, W] or None: for a letter byte the position on the hit's strand it came from (the coordinate
+             of HitStructures.lo), -1 for gap, separator and empty-field bytes
+    widths   np.int32 [n_cols]; col_off np.int64 [n_cols], the first byte of each column; right np.bool_ [n_cols],
+             True for the right-aligned columns (h3, t2, q2, q4); names, the '#RM descr' fields
+    col      np.int16 [W]: the column of each byte of a row, -1 for a separator
+    fill     the gap, separator and empty-field bytes"""
+    LINE = 70       # rmfmt.c: WBSIZE
+
+    def __init__(self, rows, pos, widths, right, names, fill):
+        self.rows, self.pos, self.fill, self.names = rows, pos, bytes(fill), list(names)
+        self.widths = np.asarray(widths, dtype=np.int32)
+        self.right = np.asarray(right, dtype=np.bool_)
+        n_cols = self.widths.size
+        self.col_off = np.zeros(n_cols, dtype=np.int64)
+        if n_cols:
+            self.col_off[1:] = np.cumsum(self.widths[:-1].astype(np.int64) + 1)
+        w = int(self.widths.sum(dtype=np.int64)) + max(n_cols - 1, 0)
+        self.col = np.full(w, -1, dtype=np.int16)
+        for c in range(n_cols):
+            self.col[self.col_off[c]:self.col_off[c] + self.widths[c]] = c
+
+    def lines(self, h: int) -> List[bytes]:
+        """Row h as rmfmt -a writes it: its bytes cut into lines of 70 (the sequence lines, without the '>' line)."""
+        row = bytes(self.rows[h].cpu().numpy().tobytes())
+        return [row[i:i + self.LINE] for i in range(0, len(row), self.LINE)]
+
+
 class Scanner:
     """The motif program on one GPU (RM_fm_init + RM_find_motif)."""
 
@@ -605,6 +649,75 @@ class Scanner:
         # (the records are read by kernels queued behind this stream: torch keeps their memory until those have run)
         hits.record_stream(torch.cuda.current_stream(dev))
         return st
+
+    def align(self, db: Database, hits, letters: Optional[bytes] = None, widths=None, fill: bytes = b"-|.", pos: bool = False) -> HitAlignment:
+        """Records of a database made by database_from_tensor() or database_from_fasta_tensor() as an alignment on the
+        GPU (rma_hit_alignment; the rule is csrc/rm_hitalign.h's): a uint8 matrix [n, W] whose row h, cut into lines
+        of 70, is what `rmfmt -a` writes for the printed form of record h among these records.  Every descriptor
+        element (and context) is a column as wide as its longest instance over the records; shorter instances are
+        padded with fill[0], the 3' strands h3, t2, q2, q4 on their left so that paired bases share a column; fill[1]
+        separates columns and fill[2] stands for an empty element.  hits and letters as hit_structures().  widths:
+        one per column, at least what the records need (RnamotifError naming the column otherwise) -- the .widths of
+        another call, or the maximum of several, so that batches share their columns; default: what these records
+        need.  pos=True adds the position on the hit's strand of every letter byte.  The tensors are torch's and
+        ready on torch's current stream; the call waits for the record check and the widths.  A malformed record is
+        refused (RnamotifError naming its index) before anything is written."""
+        import torch
+        if getattr(db, "_h", None) is None or not db._h:
+            raise ValueError("the database is closed")
+        if getattr(db, "_text", None) is None:
+            raise ValueError("the database was not made by database_from_tensor(): print its hits and use bin/rmfmt -a")
+        if not isinstance(hits, torch.Tensor):
+            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
+        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{self.device}")
+        if hits.dtype != torch.int32:
+            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
+        stride = self.descr.hit_stride
+        if hits.ndim != 2 or int(hits.shape[1]) != stride:
+            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this scanner's descriptor are needed")
+        if letters is None and db.alphabet is not None:
+            letters = alphabet_letters(db.alphabet)
+        if letters is not None and len(letters) != 256:
+            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
+        fill = bytes(fill)
+        if len(fill) != 3:
+            raise ValueError(f"fill: 3 bytes (gap, separator, empty) are needed, not {len(fill)}")
+        hits = hits.contiguous()
+        n = int(hits.shape[0])
+        dev = torch.device("cuda", self.device)
+        L = lib()
+        err = C.create_string_buffer(_ERRLEN)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        i32p = C.POINTER(C.c_int32)
+        n_cols, row_bytes = C.c_int32(0), C.c_int64(0)
+        need, right = np.zeros(102, dtype=np.int32), np.zeros(102, dtype=np.uint8)
+        # (given widths: the shape of no record, for the columns and their directions; the fill call holds the widths
+        # to the records)
+        _check(L.rma_hit_alignment_shape(self._h, db._h, hits.data_ptr() if n and widths is None else None, n if widths is None else 0,
+                                         C.byref(n_cols), need.ctypes.data_as(i32p), right.ctypes.data, C.byref(row_bytes), stream,
+                                         err, _ERRLEN), err)
+        nc = int(n_cols.value)
+        if widths is None:
+            w = need[:nc].copy()
+        else:
+            w = np.ascontiguousarray(np.asarray(widths), dtype=np.int32)
+            if w.ndim != 1 or w.size != nc:
+                raise ValueError(f"widths: one per column, {nc}, not {w.size if w.ndim == 1 else tuple(w.shape)}")
+            if (w < 0).any():
+                raise ValueError("widths: a negative width")
+        al = HitAlignment(None, None, w, right[:nc], self.descr.names(), fill)
+        width = int(al.col.size)
+        al.rows = torch.empty((n, width), dtype=torch.uint8, device=dev)
+        if pos:
+            al.pos = torch.empty((n, width), dtype=torch.int32, device=dev)
+        if n:
+            _check(L.rma_hit_alignment(self._h, db._h, hits.data_ptr(), n, w.ctypes.data_as(i32p), letters, fill,
+                                       al.rows.data_ptr() if width else None, al.pos.data_ptr() if pos and width else None,
+                                       stream, err, _ERRLEN), err)
+            # (the records are read by kernels queued behind this stream: torch keeps their memory until those have run)
+            hits.record_stream(torch.cuda.current_stream(dev))
+        return al
 
     def prune(self, db: Database, hits, groups=None):
         """Which of these records the rmprune tool would keep, decided on the GPU (rma_prune_hits; the rule is

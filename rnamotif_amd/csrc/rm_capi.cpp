@@ -68,6 +68,30 @@ extern "C" const rma_efndata_t *rma_descr_efndata( const rma_descr_t *d ) { retu
 extern "C" int rma_descr_minlen( const rma_descr_t *d ) { return d->pr.descr->dminlen; }
 extern "C" int rma_descr_maxlen( const rma_descr_t *d ) { return d->pr.descr->dmaxlen; }
 
+// the fields of the "#RM descr" line, as the printer writes them
+extern "C" size_t rma_descr_names( const rma_descr_t *d, char *buf, size_t buflen )
+{
+	char	*text = nullptr;
+	size_t	len = 0;
+	FILE	*fp = open_memstream( &text, &len );
+	if( fp == nullptr )
+		return 0;
+	rma::HitPrinter( *d->pr.descr, fp ).header( fp );
+	fclose( fp );
+	std::string	line;
+	const char	*key = "#RM descr ", *at = text != nullptr ? strstr( text, key ) : nullptr;
+	if( at != nullptr ){
+		at += strlen( key );
+		line.assign( at, strcspn( at, "\n" ) );
+	}
+	free( text );
+	if( buf != nullptr && buflen > 0 ){
+		strncpy( buf, line.c_str(), buflen - 1 );
+		buf[ buflen - 1 ] = '\0';
+	}
+	return line.size();
+}
+
 extern "C" void rma_program_info( const rma_program_t *p, int32_t info[ 8 ] )
 {
 	info[ 0 ] = p->n_elems;

@@ -41,6 +41,7 @@
 #include "rm_dbpack_dev.h"
 #include "rm_hitwin_dev.h"
 #include "rm_hitstruct_dev.h"
+#include "rm_hitalign_dev.h"
 #include "rm_prune_dev.h"
 #include "rm_fasta_dev_kernels.h"
 #include "rm_stream.h"
@@ -1497,6 +1498,132 @@ extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const 
 			sc->d_hs_carry, tab, codes, out, c0 + cn == n_hits, st ) );
 		HIPCHK( rma::hit_carry_add( sc->d_hs_carry, s->d_off + cn, st ) );
 	}
+	return stream_after( caller, st, err, errlen );
+}
+
+// ---------------------------------------------------------------- hit records as an alignment
+// rma_hit_alignment_shape() / rma_hit_alignment(): the record check of rm_hitwin_dev.hip over all records, then the
+// widths and fill kernels of rm_hitalign_dev.hip in chunks of HW_CHUNK records, on the stream of the scanner's span
+// scratch, behind the caller's stream and, when something was written, ahead of what the caller queues next.  The
+// call's 102 width words lie where that scratch keeps a chunk's window lengths, which neither kernel needs.
+namespace {
+
+// Every record checked on the device and the widths of the columns reduced over all of them into need[ HA_MAX_COLS ]
+// (n_hits > 0, hit_structures_args has passed): one synchronisation.
+int hit_alignment_widths( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, void *stream, int32_t *need,
+	char *err, size_t errlen )
+{
+	rma::HitWindowScratch	*s = sc->hs_win;
+	hipStream_t	st = s->stream;
+	const int	stride = rma_hit_stride( &sc->prog );
+	const rma::HitWinShape	shape = rma::hitwin_shape( sc->prog );
+	int32_t	*d_w = reinterpret_cast<int32_t *>( s->d_len ), *h_w = reinterpret_cast<int32_t *>( s->h_off );
+	// behind the caller's work on its stream (the records) and the database's tables
+	if( stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( d_w, 0, rma::HA_MAX_COLS * sizeof( int32_t ), st ) );
+	HIPCHK( rma::hit_spans( d_hits, n_hits, stride, shape, db->d_slen, db->d_text_start, db->n_seq, nullptr, nullptr, nullptr, s->d_bad, st ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
+		HIPCHK( rma::hit_align_widths( d_hits + c0 * stride, std::min( HW_CHUNK, n_hits - c0 ), stride, shape, d_w, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( h_w, d_w, rma::HA_MAX_COLS * sizeof( int32_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( s->h_bad[ 0 ] != ~0ull )
+		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), nullptr, "written", err, errlen );
+	memcpy( need, h_w, rma::HA_MAX_COLS * sizeof( int32_t ) );
+	return 0;
+}
+
+}	// namespace
+
+extern "C" int rma_hit_alignment_shape( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	int32_t *n_cols, int32_t *widths, uint8_t *right, int64_t *row_bytes, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_alignment_shape";
+	if( sc == nullptr || n_cols == nullptr || widths == nullptr || row_bytes == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "room for the shape" );
+		return 1;
+	}
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	int32_t	need[ rma::HA_MAX_COLS ];
+	memset( need, 0, sizeof( need ) );
+	if( n_hits > 0 && hit_alignment_widths( sc, db, d_hits, n_hits, stream, need, err, errlen ) )
+		return 1;
+	const int	nc = rma::hitalign_n_cols( rma::hitwin_shape( sc->prog ) );
+	*n_cols = nc;
+	if( right != nullptr )
+		rma::hitalign_directions( sc->prog, right );
+	int64_t	w = nc - 1;
+	for( int c = 0; c < rma::HA_MAX_COLS; c++ ){
+		widths[ c ] = c < nc ? need[ c ] : 0;
+		w += widths[ c ];
+	}
+	*row_bytes = w;
+	return 0;
+}
+
+extern "C" int rma_hit_alignment( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const int32_t *widths, const uint8_t *letters, const uint8_t *fill, uint8_t *d_rows, int32_t *d_pos,
+	void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_alignment";
+	if( sc == nullptr || widths == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "widths" );
+		return 1;
+	}
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	const int	nc = rma::hitalign_n_cols( rma::hitwin_shape( sc->prog ) );
+	for( int c = 0; c < nc; c++ )
+		if( widths[ c ] < 0 ){
+			snprintf( err, errlen, "%s: column %d: width %d: nothing written", who, c, widths[ c ] );
+			return 1;
+		}
+	static const uint8_t	tool_fill[ 3 ] = { '-', '|', '.' };
+	const rma::HitAlignLayout	lay = rma::hitalign_layout( sc->prog, widths, fill != nullptr ? fill : tool_fill );
+	const int64_t	W = lay.row_bytes;
+	if( n_hits == 0 )
+		return 0;
+	if( d_rows == nullptr || W > INT64_MAX / 16 / n_hits ){
+		snprintf( err, errlen, "%s: %lld rows of %lld bytes: bad arguments", who, ( long long )n_hits, ( long long )W );
+		return 1;
+	}
+	// the outputs: the caller's, each inside its allocation on the scanner's device
+	if( W > 0 && ( check_device_bytes( d_rows, sc->device, 0, n_hits * W, "the rows", err, errlen ) ||
+		( d_pos != nullptr && check_device_bytes( d_pos, sc->device, 0, n_hits * W * 4, "the positions", err, errlen ) ) ) )
+		return 1;
+	rma::HitWindowScratch	*s = sc->hs_win;
+	hipStream_t	st = s->stream, caller = static_cast<hipStream_t>( stream );
+	// the letters, as rma_hit_structures takes them: on their way ahead of the check, whose synchronisation leaves the
+	// page-locked copy free for the next call
+	const uint8_t	*tab = s->d_tab;
+	int	codes = 0;
+	if( letters != nullptr )
+		memcpy( s->h_tab, letters, 256 );
+	else if( db->default_table )
+		for( int b = 0; b < 256; b++ )
+			s->h_tab[ b ] = rma::hitwin_reader_letter( static_cast<unsigned char>( b ) );
+	else{
+		tab = db->d_table;
+		codes = 1;
+	}
+	if( tab == s->d_tab )
+		HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, st ) );
+	int32_t	need[ rma::HA_MAX_COLS ];
+	if( hit_alignment_widths( sc, db, d_hits, n_hits, stream, need, err, errlen ) )
+		return 1;
+	for( int c = 0; c < nc; c++ )
+		if( widths[ c ] < need[ c ] ){
+			snprintf( err, errlen, "%s: column %d: width %d given, the records need %d: nothing written", who, c, widths[ c ], need[ c ] );
+			return 1;
+		}
+	const int	stride = rma_hit_stride( &sc->prog );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
+		HIPCHK( rma::hit_align_fill( db->text, d_hits + c0 * stride, std::min( HW_CHUNK, n_hits - c0 ), stride, rma::hitwin_shape( sc->prog ), lay,
+			db->d_slen, db->d_text_start, tab, codes, d_rows + c0 * W, d_pos != nullptr ? d_pos + c0 * W : nullptr, st ) );
 	return stream_after( caller, st, err, errlen );
 }
 
