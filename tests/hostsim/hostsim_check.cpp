@@ -334,8 +334,11 @@ int main( int argc, char **argv )
 							HostSeq	hs{ buf.data() };
 							int16_t	bpbuf[ 97 ];
 							uint8_t	bcbuf[ 100 ];
-							const int	got = rme_site_energy( &dp, &T16, &hs, sh.data() + h * stride, k );
-							const int	got_c = rme_site_energy( &dp, &T16, &hs, sh.data() + h * stride, k, bpbuf, bcbuf, 96 );
+							// (calls over more than 15 helices: the instance with the large stacks, as rma_scan picks it)
+							const int	got = dp.efn_big ? rme_site_energy<HostSeq, 1>( &dp, &T16, &hs, sh.data() + h * stride, k ) :
+								rme_site_energy( &dp, &T16, &hs, sh.data() + h * stride, k );
+							const int	got_c = dp.efn_big ? rme_site_energy<HostSeq, 1>( &dp, &T16, &hs, sh.data() + h * stride, k, bpbuf, bcbuf, 96 ) :
+								rme_site_energy( &dp, &T16, &hs, sh.data() + h * stride, k, bpbuf, bcbuf, 96 );
 							const int	want = oh.data[ h * stride + n_cmp + k ];
 							n_efn++;
 							if( got != want || got_c != want ){
@@ -352,12 +355,17 @@ int main( int argc, char **argv )
 							if( dp.efn_sites[ k ].kind != RMA_EFN_KIND_EFN2 )
 								continue;
 							HostSeq	hs{ buf.data() };
-							const int	got = rme2_site_energy( &dp, pr.efn2.get(), &hs, sh.data() + h * stride, k );
+							int16_t	bpbuf[ 97 ];
+							uint8_t	bcbuf[ 100 ];
+							const int	got = dp.efn_big ? rme2_site_energy<HostSeq, 1>( &dp, pr.efn2.get(), &hs, sh.data() + h * stride, k ) :
+								rme2_site_energy( &dp, pr.efn2.get(), &hs, sh.data() + h * stride, k );
+							const int	got_c = dp.efn_big ? rme2_site_energy<HostSeq, 1>( &dp, pr.efn2.get(), &hs, sh.data() + h * stride, k, bpbuf, bcbuf, 96 ) :
+								rme2_site_energy( &dp, pr.efn2.get(), &hs, sh.data() + h * stride, k, bpbuf, bcbuf, 96 );
 							const int	want = oh.data[ h * stride + n_cmp + k ];
 							n_efn2++;
-							if( got != want ){
+							if( got != want || got_c != want ){
 								if( bad < 10 )
-									fprintf( stderr, "seq %d comp %d hit %lld efn2 site %d: oracle %d, device core %d\n", seq, comp, ( long long )h, k, want, got );
+									fprintf( stderr, "seq %d comp %d hit %lld efn2 site %d: oracle %d, device core %d, with cache %d\n", seq, comp, ( long long )h, k, want, got, got_c );
 								bad++;
 							}
 						}
@@ -376,6 +384,8 @@ int main( int argc, char **argv )
 			printf( " (%lld efn2 energies compared)", ( long long )n_efn2 );
 		if( n_efn > 0 )
 			printf( " (%lld efn energies compared)", ( long long )n_efn );
+		if( dp.efn_big )
+			printf( " (large energy stacks)" );
 		printf( "\n" );
 		return bad ? 1 : 0;
 	}catch( rma::Error &e ){
