@@ -423,6 +423,35 @@ def prune_groups(sids) -> np.ndarray:
     return np.asarray(ids, dtype=np.int32)
 
 
+def _record_args(db, hits, device, stride, whose, text_hint, letters=None):
+    """What every call over records on the GPU does first.  db: open and, with text_hint (what to do instead), made
+    from a tensor; hits: an int32 CUDA tensor [n, stride] on `device` (None: the device of db's scanner), records of
+    the descriptor of `whose` ("scanner", "replay"); letters: 256 bytes, default db's alphabet= (calls that read text).
+    Returns (hits contiguous, n, the torch device, torch's current stream on it, letters)."""
+    import torch
+    if getattr(db, "_h", None) is None or not db._h:
+        raise ValueError("the database is closed")
+    if text_hint is not None and getattr(db, "_text", None) is None:
+        raise ValueError("the database was not made by database_from_tensor(): " + text_hint)
+    if not isinstance(hits, torch.Tensor):
+        raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
+    if device is None:
+        device = db.scanner.device
+    if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != device:
+        raise ValueError(f"hits is on {hits.device}: the database is on cuda:{device}")
+    if hits.dtype != torch.int32:
+        raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
+    if hits.ndim != 2 or int(hits.shape[1]) != stride:
+        raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this {whose}'s descriptor are needed")
+    if text_hint is not None:
+        if letters is None and db.alphabet is not None:
+            letters = alphabet_letters(db.alphabet)
+        if letters is not None and len(letters) != 256:
+            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
+    dev = torch.device("cuda", device)
+    return hits.contiguous(), int(hits.shape[0]), dev, torch.cuda.current_stream(dev), letters
+
+
 class HitStructures:
     """Scanner.hit_structures()'s result: the windows of n records, base by base, as tensors on the scanner's device.
 
@@ -613,29 +642,11 @@ class Scanner:
         and ready on torch's current stream; the call waits once, for the total length.  A malformed record is refused
         (RnamotifError naming its index) before anything is written."""
         import torch
-        if getattr(db, "_h", None) is None or not db._h:
-            raise ValueError("the database is closed")
-        if getattr(db, "_text", None) is None:
-            raise ValueError("the database was not made by database_from_tensor(): replay it with batch() or pack()")
-        if not isinstance(hits, torch.Tensor):
-            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
-        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{self.device}")
-        if hits.dtype != torch.int32:
-            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
-        stride = self.descr.hit_stride
-        if hits.ndim != 2 or int(hits.shape[1]) != stride:
-            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this scanner's descriptor are needed")
-        if letters is None and db.alphabet is not None:
-            letters = alphabet_letters(db.alphabet)
-        if letters is not None and len(letters) != 256:
-            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
-        hits = hits.contiguous()
-        n = int(hits.shape[0])
-        dev = torch.device("cuda", self.device)
+        hits, n, dev, cur, letters = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner",
+                                                  "replay it with batch() or pack()", letters)
         L = lib()
         err = C.create_string_buffer(_ERRLEN)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = cur.cuda_stream
         total = C.c_int64(0)
         if n:
             _check(L.rma_hit_structures_size(self._h, db._h, hits.data_ptr(), n, stream, C.byref(total), err, _ERRLEN), err)
@@ -647,7 +658,7 @@ class Scanner:
                                     st.lo.data_ptr() if n else None, st.base.data_ptr() if t else None,
                                     st.elem.data_ptr() if t else None, st.mate.data_ptr() if t else None, stream, err, _ERRLEN), err)
         # (the records are read by kernels queued behind this stream: torch keeps their memory until those have run)
-        hits.record_stream(torch.cuda.current_stream(dev))
+        hits.record_stream(cur)
         return st
 
     def align(self, db: Database, hits, letters: Optional[bytes] = None, widths=None, fill: bytes = b"-|.", pos: bool = False) -> HitAlignment:
@@ -663,32 +674,14 @@ class Scanner:
         ready on torch's current stream; the call waits for the record check and the widths.  A malformed record is
         refused (RnamotifError naming its index) before anything is written."""
         import torch
-        if getattr(db, "_h", None) is None or not db._h:
-            raise ValueError("the database is closed")
-        if getattr(db, "_text", None) is None:
-            raise ValueError("the database was not made by database_from_tensor(): print its hits and use bin/rmfmt -a")
-        if not isinstance(hits, torch.Tensor):
-            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
-        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{self.device}")
-        if hits.dtype != torch.int32:
-            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
-        stride = self.descr.hit_stride
-        if hits.ndim != 2 or int(hits.shape[1]) != stride:
-            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this scanner's descriptor are needed")
-        if letters is None and db.alphabet is not None:
-            letters = alphabet_letters(db.alphabet)
-        if letters is not None and len(letters) != 256:
-            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
+        hits, n, dev, cur, letters = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner",
+                                                  "print its hits and use bin/rmfmt -a", letters)
         fill = bytes(fill)
         if len(fill) != 3:
             raise ValueError(f"fill: 3 bytes (gap, separator, empty) are needed, not {len(fill)}")
-        hits = hits.contiguous()
-        n = int(hits.shape[0])
-        dev = torch.device("cuda", self.device)
         L = lib()
         err = C.create_string_buffer(_ERRLEN)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = cur.cuda_stream
         i32p = C.POINTER(C.c_int32)
         n_cols, row_bytes = C.c_int32(0), C.c_int64(0)
         need, right = np.zeros(102, dtype=np.int32), np.zeros(102, dtype=np.uint8)
@@ -716,7 +709,7 @@ class Scanner:
                                        al.rows.data_ptr() if width else None, al.pos.data_ptr() if pos and width else None,
                                        stream, err, _ERRLEN), err)
             # (the records are read by kernels queued behind this stream: torch keeps their memory until those have run)
-            hits.record_stream(torch.cuda.current_stream(dev))
+            hits.record_stream(cur)
         return al
 
     def prune(self, db: Database, hits, groups=None):
@@ -730,29 +723,15 @@ class Scanner:
         (prune_groups(db.sids)), default: every entry its own.  The call waits once, for the record check.  A
         malformed record is refused (RnamotifError naming its index)."""
         import torch
-        if getattr(db, "_h", None) is None or not db._h:
-            raise ValueError("the database is closed")
-        if not isinstance(hits, torch.Tensor):
-            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
-        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{self.device}")
-        if hits.dtype != torch.int32:
-            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
-        stride = self.descr.hit_stride
-        if hits.ndim != 2 or int(hits.shape[1]) != stride:
-            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this scanner's descriptor are needed")
+        hits, n, dev, stream, _ = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner", None)
         g = None
         if groups is not None:
             g = np.ascontiguousarray(np.asarray(groups), dtype=np.int32)
             if g.ndim != 1 or g.size != db.n_seqs:
                 raise ValueError(f"groups: one per entry, {db.n_seqs}, not {g.size if g.ndim == 1 else tuple(g.shape)}")
-        hits = hits.contiguous()
-        n = int(hits.shape[0])
-        dev = torch.device("cuda", self.device)
         keep = torch.empty(n, dtype=torch.bool, device=dev)
         if n:
             err = C.create_string_buffer(_ERRLEN)
-            stream = torch.cuda.current_stream(dev)
             _check(lib().rma_prune_hits(self._h, db._h, hits.data_ptr(), n,
                                         g.ctypes.data_as(C.POINTER(C.c_int32)) if g is not None else None,
                                         keep.data_ptr(), stream.cuda_stream, err, _ERRLEN), err)
@@ -889,34 +868,15 @@ class Replay:
         -> alphabet[i] as the readers take it, anything else n), else the readers' letters.  Runs behind the work
         queued on torch's current stream.  Returns the number printed, or (that number, np.bool_ mask of the
         records printed) with accepted=True."""
-        import torch
-        if getattr(db, "_h", None) is None or not db._h:
-            raise ValueError("the database is closed")
-        if getattr(db, "_text", None) is None:
-            raise ValueError("the database was not made by database_from_tensor(): replay it with batch() or pack()")
-        if not isinstance(hits, torch.Tensor):
-            raise TypeError(f"hits is a {type(hits).__name__}, not a torch.Tensor")
-        device = db.scanner.device
-        if hits.device.type != "cuda" or (hits.device.index if hits.device.index is not None else torch.cuda.current_device()) != device:
-            raise ValueError(f"hits is on {hits.device}: the database is on cuda:{device}")
-        if hits.dtype != torch.int32:
-            raise TypeError(f"hits is {hits.dtype}: int32 records are needed")
-        stride = self.descr.hit_stride
-        if hits.ndim != 2 or int(hits.shape[1]) != stride:
-            raise ValueError(f"hits has shape {tuple(hits.shape)}: [n, {stride}] records of this replay's descriptor are needed")
-        hits = hits.contiguous()
-        n = int(hits.shape[0])
-        if letters is None and db.alphabet is not None:
-            letters = alphabet_letters(db.alphabet)
-        if letters is not None and len(letters) != 256:
-            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
+        hits, n, _, cur, letters = _record_args(db, hits, None, self.descr.hit_stride, "replay",
+                                                "replay it with batch() or pack()", letters)
         for what, names in (("sids", sids), ("sdefs", sdefs)):
             if names is not None and len(names) != db.n_seqs:
                 raise ValueError(f"{what}: one per entry, {db.n_seqs}, not {len(names)}")
         mask = np.zeros(max(n, 1), dtype=np.uint8)
         printed = C.c_int64()
         err = C.create_string_buffer(_ERRLEN)
-        stream = torch.cuda.current_stream(hits.device).cuda_stream
+        stream = cur.cuda_stream
         _check(lib().rma_replay_device(self._h, db._h, hits.data_ptr() if n else None, n, letters,
                                        _cstr_array(sids) if sids is not None else None,
                                        _cstr_array(sdefs) if sdefs is not None else None, stream, C.byref(printed),

@@ -24,7 +24,7 @@ struct rma_replay {
 	bool	own_fp;
 	rma::Replayer	*rp;
 	rma::SearchStats	st;
-	rma::HitWindowScratch	*dev = nullptr;	// rma_replay_device's buffers (rm_scanner.cpp), made on its first call
+	rma::HitWindowScratch	*dev = nullptr;	// rma_replay_device's buffers (rm_hitpost.cpp), made on its first call
 };
 
 static int set_err( char *err, size_t errlen, const char *msg )

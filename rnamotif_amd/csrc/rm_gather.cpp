@@ -21,18 +21,9 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include "rm_hitsort_dev.h"
-#include "rnamotif_amd.h"
+#include "rm_scanner_impl.h"
 
-// rm_scanner.cpp
-int	rma_scanner_device( const rma_scanner_t *sc );
-hipStream_t	rma_scanner_stream( const rma_scanner_t *sc );
-int	rma_scanner_stride( const rma_scanner_t *sc );
-void	rma_scanner_last( const rma_scanner_t *sc, const int32_t **d_hits, int64_t *n );
-enum { RMA_LAST_NONE = 0, RMA_LAST_ON_DEVICE, RMA_LAST_ON_HOST };
-int	rma_scanner_last_state( const rma_scanner_t *sc );	// where the last scan's ordered records are
-bool	rma_scanner_last_relabelled( const rma_scanner_t *sc );
-void	rma_scanner_set_relabelled( rma_scanner_t *sc );
+enum { RMA_LAST_NONE = 0, RMA_LAST_ON_DEVICE, RMA_LAST_ON_HOST };	// rma_scanner::last_state
 
 namespace {
 
@@ -143,8 +134,6 @@ struct rma_comm {
 	size_t	agreed_cap = 0;
 };
 
-#define HIPCHK( call )	do{ hipError_t e_ = ( call ); if( e_ != hipSuccess ){ \
-		snprintf( err, errlen, "%s: %s", #call, hipGetErrorString( e_ ) ); return 1; } }while( 0 )
 #define NCCLCHK( call )	do{ ncclResult_t r_ = ( call ); if( r_ != ncclSuccess ){ \
 		snprintf( err, errlen, "%s: %s", #call, R->GetErrorString( r_ ) ); return 1; } }while( 0 )
 // a call of the communicator's transport
@@ -253,8 +242,8 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 {
 	*hits = nullptr;
 	*n_hits = 0;
-	if( rma_scanner_device( sc ) != c->device ){
-		snprintf( err, errlen, "rma_gather_hits: the scanner is on device %d, the communicator on device %d", rma_scanner_device( sc ), c->device );
+	if( sc->device != c->device ){
+		snprintf( err, errlen, "rma_gather_hits: the scanner is on device %d, the communicator on device %d", sc->device, c->device );
 		return 1;
 	}
 	if( root < 0 || root >= c->world ){
@@ -262,21 +251,20 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 		return 1;
 	}
 	HIPCHK( hipSetDevice( c->device ) );
-	hipStream_t	s = rma_scanner_stream( sc );
-	const int	stride = rma_scanner_stride( sc );
-	const int32_t	*d_mine = nullptr;
-	int64_t	n_mine = 0;
-	rma_scanner_last( sc, &d_mine, &n_mine );
+	hipStream_t	s = sc->stream;
+	const int	stride = sc->dprog.hit_stride;
+	const int32_t	*d_mine = sc->d_last;
+	const int64_t	n_mine = sc->n_last;
 	// What this rank can say before anything is exchanged.  A rank that cannot take part still goes through the
 	// count exchange -- with a flag -- so that no peer is left waiting in a collective it never joins.
 	std::string	trouble;
-	if( rma_scanner_last_state( sc ) == RMA_LAST_ON_HOST )
+	if( sc->last_state == RMA_LAST_ON_HOST )
 		trouble = "rma_gather_hits: the last scan's records were ordered on the host and are not in HBM (end the scan with rma_scan_end_on_device())";
 	else if( n_mine > 0 && ( global_index == nullptr || n_index <= 0 ) )
 		trouble = "rma_gather_hits: " + std::to_string( ( long long )n_mine ) + " records and no entry numbers";
 	// word 0 of every record: the entry's number in the whole database -- once per scan (a second gather of the same
 	// records finds them relabelled)
-	if( trouble.empty() && n_mine > 0 && !rma_scanner_last_relabelled( sc ) ){
+	if( trouble.empty() && n_mine > 0 && !sc->last_relabelled ){
 		hipError_t	e = hipSuccess;
 		if( size_t( n_index ) > c->index_cap ){
 			e = hipStreamSynchronize( s );
@@ -293,7 +281,7 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 		if( e == hipSuccess )
 			e = rma::relabel_entries( const_cast<int32_t *>( d_mine ), n_mine, stride, c->d_index, n_index, s );
 		if( e == hipSuccess )
-			rma_scanner_set_relabelled( sc );
+			sc->last_relabelled = true;
 		else
 			trouble = std::string( "rma_gather_hits: entry numbers: " ) + hipGetErrorString( e );
 	}

@@ -1,5 +1,5 @@
 // rm_hitalign_dev.h -- hit records laid into the columns of an alignment on the device (rma_hit_alignment_shape,
-// rma_hit_alignment, rm_scanner.cpp).  The rule is rm_hitalign.h's, shared with the host; the record check is
+// rma_hit_alignment, rm_hitpost.cpp).  The rule is rm_hitalign.h's, shared with the host; the record check is
 // rma_hit_span_kernel's (rm_hitwin_dev.hip), run before either kernel.
 //
 //   rma_hit_widths_kernel  a wave takes records in turn, lane e holding columns e and 64 + e -- two registers cover

@@ -1,0 +1,649 @@
+// rm_hitpost.cpp -- the calls of the C ABI (include/rnamotif_amd.h) that consume hit records already on the device,
+// on the host: rma_hit_windows (the device half of rma_replay_device), rma_hit_structures, rma_hit_alignment and
+// rma_prune_hits.  Their kernels are rm_hitwin_dev.hip, rm_hitstruct_dev.hip, rm_hitalign_dev.hip and rm_prune_dev.hip.
+// Of a scan they need nothing: a scanner's program and device, a database's tables and text (rm_scanner_impl.h), and
+// scratch of their own.  What they all do first is written once:
+//   record_call_args    the database, the records and the device refused or accepted
+//   letters_on_device   the table the window bytes go through
+//   check_records       behind the caller's stream, the bad-record word reset, every record judged by the span kernel
+#include <algorithm>
+#include <cstring>
+#include <functional>
+#include <vector>
+#include "rm_scanner_impl.h"
+#include "rm_hitpost.h"
+#include "rm_hitwin_dev.h"
+#include "rm_hitstruct_dev.h"
+#include "rm_hitalign_dev.h"
+
+namespace {
+// records of a call go through the kernels HW_CHUNK at a time; windows come to the host (rma_hit_windows) in pieces
+// of at most HW_PIECE_WINDOW bytes of windows and HW_PIECE_RECORDS bytes of records (a longer window comes alone)
+constexpr int64_t	HW_CHUNK = int64_t( 1 ) << 17;
+constexpr int64_t	HW_PIECE_WINDOW = int64_t( 16 ) << 20, HW_PIECE_RECORDS = int64_t( 8 ) << 20;
+
+// *p has room for `want` bytes, device or page-locked memory: what is there, or a new piece a quarter larger
+hipError_t room( void **p, size_t *cap, size_t want, bool host )
+{
+	if( *cap >= want )
+		return hipSuccess;
+	if( *p != nullptr )
+		( void )( host ? hipHostFree( *p ) : hipFree( *p ) );
+	*p = nullptr;
+	*cap = 0;
+	want += want / 4;
+	hipError_t	e = host ? hipHostMalloc( p, want, hipHostMallocDefault ) : hipMalloc( p, want );
+	if( e == hipSuccess )
+		*cap = want;
+	return e;
+}
+hipError_t dev_room( void **p, size_t *cap, size_t want ) { return room( p, cap, want, false ); }
+hipError_t host_room( void **p, size_t *cap, size_t want ) { return room( p, cap, want, true ); }
+}	// namespace
+
+// the two fixed blocks (rm_hitpost.h), the scan's room, windows; page-locked: records, windows
+struct rma::HitWindowScratch : rma::HitWinFixed {
+	int	device = -1;
+	hipStream_t	stream = nullptr;
+	void	*d_fixed = nullptr, *d_tmp = nullptr, *d_win = nullptr;
+	size_t	fixed_bytes = 0, tmp_bytes = 0, win_cap = 0;
+	void	*h_fixed = nullptr, *h_rec = nullptr, *h_win = nullptr;
+	size_t	h_fixed_bytes = 0, rec_cap = 0, h_win_cap = 0;
+	std::vector<int64_t>	piece_off;
+};
+
+void rma::hitwin_scratch_free( HitWindowScratch *s )
+{
+	if( s == nullptr )
+		return;
+	( void )hipSetDevice( s->device );
+	if( s->stream != nullptr )
+		( void )hipStreamSynchronize( s->stream );
+	for( void *p : { s->d_fixed, s->d_tmp, s->d_win } )
+		if( p != nullptr )
+			( void )hipFree( p );
+	for( void *p : { s->h_fixed, s->h_rec, s->h_win } )
+		if( p != nullptr )
+			( void )hipHostFree( p );
+	if( s->stream != nullptr )
+		( void )hipStreamDestroy( s->stream );
+	delete s;
+}
+
+// What a scanner keeps for these calls, made by the first that needs it.
+struct rma::HitPost {
+	// rma_hit_structures, rma_hit_alignment: the span scratch and stream, the program's table and, behind it, the running total
+	HitWindowScratch	*win = nullptr;
+	HitStructTable	*d_hs_table = nullptr;
+	int64_t	*d_hs_carry = nullptr;
+	// rma_prune_hits: the program's table (two result words behind it), the keys, flags and block list of a call, the
+	// entries' name groups, two page-locked words, and the event behind the last call's kernels
+	PruneTable	*d_pr_table = nullptr;
+	void	*d_pr = nullptr, *d_pr_groups = nullptr, *h_pr = nullptr;
+	size_t	pr_bytes = 0, pr_groups_bytes = 0, h_pr_bytes = 0;
+	hipEvent_t	pr_done = nullptr;
+};
+
+// (the scanner's device is current; the scratch stream is synchronised before anything is freed)
+void rma::hitpost_free( HitPost *p )
+{
+	if( p == nullptr )
+		return;
+	hitwin_scratch_free( p->win );
+	( void )hipFree( p->d_hs_table );		// (the running total lies behind the table)
+	( void )hipFree( p->d_pr_table );
+	( void )hipFree( p->d_pr );
+	( void )hipFree( p->d_pr_groups );
+	( void )hipHostFree( p->h_pr );
+	if( p->pr_done )
+		( void )hipEventDestroy( p->pr_done );
+	delete p;
+}
+
+static rma::HitPost &post_of( rma_scanner_t *sc )
+{
+	if( sc->post == nullptr )
+		sc->post = new rma::HitPost;
+	return *sc->post;
+}
+
+static int scratch_on( rma::HitWindowScratch **scratch, int device, char *err, size_t errlen )
+{
+	if( *scratch != nullptr && ( *scratch )->device == device )
+		return 0;
+	rma::hitwin_scratch_free( *scratch );
+	*scratch = new rma::HitWindowScratch;
+	rma::HitWindowScratch	*s = *scratch;
+	s->device = device;
+	HIPCHK( hipStreamCreateWithFlags( &s->stream, hipStreamNonBlocking ) );
+	HIPCHK( dev_room( &s->d_fixed, &s->fixed_bytes, s->carve_dev( nullptr, size_t( HW_CHUNK ) ) ) );
+	s->carve_dev( s->d_fixed, size_t( HW_CHUNK ) );
+	size_t	tmp = 0;
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, HW_CHUNK + 1, nullptr, &tmp, s->stream ) );
+	HIPCHK( dev_room( &s->d_tmp, &s->tmp_bytes, std::max<size_t>( tmp, 256 ) ) );
+	HIPCHK( host_room( &s->h_fixed, &s->h_fixed_bytes, s->carve_host( nullptr, size_t( HW_CHUNK ) ) ) );
+	s->carve_host( s->h_fixed, size_t( HW_CHUNK ) );
+	return 0;
+}
+
+// ---------------------------------------------------------------- what every call does first
+namespace {
+
+struct RecordCall {
+	const char	*who;		// the prefix of every refusal
+	int	device;			// the scanner's, which must be the database's; < 0: a call without a scanner, which takes the
+					// database's and touches no device for no records (rma_replay_device)
+	bool	device_db;		// the database must be one rma_db_create_device() made, not yet destroyed, whose text is read
+	int64_t	most;			// records: more would overflow a byte count of the call
+};
+
+// The single argument check.  Passed with n_hits > 0: the database's device is current, the n_hits records of
+// `stride` words lie inside their allocation on it.
+int record_call_args( const RecordCall &c, const rma_db *db, int stride, const int32_t *d_hits, int64_t n_hits, char *err, size_t errlen )
+{
+	if( c.device_db && !rma::is_device_db( db ) ){
+		snprintf( err, errlen, "%s: the database (%p) was not made by rma_db_create_device() or has been destroyed", c.who,
+			static_cast<const void *>( db ) );
+		return 1;
+	}
+	if( n_hits < 0 || ( n_hits > 0 && d_hits == nullptr ) || n_hits > c.most ){
+		snprintf( err, errlen, "%s: %lld records: bad arguments", c.who, ( long long )n_hits );
+		return 1;
+	}
+	if( c.device >= 0 && db->device != c.device ){
+		snprintf( err, errlen, "%s: the database is on device %d, the scanner on device %d", c.who, db->device, c.device );
+		return 1;
+	}
+	if( n_hits == 0 && c.device < 0 )
+		return 0;
+	HIPCHK( hipSetDevice( db->device ) );
+	if( n_hits == 0 )
+		return 0;
+	if( rma::check_device_bytes( d_hits, db->device, 0, n_hits * stride * 4, "the records", err, errlen ) )
+		return 1;
+	if( c.device_db && db->text_hi > db->text_lo &&
+		rma::check_device_bytes( db->text, db->device, db->text_lo, db->text_hi, "the database's text", err, errlen ) )
+		return 1;
+	return 0;
+}
+
+// The letters of window bytes: the caller's 256, the readers', or the letters of the database's own codes (*codes = 1,
+// its table on the device); the first two on their way to the scratch's table on its stream.
+int letters_on_device( rma::HitWindowScratch *s, const rma_db *db, const uint8_t *letters, const uint8_t **tab, int *codes, char *err, size_t errlen )
+{
+	*tab = s->d_tab;
+	*codes = 0;
+	if( letters != nullptr )
+		memcpy( s->h_tab, letters, 256 );
+	else if( db->default_table )
+		for( int b = 0; b < 256; b++ )
+			s->h_tab[ b ] = rma::hitwin_reader_letter( static_cast<unsigned char>( b ) );
+	else{
+		*tab = db->d_table;
+		*codes = 1;
+		return 0;
+	}
+	HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, s->stream ) );
+	return 0;
+}
+
+// The record check, queued on the scratch's stream behind the caller's work on its stream (the records) and the
+// database's tables: *d_bad -- the least index of a bad record -- reset, zero_bytes bytes at `zero` (the call's running
+// result; may be null) cleared, and, with `whole`, every record judged by the span kernel, which writes nothing else.
+// The caller queues its own kernels, copies *d_bad back with its result and synchronises once.
+int check_records( rma::HitWindowScratch *s, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits, int64_t n_hits,
+	void *stream, bool whole, void *zero, size_t zero_bytes, char *err, size_t errlen )
+{
+	hipStream_t	st = s->stream;
+	if( rma::stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
+	if( zero != nullptr )
+		HIPCHK( hipMemsetAsync( zero, 0, zero_bytes, st ) );
+	if( whole )
+		HIPCHK( rma::hit_spans( d_hits, n_hits, rma_hit_stride( &prog ), rma::hitwin_shape( prog ), db->d_slen, db->d_text_start, db->n_seq,
+			nullptr, nullptr, nullptr, s->d_bad, st ) );
+	return 0;
+}
+
+}	// namespace
+
+// the words of a bad record, why it is bad; tab: the helix check as well (rma_hit_structures); nothing: "printed" or "written"
+static int bad_record( rma::HitWindowScratch *s, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits, int64_t h,
+	const rma::HitStructTable *tab, const char *nothing, char *err, size_t errlen )
+{
+	const int	stride = rma_hit_stride( &prog );
+	std::vector<int32_t>	w( static_cast<size_t>( stride ) );
+	HIPCHK( hipMemcpyAsync( w.data(), d_hits + h * stride, size_t( stride ) * 4, hipMemcpyDeviceToHost, s->stream ) );
+	HIPCHK( hipStreamSynchronize( s->stream ) );
+	int32_t	lo, hi;
+	int	which;
+	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
+	const int	r = tab != nullptr ? rma::hitstruct_check( w.data(), *tab, shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which ) :
+		rma::hitwin_span( w.data(), shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which );
+	if( r == rma::HW_ENTRY )
+		snprintf( err, errlen, "record %lld: entry %d outside [0, %d): nothing %s", ( long long )h, w[ 0 ], db->n_seq, nothing );
+	else if( r == rma::HW_STRAND )
+		snprintf( err, errlen, "record %lld: strand %d, not 0 or 1: nothing %s", ( long long )h, w[ 1 ], nothing );
+	else if( r == rma::HS_HELIX ){
+		const int	first = tab->e[ which ].strand[ 0 ];
+		snprintf( err, errlen, "record %lld: element %d has length %d, element %d of the same helix length %d: nothing %s", ( long long )h,
+			which, w[ RMA_HIT_HDR + 4 * which + 1 ], first, w[ RMA_HIT_HDR + 4 * first + 1 ], nothing );
+	}
+	else if( r == rma::HW_EXTENT ){
+		const int	k = which < shape.n_elems ? RMA_HIT_HDR + 4 * which : which == shape.n_elems ? shape.ctx_off : shape.ctx_off + 2;
+		char	what[ 32 ];
+		if( which < shape.n_elems )
+			snprintf( what, sizeof( what ), "element %d", which );
+		else
+			snprintf( what, sizeof( what ), "the %s context", which == shape.n_elems ? "left" : "right" );
+		snprintf( err, errlen, "record %lld: %s at offset %d, length %d, outside entry %d's %d bases: nothing %s", ( long long )h,
+			what, w[ k ], w[ k + 1 ], w[ 0 ], db->h_slen[ size_t( w[ 0 ] ) ], nothing );
+	}else
+		snprintf( err, errlen, "record %lld: refused on the device, not on the host (records changed during the call?)", ( long long )h );
+	return 1;
+}
+
+// ---------------------------------------------------------------- windows of hits of device databases
+// The device half of rma_replay_device() (rm_capi.cpp has the replay): the records are checked and their windows
+// cut out of the database's text on the device (rm_hitwin_dev.hip), in chunks of HW_CHUNK records, and come to
+// the host in pieces.  One synchronisation learns a chunk's offsets (and, in the first chunk, whether some
+// record is bad), one per piece ends its copy.
+int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits,
+	int64_t n_hits, const uint8_t *letters, void *stream, const std::function<void( const rma::HitWindowPiece & )> &each,
+	char *err, size_t errlen )
+{
+	const int	stride = rma_hit_stride( &prog );
+	// (n_hits * stride * 4: the bytes of the records)
+	const RecordCall	call{ "rma_replay_device", -1, true, INT64_MAX / 4 / stride };
+	if( record_call_args( call, db, stride, d_hits, n_hits, err, errlen ) )
+		return 1;
+	if( n_hits == 0 )
+		return 0;
+	if( scratch_on( scratch, db->device, err, errlen ) )
+		return 1;
+	rma::HitWindowScratch	*s = *scratch;
+	hipStream_t	st = s->stream;
+	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	if( letters_on_device( s, db, letters, &tab, &codes, err, errlen ) )
+		return 1;
+	// every record checked before any text is read: all of them here when there is more than one chunk, else
+	// the first chunk's spans do it
+	if( check_records( s, db, prog, d_hits, n_hits, stream, n_hits > HW_CHUNK, nullptr, 0, err, errlen ) )
+		return 1;
+	const int64_t	piece_records = std::max<int64_t>( 1, HW_PIECE_RECORDS / ( 4 * stride ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		const int32_t	*ch = d_hits + c0 * stride;
+		HIPCHK( rma::hit_spans( ch, cn, stride, shape, db->d_slen, db->d_text_start, db->n_seq, s->d_lo, s->d_len, s->d_src,
+			s->d_bad, st ) );
+		size_t	tb = s->tmp_bytes;
+		HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, st ) );
+		HIPCHK( hipMemcpyAsync( s->h_off, s->d_off, size_t( cn + 1 ) * 8, hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipMemcpyAsync( s->h_lo, s->d_lo, size_t( cn ) * 4, hipMemcpyDeviceToHost, st ) );
+		if( c0 == 0 )
+			HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipStreamSynchronize( st ) );
+		if( c0 == 0 && *s->h_bad != ~0ull )
+			return bad_record( s, db, prog, d_hits, int64_t( *s->h_bad ), nullptr, "printed", err, errlen );
+		for( int64_t a = 0; a < cn; ){
+			int64_t	b = a + 1;
+			while( b < cn && b - a < piece_records && s->h_off[ b + 1 ] - s->h_off[ a ] <= HW_PIECE_WINDOW )
+				b++;
+			const int64_t	bytes = s->h_off[ b ] - s->h_off[ a ];
+			HIPCHK( dev_room( &s->d_win, &s->win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
+			HIPCHK( host_room( &s->h_win, &s->h_win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
+			HIPCHK( host_room( &s->h_rec, &s->rec_cap, size_t( b - a ) * stride * 4 ) );
+			HIPCHK( rma::hit_gather( db->text, b - a, s->d_src + a, s->d_off + a, tab, codes, static_cast<uint8_t *>( s->d_win ), st ) );
+			HIPCHK( hipMemcpyAsync( s->h_rec, ch + a * stride, size_t( b - a ) * stride * 4, hipMemcpyDeviceToHost, st ) );
+			if( bytes > 0 )
+				HIPCHK( hipMemcpyAsync( s->h_win, s->d_win, size_t( bytes ), hipMemcpyDeviceToHost, st ) );
+			HIPCHK( hipStreamSynchronize( st ) );
+			s->piece_off.resize( size_t( b - a + 1 ) );
+			for( int64_t i = a; i <= b; i++ )
+				s->piece_off[ size_t( i - a ) ] = s->h_off[ i ] - s->h_off[ a ];
+			each( rma::HitWindowPiece{ static_cast<const int32_t *>( s->h_rec ), c0 + a, b - a, static_cast<const char *>( s->h_win ),
+				s->piece_off.data(), s->h_lo + a, db->h_slen.data(), db->n_seq } );
+			a = b;
+		}
+	}
+	return 0;
+}
+
+// ---------------------------------------------------------------- hit structures as device tensors
+// rma_hit_structures_size() / rma_hit_structures(): the spans, sources and offsets of rm_hitwin_dev.hip in chunks of
+// HW_CHUNK records, the helix check and the fill kernel of rm_hitstruct_dev.hip.  The outputs are the caller's and are
+// written in place: a chunk's offsets count from its first record (the scan's), the window bytes of the chunks
+// before it wait in a word on the device (*d_hs_carry), so no chunk needs the host.  The work runs on a stream of the
+// scanner's own, behind the caller's stream and, when something was written, ahead of what the caller queues next.
+namespace {
+
+// What the calls for structures and alignments do first: the database, the records and the scanner's scratch (made on
+// first use).  n_hits == 0 needs none of it.
+int hit_structures_args( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, const char *who, char *err, size_t errlen )
+{
+	const int	stride = rma_hit_stride( &sc->prog );
+	// (n_hits * stride * 4 bytes of records, ( n_hits + 1 ) * 8 of offsets)
+	const RecordCall	call{ who, sc->device, true, INT64_MAX / 16 / stride };
+	if( record_call_args( call, db, stride, d_hits, n_hits, err, errlen ) )
+		return 1;
+	if( n_hits == 0 )
+		return 0;
+	rma::HitPost	&p = post_of( sc );
+	if( scratch_on( &p.win, sc->device, err, errlen ) )
+		return 1;
+	if( p.d_hs_table == nullptr ){
+		// the program's table and, behind it, the running total
+		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
+		const size_t	at = ( sizeof( rma::HitStructTable ) + 7 ) & ~size_t( 7 );
+		void	*m = nullptr;
+		HIPCHK( hipMalloc( &m, at + sizeof( int64_t ) ) );
+		p.d_hs_table = static_cast<rma::HitStructTable *>( m );
+		p.d_hs_carry = reinterpret_cast<int64_t *>( static_cast<char *>( m ) + at );
+		HIPCHK( hipMemcpy( p.d_hs_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
+	}
+	return 0;
+}
+
+// One chunk's spans, sources and offsets into the scratch; *bad as hit_spans
+int hit_structures_spans( rma_scanner_t *sc, const rma_db *db, const int32_t *ch, int64_t cn, unsigned long long *bad, char *err, size_t errlen )
+{
+	rma::HitWindowScratch	*s = sc->post->win;
+	HIPCHK( rma::hit_spans( ch, cn, rma_hit_stride( &sc->prog ), rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq,
+		s->d_lo, s->d_len, s->d_src, bad, s->stream ) );
+	size_t	tb = s->tmp_bytes;
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, s->stream ) );
+	return 0;
+}
+
+// Every record checked on the device and the window bytes counted (n_hits > 0, hit_structures_args has passed): one
+// synchronisation.  A call of one chunk leaves that chunk's spans in the scratch.
+int hit_structures_count( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, void *stream, int64_t *total,
+	char *err, size_t errlen )
+{
+	rma::HitPost	&p = *sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream;
+	const int	stride = rma_hit_stride( &sc->prog );
+	// d_bad[ 0 ]: the least index of a bad record, counted over the call; d_bad[ 2 ]: where the spans of a later chunk,
+	// which count from the chunk's first record, put theirs (the same records, already judged).  A call of one chunk
+	// has no pass over all records: the chunk's own spans judge them.
+	const bool	chunks = n_hits > HW_CHUNK;
+	if( check_records( s, db, sc->prog, d_hits, n_hits, stream, chunks, p.d_hs_carry, sizeof( int64_t ), err, errlen ) )
+		return 1;
+	HIPCHK( rma::hit_helix_check( d_hits, n_hits, stride, p.d_hs_table, s->d_bad, st ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		if( hit_structures_spans( sc, db, d_hits + c0 * stride, cn, chunks ? s->d_bad + 2 : s->d_bad, err, errlen ) )
+			return 1;
+		HIPCHK( rma::hit_carry_add( p.d_hs_carry, s->d_off + cn, st ) );
+	}
+	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.d_hs_carry, sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( s->h_bad[ 0 ] != ~0ull ){
+		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
+		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), &tab, "written", err, errlen );
+	}
+	*total = int64_t( s->h_bad[ 1 ] );
+	return 0;
+}
+
+}	// namespace
+
+extern "C" int rma_hit_structures_size( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	void *stream, int64_t *total, char *err, size_t errlen )
+{
+	*total = 0;
+	if( hit_structures_args( sc, db, d_hits, n_hits, "rma_hit_structures_size", err, errlen ) )
+		return 1;
+	return n_hits == 0 ? 0 : hit_structures_count( sc, db, d_hits, n_hits, stream, total, err, errlen );
+}
+
+extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, int64_t total, int64_t *d_off, int32_t *d_lo, uint8_t *d_base, int16_t *d_elem, int32_t *d_mate,
+	void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_structures";
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	if( total < 0 || total > INT64_MAX / 16 || d_off == nullptr || ( n_hits > 0 && d_lo == nullptr ) ||
+		( total > 0 && ( d_base == nullptr || d_elem == nullptr || d_mate == nullptr ) ) ){
+		snprintf( err, errlen, "%s: %lld window bytes: bad arguments", who, ( long long )total );
+		return 1;
+	}
+	// the outputs: the caller's, each inside its allocation on the scanner's device
+	if( rma::check_device_bytes( d_off, sc->device, 0, ( n_hits + 1 ) * 8, "the offsets", err, errlen ) ||
+		( n_hits > 0 && rma::check_device_bytes( d_lo, sc->device, 0, n_hits * 4, "the first positions", err, errlen ) ) ||
+		( total > 0 && ( rma::check_device_bytes( d_base, sc->device, 0, total, "the bases", err, errlen ) ||
+			rma::check_device_bytes( d_elem, sc->device, 0, total * 2, "the elements", err, errlen ) ||
+			rma::check_device_bytes( d_mate, sc->device, 0, total * 12, "the mates", err, errlen ) ) ) )
+		return 1;
+	hipStream_t	caller = static_cast<hipStream_t>( stream );
+	int64_t	found = 0;
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	// the letters as rma_replay_device takes them, on their way ahead of the count, whose synchronisation leaves the
+	// page-locked copy free for the next call
+	if( n_hits > 0 && ( letters_on_device( sc->post->win, db, letters, &tab, &codes, err, errlen ) ||
+		hit_structures_count( sc, db, d_hits, n_hits, stream, &found, err, errlen ) ) )
+		return 1;
+	if( found != total ){
+		snprintf( err, errlen, "%s: the windows of the %lld records have %lld bytes, not the %lld of `total`: nothing written", who,
+			( long long )n_hits, ( long long )found, ( long long )total );
+		return 1;
+	}
+	if( n_hits == 0 ){
+		HIPCHK( hipMemsetAsync( d_off, 0, sizeof( int64_t ), caller ) );
+		return 0;
+	}
+	rma::HitPost	&p = *sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream;
+	const int	stride = rma_hit_stride( &sc->prog );
+	HIPCHK( hipMemsetAsync( p.d_hs_carry, 0, sizeof( int64_t ), st ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		const int32_t	*ch = d_hits + c0 * stride;
+		// (a call of one chunk: the count's spans are still there)
+		if( n_hits > HW_CHUNK && hit_structures_spans( sc, db, ch, cn, s->d_bad + 2, err, errlen ) )
+			return 1;
+		const rma::HitStructOut	out{ d_off + c0, d_lo + c0, d_base, d_elem, d_mate };
+		HIPCHK( rma::hit_struct_fill( db->text, ch, cn, stride, rma::hitwin_shape( sc->prog ), p.d_hs_table, s->d_lo, s->d_src, s->d_off,
+			p.d_hs_carry, tab, codes, out, c0 + cn == n_hits, st ) );
+		HIPCHK( rma::hit_carry_add( p.d_hs_carry, s->d_off + cn, st ) );
+	}
+	return rma::stream_after( caller, st, err, errlen );
+}
+
+// ---------------------------------------------------------------- hit records as an alignment
+// rma_hit_alignment_shape() / rma_hit_alignment(): the record check of rm_hitwin_dev.hip over all records, then the
+// widths and fill kernels of rm_hitalign_dev.hip in chunks of HW_CHUNK records, on the stream of the scanner's span
+// scratch, behind the caller's stream and, when something was written, ahead of what the caller queues next.  The
+// call's 102 width words lie where that scratch keeps a chunk's window lengths, which neither kernel needs.
+namespace {
+
+// Every record checked on the device and the widths of the columns reduced over all of them into need[ HA_MAX_COLS ]
+// (n_hits > 0, hit_structures_args has passed): one synchronisation.
+int hit_alignment_widths( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, void *stream, int32_t *need,
+	char *err, size_t errlen )
+{
+	rma::HitWindowScratch	*s = sc->post->win;
+	hipStream_t	st = s->stream;
+	const int	stride = rma_hit_stride( &sc->prog );
+	const rma::HitWinShape	shape = rma::hitwin_shape( sc->prog );
+	int32_t	*d_w = reinterpret_cast<int32_t *>( s->d_len ), *h_w = reinterpret_cast<int32_t *>( s->h_off );
+	if( check_records( s, db, sc->prog, d_hits, n_hits, stream, true, d_w, rma::HA_MAX_COLS * sizeof( int32_t ), err, errlen ) )
+		return 1;
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
+		HIPCHK( rma::hit_align_widths( d_hits + c0 * stride, std::min( HW_CHUNK, n_hits - c0 ), stride, shape, d_w, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( h_w, d_w, rma::HA_MAX_COLS * sizeof( int32_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( s->h_bad[ 0 ] != ~0ull )
+		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), nullptr, "written", err, errlen );
+	memcpy( need, h_w, rma::HA_MAX_COLS * sizeof( int32_t ) );
+	return 0;
+}
+
+}	// namespace
+
+extern "C" int rma_hit_alignment_shape( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	int32_t *n_cols, int32_t *widths, uint8_t *right, int64_t *row_bytes, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_alignment_shape";
+	if( sc == nullptr || n_cols == nullptr || widths == nullptr || row_bytes == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "room for the shape" );
+		return 1;
+	}
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	int32_t	need[ rma::HA_MAX_COLS ];
+	memset( need, 0, sizeof( need ) );
+	if( n_hits > 0 && hit_alignment_widths( sc, db, d_hits, n_hits, stream, need, err, errlen ) )
+		return 1;
+	const int	nc = rma::hitalign_n_cols( rma::hitwin_shape( sc->prog ) );
+	*n_cols = nc;
+	if( right != nullptr )
+		rma::hitalign_directions( sc->prog, right );
+	int64_t	w = nc - 1;
+	for( int c = 0; c < rma::HA_MAX_COLS; c++ ){
+		widths[ c ] = c < nc ? need[ c ] : 0;
+		w += widths[ c ];
+	}
+	*row_bytes = w;
+	return 0;
+}
+
+extern "C" int rma_hit_alignment( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const int32_t *widths, const uint8_t *letters, const uint8_t *fill, uint8_t *d_rows, int32_t *d_pos,
+	void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_alignment";
+	if( sc == nullptr || widths == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "widths" );
+		return 1;
+	}
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	const int	nc = rma::hitalign_n_cols( rma::hitwin_shape( sc->prog ) );
+	for( int c = 0; c < nc; c++ )
+		if( widths[ c ] < 0 ){
+			snprintf( err, errlen, "%s: column %d: width %d: nothing written", who, c, widths[ c ] );
+			return 1;
+		}
+	static const uint8_t	tool_fill[ 3 ] = { '-', '|', '.' };
+	const rma::HitAlignLayout	lay = rma::hitalign_layout( sc->prog, widths, fill != nullptr ? fill : tool_fill );
+	const int64_t	W = lay.row_bytes;
+	if( n_hits == 0 )
+		return 0;
+	if( d_rows == nullptr || W > INT64_MAX / 16 / n_hits ){
+		snprintf( err, errlen, "%s: %lld rows of %lld bytes: bad arguments", who, ( long long )n_hits, ( long long )W );
+		return 1;
+	}
+	// the outputs: the caller's, each inside its allocation on the scanner's device
+	if( W > 0 && ( rma::check_device_bytes( d_rows, sc->device, 0, n_hits * W, "the rows", err, errlen ) ||
+		( d_pos != nullptr && rma::check_device_bytes( d_pos, sc->device, 0, n_hits * W * 4, "the positions", err, errlen ) ) ) )
+		return 1;
+	rma::HitWindowScratch	*s = sc->post->win;
+	hipStream_t	st = s->stream, caller = static_cast<hipStream_t>( stream );
+	// the letters, as rma_hit_structures takes them: on their way ahead of the check, whose synchronisation leaves the
+	// page-locked copy free for the next call
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	if( letters_on_device( s, db, letters, &tab, &codes, err, errlen ) )
+		return 1;
+	int32_t	need[ rma::HA_MAX_COLS ];
+	if( hit_alignment_widths( sc, db, d_hits, n_hits, stream, need, err, errlen ) )
+		return 1;
+	for( int c = 0; c < nc; c++ )
+		if( widths[ c ] < need[ c ] ){
+			snprintf( err, errlen, "%s: column %d: width %d given, the records need %d: nothing written", who, c, widths[ c ], need[ c ] );
+			return 1;
+		}
+	const int	stride = rma_hit_stride( &sc->prog );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
+		HIPCHK( rma::hit_align_fill( db->text, d_hits + c0 * stride, std::min( HW_CHUNK, n_hits - c0 ), stride, rma::hitwin_shape( sc->prog ), lay,
+			db->d_slen, db->d_text_start, tab, codes, d_rows + c0 * W, d_pos != nullptr ? d_pos + c0 * W : nullptr, st ) );
+	return rma::stream_after( caller, st, err, errlen );
+}
+
+// ---------------------------------------------------------------- rmprune's rule over records on the device
+// rma_prune_hits(): the kernels of rm_prune_dev.hip on the caller's stream.  The scratch -- the program's table, a
+// call's keys, flags and list of blocks, the entries' name groups -- is the scanner's, made on the first call and
+// grown; a later call on another stream waits for the kernels of the one before it (pr_done).  One wait, for two
+// words: the least index of a refused record and the number of blocks, which sizes the last launch.  The database
+// may be any: only its entry lengths are read.
+extern "C" int rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const int32_t *group_of_entry, uint8_t *d_keep, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_prune_hits";
+	if( sc == nullptr || db == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "database" );
+		return 1;
+	}
+	const int	stride = rma_hit_stride( &sc->prog );
+	const rma::PruneTable	tab = rma::prune_table( sc->prog );
+	const int	row = rma::prune_row_words( tab );
+	// (n_hits * 16 bytes of headers, n_hits * row * 4 of key rows, n_hits * stride * 4 of records; records without
+	// flags to write are refused as records without records)
+	const RecordCall	call{ who, sc->device, false, INT64_MAX / 16 / std::max( stride, row ) };
+	if( record_call_args( call, db, stride, d_keep != nullptr ? d_hits : nullptr, n_hits, err, errlen ) )
+		return 1;
+	if( n_hits == 0 )
+		return 0;
+	if( rma::check_device_bytes( d_keep, sc->device, 0, n_hits, "the keep flags", err, errlen ) )
+		return 1;
+	rma::HitPost	&p = post_of( sc );
+	hipStream_t	st = static_cast<hipStream_t>( stream );
+	if( p.d_pr_table == nullptr ){
+		const size_t	at = align256( sizeof( rma::PruneTable ) );
+		void	*m = nullptr;
+		HIPCHK( hipMalloc( &m, at + 256 ) );
+		p.d_pr_table = static_cast<rma::PruneTable *>( m );
+		HIPCHK( hipMemcpy( p.d_pr_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
+		HIPCHK( hipEventCreateWithFlags( &p.pr_done, hipEventDisableTiming ) );
+		HIPCHK( hipEventRecord( p.pr_done, st ) );
+	}
+	// behind the kernels of the call before this one (they read the scratch) and the database's tables
+	HIPCHK( hipStreamWaitEvent( st, p.pr_done, 0 ) );
+	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	const size_t	n = size_t( n_hits ), parts = size_t( rma::prune_parts( n_hits ) );
+	rma::PruneDev	pd;
+	HIPCHK( dev_room( &p.d_pr, &p.pr_bytes, rma::prune_carve( pd, nullptr, n, parts, size_t( row ) ) ) );
+	HIPCHK( host_room( &p.h_pr, &p.h_pr_bytes, 256 ) );
+	rma::prune_carve( pd, p.d_pr, n, parts, size_t( row ) );
+	char	*dt = reinterpret_cast<char *>( p.d_pr_table ) + align256( sizeof( rma::PruneTable ) );
+	pd.tab = p.d_pr_table;
+	pd.groups = nullptr;
+	pd.bad = reinterpret_cast<unsigned long long *>( dt );
+	pd.n_blocks = reinterpret_cast<long long *>( dt + 8 );
+	if( group_of_entry != nullptr && db->n_seq > 0 ){
+		// (pageable memory: the copy has left the caller's array when the call returns)
+		HIPCHK( dev_room( &p.d_pr_groups, &p.pr_groups_bytes, size_t( db->n_seq ) * 4 ) );
+		HIPCHK( hipMemcpyAsync( p.d_pr_groups, group_of_entry, size_t( db->n_seq ) * 4, hipMemcpyHostToDevice, st ) );
+		pd.groups = static_cast<const int32_t *>( p.d_pr_groups );
+	}
+	HIPCHK( hipMemsetAsync( pd.bad, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( pd.n_blocks, 0, sizeof( long long ), st ) );
+	HIPCHK( rma::prune_blocks( d_hits, n_hits, stride, rma::hitwin_shape( sc->prog ), row, db->d_slen, db->n_seq, pd, st ) );
+	unsigned long long	*h = static_cast<unsigned long long *>( p.h_pr );
+	HIPCHK( hipMemcpyAsync( h, pd.bad, 16, hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( h[ 0 ] != ~0ull ){
+		if( scratch_on( &p.win, sc->device, err, errlen ) )
+			return 1;
+		return bad_record( p.win, db, sc->prog, d_hits, int64_t( h[ 0 ] ), nullptr, "judged", err, errlen );
+	}
+	const int64_t	n_blocks = int64_t( h[ 1 ] );
+	if( n_blocks < 1 || n_blocks > n_hits ){
+		snprintf( err, errlen, "%s: %lld blocks of %lld records (records changed during the call?)", who, ( long long )n_blocks, ( long long )n_hits );
+		return 1;
+	}
+	HIPCHK( rma::prune_rezip( n_hits, row, pd, n_blocks, d_keep, st ) );
+	HIPCHK( hipEventRecord( p.pr_done, st ) );
+	return 0;
+}

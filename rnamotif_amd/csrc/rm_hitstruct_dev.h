@@ -1,4 +1,4 @@
-// rm_hitstruct_dev.h -- hit records expanded into per-base tensors on the device (rma_hit_structures, rm_scanner.cpp):
+// rm_hitstruct_dev.h -- hit records expanded into per-base tensors on the device (rma_hit_structures, rm_hitpost.cpp):
 // letter, element and mates of every base of every record's window.  The rule is rm_hitstruct.h's, shared with the host;
 // spans, sources and offsets come from rm_hitwin_dev.hip (rma_hit_span_kernel, the exclusive scan).
 //

@@ -115,7 +115,7 @@ RMW_FN int64_t hitwin_src( int comp, int32_t slen, int32_t lo, int64_t i )
 	return comp ? int64_t( slen ) - 1 - ( lo + i ) : lo + i;
 }
 
-// ---- the device half of rma_replay_device() (rm_scanner.cpp) as the host half (rm_capi.cpp) sees it
+// ---- the device half of rma_replay_device() (rm_hitpost.cpp) as the host half (rm_capi.cpp) sees it
 
 // the device and page-locked buffers of one replay handle, made on its first use, on the database's device
 struct HitWindowScratch;

@@ -1,5 +1,5 @@
 // rm_hitwin_dev.h -- the windows of hit records cut out of a device database's text on the device
-// (rma_replay_device, rm_scanner.cpp).  The rule is rm_hitwin.h's, shared with the host.
+// (rma_replay_device, rm_hitpost.cpp).  The rule is rm_hitwin.h's, shared with the host.
 //
 //   rma_hit_span_kernel    one lane per record: checks it, its window's length (0 for a bad record, whose index
 //                          goes into *bad by an atomic minimum), the span's first position

@@ -1,4 +1,4 @@
-// rm_prune_dev.h -- rmprune's rule over hit records on the device (rma_prune_hits, rm_scanner.cpp): a keep flag per
+// rm_prune_dev.h -- rmprune's rule over hit records on the device (rma_prune_hits, rm_hitpost.cpp): a keep flag per
 // record.  The rule is rm_prune.h's, shared with the host.  No workgroup waits for another: every kernel reads what
 // the one before it on the stream wrote.
 //

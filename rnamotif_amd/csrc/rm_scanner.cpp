@@ -15,50 +15,30 @@
 //                         work areas and ordering stage
 // A database is uploaded on the device's upload stream; a scan waits for that on its own stream
 // (an event), so the upload of the next database runs under the scan of this one.
-#include <hip/hip_runtime_api.h>
+// The two structs are defined in rm_scanner_impl.h; the calls that consume records already on the
+// device (windows, structures, alignments, pruning) are rm_hitpost.cpp's.
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
 #include <set>
-#include <string>
-#include <vector>
 
 #define RMD_FN		static inline
 #define RMD_FN_MEMBER	inline
-#include "rm_kernels.h"
-#include "rm_launch_plan.h"
+#include "rm_scanner_impl.h"
 #include "rm_scan_report.h"
 #include "rm_efn_core.h"
 #include "rm_efndata.h"
 #include "rm_fasta.h"
 #include "rm_pack.h"
-#include "rm_hitsort.h"
-#include "rm_hitsort_dev.h"
 #include "rm_dbpack_dev.h"
-#include "rm_hitwin_dev.h"
-#include "rm_hitstruct_dev.h"
-#include "rm_hitalign_dev.h"
-#include "rm_prune_dev.h"
 #include "rm_fasta_dev_kernels.h"
 #include "rm_stream.h"
-#include "rnamotif_amd.h"
 
-#define HIPCHK( call )	do{ hipError_t e_ = ( call ); if( e_ != hipSuccess ){ \
-		snprintf( err, errlen, "%s: %s", #call, hipGetErrorString( e_ ) ); return 1; } }while( 0 )
-
-namespace {
+using rma::Block;
 
 // ---------------------------------------------------------------- per-device context
-struct Block {
-	void	*p = nullptr;
-	size_t	bytes = 0;
-};
-
-struct DevCtx {
+struct rma::DevCtx {
 	int	device = 0;
 	std::mutex	mu;
 	hipStream_t	upload = nullptr;
@@ -118,6 +98,9 @@ struct DevCtx {
 		spare_bytes = 0;
 	}
 };
+using rma::DevCtx;
+
+namespace {
 
 std::mutex	g_ctx_mu;
 std::vector<std::unique_ptr<DevCtx>>	g_ctx;
@@ -140,8 +123,10 @@ DevCtx *dev_ctx( int device, char *err, size_t errlen )
 	return g_ctx.back().get();
 }
 
+}	// namespace
+
 // the tiling of a database for one launch shape, on the host and (blk) on the device
-struct Layout : rma::LayoutKey, rma::Tiling {
+struct rma::Layout : rma::LayoutKey, rma::Tiling {
 	Block	blk;
 	int64_t	*d_tile_start = nullptr;
 	int32_t	*d_tile_seq = nullptr;
@@ -149,103 +134,18 @@ struct Layout : rma::LayoutKey, rma::Tiling {
 	hipEvent_t	ready = nullptr;	// the copies are complete: every scan waits for it on its stream
 	~Layout(){ if( ready != nullptr ) ( void )hipEventDestroy( ready ); }
 };
-
-}	// namespace
-
-struct rma_scanner {
-	rma_program_t	prog;
-	rmd_program_t	dprog;
-	rma::Options	opt;
-	rma::ProgramPlan	plan;		// tile sizes of the descriptor (rma_scanner_create)
-	int	device = 0;
-	DevCtx	*ctx = nullptr;
-	hipStream_t	stream = nullptr;
-	hipEvent_t	ev[ 5 ] = { nullptr, nullptr, nullptr, nullptr, nullptr };	// search kernel's start / end, efn kernel's, [4]: the search kernel's end when a drain kernel follows
-	bool	drained = false;		// the last launch had a drain kernel
-	bool	searched = false, efn_ran = false;	// a search kernel was launched at all; the last scan had an efn kernel
-	rma_efn2data_t	*d_efn2 = nullptr;	// efn2() tables, global memory
-	bool	need_efn2 = false;
-	rmd_program_t	*d_prog = nullptr;	// compact image, prog_bytes long
-	int	prog_bytes = 0;
-	int16_t	*d_t16 = nullptr;
-	int32_t	*d_tlkey = nullptr, *d_loginc = nullptr;
-	bool	have_efn = false;
-	int32_t	*d_hits = nullptr;
-	int64_t	hit_cap = 0;
-	unsigned long long	*d_counters = nullptr;	// [RMK_N_COUNTERS], rm_diag.h: RMK_C_*
-	unsigned	*d_spill = nullptr;		// [grid_blocks][spill_cap] queue overflow of every workgroup
-	int	spill_cap = 0;
-	bool	whole_items = false;		// ... which takes the items whole, not in pieces (see search_finish)
-	int	glist_cap = 0;			// pooled instance: items of the list the drain kernel walks (the head of d_pool)
-	int	glist_need = 0;			// ... and what a scan of the instance that walks nothing asked for (search_finish)
-	unsigned	*d_pool = nullptr;		// [grid_blocks][pool_cap][3] pooled instance: items waiting for pass B
-	int	pool_cap = 0;
-	int32_t	*h_raw = nullptr;		// pinned
-	size_t	h_raw_cap = 0;
-	std::vector<int32_t>	h_sorted;
-	std::vector<rma::HitKey>	keys, keys_tmp;
-	rma::DevHitSort	dsort;		// ordering on the device (rm_hitsort_dev.h)
-	unsigned long long	*h_ctr = nullptr;	// pinned: the first RMK_C_COPIED counters as a launch leaves them
-	int	grid_blocks = 0;		// most workgroups of a launch of a lean instance (eight of four waves per CU)
-	int	spill_blocks = 0;		// workgroups d_spill has areas for
-	// the scan between rma_scan_begin() and rma_scan_end()
-	struct InFlight {
-		const rma_db	*db = nullptr;
-		const Layout	*lay = nullptr;
-		rma::LaunchPlan	plan;
-	}	fly;
-	// what the last scan left on the device, in order (rma_scan_end): for rma_gather_hits()
-	const int32_t	*d_last = nullptr;
-	int64_t	n_last = 0;
-	int	last_state = 0;			// (rma_scanner_last_state)
-	bool	last_relabelled = false;	// rma_gather_hits has put database-wide entry numbers into d_last's records
-	// rma_hit_structures: the span scratch and stream (made on its first call), the program's table and the running total
-	rma::HitWindowScratch	*hs_win = nullptr;
-	rma::HitStructTable	*d_hs_table = nullptr;
-	int64_t	*d_hs_carry = nullptr;
-	// rma_prune_hits: the program's table (two result words behind it), the keys, flags and block list of a call, the
-	// entries' name groups, two page-locked words, and the event behind the last call's kernels
-	rma::PruneTable	*d_pr_table = nullptr;
-	void	*d_pr = nullptr, *d_pr_groups = nullptr, *h_pr = nullptr;
-	size_t	pr_bytes = 0, pr_groups_bytes = 0, h_pr_bytes = 0;
-	hipEvent_t	pr_done = nullptr;
-};
-
-struct rma_db {
-	int	device = 0;
-	DevCtx	*ctx = nullptr;
-	Block	blk;			// codes | amask | base_off | slen | pos_lo | pos_hi
-	uint32_t	*d_codes = nullptr, *d_amask = nullptr;
-	int64_t	*d_base_off = nullptr;
-	int32_t	*d_slen = nullptr, *d_pos_lo = nullptr, *d_pos_hi = nullptr;
-	std::vector<int32_t>	h_slen, h_pos_lo, h_pos_hi;	// (host copies: the tilings are made from them)
-	std::vector<int64_t>	h_base_off;
-	std::vector<int64_t>	h_text_start;		// (rma_db_create_device: what the copies to the device read)
-	std::vector<uint8_t>	h_table;
-	// rma_db_create_device: the text (bytes [text_lo, text_hi) of it hold the entries), the entries' starts and
-	// the table on the device, and whether the table was the default one -- what rma_replay_device() reads
-	const uint8_t	*text = nullptr;
-	int64_t	text_bytes = 0, text_lo = 0, text_hi = 0;
-	const int64_t	*d_text_start = nullptr;
-	const uint8_t	*d_table = nullptr;
-	bool	default_table = true;
-	// rma_db_create_device_fasta: the clean text is the database's own, and the entries have names
-	Block	text_blk;
-	std::vector<std::string>	sids, sdefs;
-	int32_t	n_seq = 0, max_slen = 0;
-	int64_t	total_bases = 0, sum_slen = 0;
-	int64_t	padded_bases = 0;	// bases the packed arrays hold, padding between the entries included
-	bool	ascending = true;	// the entries lie in the packed arrays in their order, none overlapping
-	hipEvent_t	ready = nullptr;	// the upload is complete (recorded on the upload stream)
-	std::mutex	mu;			// layouts, busy
-	std::vector<std::unique_ptr<Layout>>	layouts;
-	std::vector<rma_scanner *>	busy;		// scanners with a scan of this database in flight
-};
+using rma::Layout;
 
 // the databases rma_db_create_device() has made and rma_db_destroy() has not yet destroyed (rma_replay_device
 // refuses any other)
 static std::mutex	g_device_dbs_mu;
 static std::set<const rma_db *>	g_device_dbs;
+
+bool rma::is_device_db( const rma_db *db )
+{
+	std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+	return g_device_dbs.count( db ) != 0;
+}
 
 extern "C" void rma_db_destroy( rma_db_t *db );
 extern "C" void rma_scanner_destroy( rma_scanner_t *sc );
@@ -423,14 +323,7 @@ extern "C" void rma_scanner_destroy( rma_scanner_t *sc )
 	( void )hipFree( sc->d_counters );
 	( void )hipFree( sc->d_spill );
 	( void )hipFree( sc->d_pool );
-	rma::hitwin_scratch_free( sc->hs_win );
-	( void )hipFree( sc->d_hs_table );		// (the running total lies behind the table)
-	( void )hipFree( sc->d_pr_table );
-	( void )hipFree( sc->d_pr );
-	( void )hipFree( sc->d_pr_groups );
-	( void )hipHostFree( sc->h_pr );
-	if( sc->pr_done )
-		( void )hipEventDestroy( sc->pr_done );
+	rma::hitpost_free( sc->post );
 	for( int i = 0; i < 5; i++ )
 		if( sc->ev[ i ] )
 			( void )hipEventDestroy( sc->ev[ i ] );
@@ -440,8 +333,6 @@ extern "C" void rma_scanner_destroy( rma_scanner_t *sc )
 }
 
 // ---------------------------------------------------------------- databases
-static size_t align256( size_t x ) { return ( x + 255 ) & ~size_t( 255 ); }
-
 // A database of n entries in a block of its own, the small tables -- base_off[] (the entries' offsets in
 // bases, multiples of 32, in the device arrays), slen, pos_lo / pos_hi -- on their way on the device's
 // upload stream; the packed words (n_mask mask words, twice as many code words) are the caller's to fill,
@@ -485,24 +376,25 @@ static int db_alloc( int device, const int64_t *base_off, const int32_t *slen, i
 	for( int i = 0; i < n; i++ )
 		if( base_off[ i ] < 0 || base_off[ i ] + slen[ i ] > db->padded_bases || ( i + 1 < n && base_off[ i ] + slen[ i ] > base_off[ i + 1 ] ) )
 			db->ascending = false;
-	const size_t	nn = size_t( std::max( n, 1 ) );
-	const size_t	o_codes = 0, o_amask = align256( std::max<size_t>( 2 * n_mask, 1 ) * 4 );
-	const size_t	o_off = o_amask + align256( std::max<size_t>( n_mask, 1 ) * 4 ), o_slen = o_off + align256( nn * 8 );
-	const size_t	o_lo = o_slen + align256( nn * 4 ), o_hi = o_lo + ( pos_lo ? align256( nn * 4 ) : 0 );
-	const size_t	o_extra = o_hi + ( pos_lo ? align256( nn * 4 ) : 0 );
-	const size_t	total = o_extra + extra;
+	// (carved twice: for the block's size, then in the block)
+	auto	carve = [ & ]( void *base ){
+		const size_t	nn = size_t( std::max( n, 1 ) );
+		Carver	c;
+		db->d_codes = c.take<uint32_t>( base, std::max<size_t>( 2 * n_mask, 1 ) );
+		db->d_amask = c.take<uint32_t>( base, std::max<size_t>( n_mask, 1 ) );
+		db->d_base_off = c.take<int64_t>( base, nn );
+		db->d_slen = c.take<int32_t>( base, nn );
+		if( pos_lo != nullptr ){
+			db->d_pos_lo = c.take<int32_t>( base, nn );
+			db->d_pos_hi = c.take<int32_t>( base, nn );
+		}
+		if( extra_at != nullptr )
+			*extra_at = c.take<char>( base, 0 );
+		return c.at;
+	};
+	const size_t	total = carve( nullptr ) + extra;
 	HIPCHK( ctx->take( total, &db->blk ) );
-	char	*base = static_cast<char *>( db->blk.p );
-	db->d_codes = reinterpret_cast<uint32_t *>( base + o_codes );
-	db->d_amask = reinterpret_cast<uint32_t *>( base + o_amask );
-	db->d_base_off = reinterpret_cast<int64_t *>( base + o_off );
-	db->d_slen = reinterpret_cast<int32_t *>( base + o_slen );
-	if( pos_lo != nullptr ){
-		db->d_pos_lo = reinterpret_cast<int32_t *>( base + o_lo );
-		db->d_pos_hi = reinterpret_cast<int32_t *>( base + o_hi );
-	}
-	if( extra_at != nullptr )
-		*extra_at = base + o_extra;
+	carve( db->blk.p );
 	HIPCHK( hipEventCreateWithFlags( &db->ready, hipEventDisableTiming ) );
 	hipStream_t	up = ctx->upload;
 	if( n > 0 ){
@@ -679,7 +571,7 @@ extern "C" int rma_db_create_packed_ranges( rma_scanner_t *sc, const rma_pack_t 
 // bytes [lo, hi) from it inside its allocation where the runtime can say where that ends (memory it maps
 // itself it cannot -- torch's expandable segments: the caller's extent governs alone).  A host pointer
 // handed to a kernel faults the GPU; nothing is launched before this has said yes.
-static int check_device_bytes( const void *p, int device, int64_t lo, int64_t hi, const char *what, char *err, size_t errlen )
+int rma::check_device_bytes( const void *p, int device, int64_t lo, int64_t hi, const char *what, char *err, size_t errlen )
 {
 	hipPointerAttribute_t	a;
 	memset( &a, 0, sizeof( a ) );
@@ -716,7 +608,7 @@ static int check_device_bytes( const void *p, int device, int64_t lo, int64_t hi
 }
 
 // the caller's stream has reached this point before anything later on `on` runs
-static int stream_after( hipStream_t on, hipStream_t caller, char *err, size_t errlen )
+int rma::stream_after( hipStream_t on, hipStream_t caller, char *err, size_t errlen )
 {
 	hipEvent_t	ev = nullptr;
 	HIPCHK( hipEventCreateWithFlags( &ev, hipEventDisableTiming ) );
@@ -763,7 +655,7 @@ extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_
 		}
 	}
 	HIPCHK( hipSetDevice( device ) );
-	if( hi > lo && check_device_bytes( text, device, lo, hi, "the text", err, errlen ) )
+	if( hi > lo && rma::check_device_bytes( text, device, lo, hi, "the text", err, errlen ) )
 		return 1;
 	// the table: on the device (copied there, device to device) or on the host (checked, copied up)
 	bool	table_on_device = false;
@@ -776,7 +668,7 @@ extern "C" int rma_db_create_device( rma_scanner_t *sc, const void *text, int64_
 		else if( a.type == hipMemoryTypeDevice && !a.isManaged )
 			table_on_device = true;
 		if( table_on_device ){
-			if( check_device_bytes( table, device, 0, 256, "the table", err, errlen ) )
+			if( rma::check_device_bytes( table, device, 0, 256, "the table", err, errlen ) )
 				return 1;
 		}else{
 			for( int c = 0; c < 256; c++ )
@@ -831,7 +723,7 @@ static int db_from_device_text( rma_scanner_t *sc, const void *text, int64_t tex
 	if( !table_on_device )
 		HIPCHK( hipMemcpyAsync( d_table, db->h_table.data(), 256, hipMemcpyHostToDevice, up ) );
 	// the text (and a device table) as the caller's stream leaves them
-	if( stream_after( up, static_cast<hipStream_t>( stream ), err, errlen ) )
+	if( rma::stream_after( up, static_cast<hipStream_t>( stream ), err, errlen ) )
 		return 1;
 	if( table_on_device )
 		HIPCHK( hipMemcpyAsync( d_table, table, 256, hipMemcpyDeviceToDevice, up ) );
@@ -865,7 +757,7 @@ extern "C" int rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, 
 	}
 	const int64_t	lim = maxslen > 0 ? int64_t( maxslen ) + 1 : 30000000 + 1;	// as rma_pack_read: -N n reads n letters
 	HIPCHK( hipSetDevice( device ) );
-	if( text_bytes > 0 && check_device_bytes( text, device, 0, text_bytes, "the text", err, errlen ) )
+	if( text_bytes > 0 && rma::check_device_bytes( text, device, 0, text_bytes, "the text", err, errlen ) )
 		return 1;
 	DevCtx	*ctx = dev_ctx( device, err, errlen );
 	if( ctx == nullptr )
@@ -905,7 +797,7 @@ extern "C" int rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, 
 		d_block_pre = reinterpret_cast<rma::FdPrefix *>( w + o_bpre );
 		d_totals = reinterpret_cast<rma::FdPrefix *>( w + o_tot );
 		// the text as the caller's stream leaves it
-		if( stream_after( up, static_cast<hipStream_t>( stream ), err, errlen ) )
+		if( rma::stream_after( up, static_cast<hipStream_t>( stream ), err, errlen ) )
 			return 1;
 		HIPCHK( rma::fasta_index( t8, text_bytes, reinterpret_cast<rma::FdSummary *>( w + o_sum ), reinterpret_cast<rma::FdSummary *>( w + o_local ),
 			reinterpret_cast<rma::FdSummary *>( w + o_bsum ), reinterpret_cast<rma::FdPrefix *>( w + o_bpre ),
@@ -1079,640 +971,6 @@ extern "C" void rma_db_destroy( rma_db_t *db )
 }
 
 extern "C" int64_t rma_db_bases( const rma_db_t *db ) { return db->total_bases; }
-
-// ---------------------------------------------------------------- windows of hits of device databases
-// The device half of rma_replay_device() (rm_capi.cpp has the replay): the records are checked and their windows
-// cut out of the database's text on the device (rm_hitwin_dev.hip), in chunks of HW_CHUNK records, and come to
-// the host in pieces of at most HW_PIECE_WINDOW bytes of windows and HW_PIECE_RECORDS bytes of records (a longer
-// window comes alone).  One synchronisation learns a chunk's offsets (and, in the first chunk, whether some
-// record is bad), one per piece ends its copy.
-namespace {
-constexpr int64_t	HW_CHUNK = int64_t( 1 ) << 17;
-constexpr int64_t	HW_PIECE_WINDOW = int64_t( 16 ) << 20, HW_PIECE_RECORDS = int64_t( 8 ) << 20;
-
-hipError_t dev_room( void **p, size_t *cap, size_t want )
-{
-	if( *cap >= want )
-		return hipSuccess;
-	if( *p != nullptr )
-		( void )hipFree( *p );
-	*p = nullptr;
-	*cap = 0;
-	want += want / 4;
-	hipError_t	e = hipMalloc( p, want );
-	if( e == hipSuccess )
-		*cap = want;
-	return e;
-}
-
-hipError_t host_room( void **p, size_t *cap, size_t want )
-{
-	if( *cap >= want )
-		return hipSuccess;
-	if( *p != nullptr )
-		( void )hipHostFree( *p );
-	*p = nullptr;
-	*cap = 0;
-	want += want / 4;
-	hipError_t	e = hipHostMalloc( p, want, hipHostMallocDefault );
-	if( e == hipSuccess )
-		*cap = want;
-	return e;
-}
-}	// namespace
-
-struct rma::HitWindowScratch {
-	int	device = -1;
-	hipStream_t	stream = nullptr;
-	// device: lo[ HW_CHUNK ] | len[ HW_CHUNK + 1 ] | off[ HW_CHUNK + 1 ] | src[ HW_CHUNK ] | bad | letters[ 256 ], the scan's
-	// room, windows
-	void	*d_fixed = nullptr, *d_tmp = nullptr, *d_win = nullptr;
-	size_t	fixed_bytes = 0, tmp_bytes = 0, win_cap = 0;
-	int32_t	*d_lo = nullptr;
-	int64_t	*d_len = nullptr, *d_off = nullptr, *d_src = nullptr;
-	unsigned long long	*d_bad = nullptr;
-	uint8_t	*d_tab = nullptr;
-	// page-locked: off[ HW_CHUNK + 1 ] | lo[ HW_CHUNK ] | bad | letters[ 256 ], records, windows
-	void	*h_fixed = nullptr, *h_rec = nullptr, *h_win = nullptr;
-	size_t	h_fixed_bytes = 0, rec_cap = 0, h_win_cap = 0;
-	int64_t	*h_off = nullptr;
-	int32_t	*h_lo = nullptr;
-	unsigned long long	*h_bad = nullptr;
-	uint8_t	*h_tab = nullptr;
-	std::vector<int64_t>	piece_off;
-};
-
-void rma::hitwin_scratch_free( HitWindowScratch *s )
-{
-	if( s == nullptr )
-		return;
-	( void )hipSetDevice( s->device );
-	if( s->stream != nullptr )
-		( void )hipStreamSynchronize( s->stream );
-	for( void *p : { s->d_fixed, s->d_tmp, s->d_win } )
-		if( p != nullptr )
-			( void )hipFree( p );
-	for( void *p : { s->h_fixed, s->h_rec, s->h_win } )
-		if( p != nullptr )
-			( void )hipHostFree( p );
-	if( s->stream != nullptr )
-		( void )hipStreamDestroy( s->stream );
-	delete s;
-}
-
-static int scratch_on( rma::HitWindowScratch **scratch, int device, char *err, size_t errlen )
-{
-	if( *scratch != nullptr && ( *scratch )->device == device )
-		return 0;
-	rma::hitwin_scratch_free( *scratch );
-	*scratch = new rma::HitWindowScratch;
-	rma::HitWindowScratch	*s = *scratch;
-	s->device = device;
-	HIPCHK( hipStreamCreateWithFlags( &s->stream, hipStreamNonBlocking ) );
-	const size_t	o_len = align256( size_t( HW_CHUNK ) * 4 ), o_off = o_len + align256( size_t( HW_CHUNK + 1 ) * 8 );
-	const size_t	o_src = o_off + align256( size_t( HW_CHUNK + 1 ) * 8 ), o_bad = o_src + align256( size_t( HW_CHUNK ) * 8 ), o_tab = o_bad + 256;
-	HIPCHK( dev_room( &s->d_fixed, &s->fixed_bytes, o_tab + 256 ) );
-	char	*d = static_cast<char *>( s->d_fixed );
-	s->d_lo = reinterpret_cast<int32_t *>( d );
-	s->d_len = reinterpret_cast<int64_t *>( d + o_len );
-	s->d_off = reinterpret_cast<int64_t *>( d + o_off );
-	s->d_src = reinterpret_cast<int64_t *>( d + o_src );
-	s->d_bad = reinterpret_cast<unsigned long long *>( d + o_bad );
-	s->d_tab = reinterpret_cast<uint8_t *>( d + o_tab );
-	size_t	tmp = 0;
-	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, HW_CHUNK + 1, nullptr, &tmp, s->stream ) );
-	HIPCHK( dev_room( &s->d_tmp, &s->tmp_bytes, std::max<size_t>( tmp, 256 ) ) );
-	const size_t	h_lo = align256( size_t( HW_CHUNK + 1 ) * 8 ), h_bad = h_lo + align256( size_t( HW_CHUNK ) * 4 ), h_tab = h_bad + 256;
-	HIPCHK( host_room( &s->h_fixed, &s->h_fixed_bytes, h_tab + 256 ) );
-	char	*h = static_cast<char *>( s->h_fixed );
-	s->h_off = reinterpret_cast<int64_t *>( h );
-	s->h_lo = reinterpret_cast<int32_t *>( h + h_lo );
-	s->h_bad = reinterpret_cast<unsigned long long *>( h + h_bad );
-	s->h_tab = reinterpret_cast<uint8_t *>( h + h_tab );
-	return 0;
-}
-
-// the words of a bad record, why it is bad; tab: the helix check as well (rma_hit_structures); nothing: "printed" or "written"
-static int bad_record( rma::HitWindowScratch *s, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits, int64_t h,
-	const rma::HitStructTable *tab, const char *nothing, char *err, size_t errlen )
-{
-	const int	stride = rma_hit_stride( &prog );
-	std::vector<int32_t>	w( static_cast<size_t>( stride ) );
-	HIPCHK( hipMemcpyAsync( w.data(), d_hits + h * stride, size_t( stride ) * 4, hipMemcpyDeviceToHost, s->stream ) );
-	HIPCHK( hipStreamSynchronize( s->stream ) );
-	int32_t	lo, hi;
-	int	which;
-	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
-	const int	r = tab != nullptr ? rma::hitstruct_check( w.data(), *tab, shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which ) :
-		rma::hitwin_span( w.data(), shape, db->n_seq, db->h_slen.data(), &lo, &hi, &which );
-	if( r == rma::HW_ENTRY )
-		snprintf( err, errlen, "record %lld: entry %d outside [0, %d): nothing %s", ( long long )h, w[ 0 ], db->n_seq, nothing );
-	else if( r == rma::HW_STRAND )
-		snprintf( err, errlen, "record %lld: strand %d, not 0 or 1: nothing %s", ( long long )h, w[ 1 ], nothing );
-	else if( r == rma::HS_HELIX ){
-		const int	first = tab->e[ which ].strand[ 0 ];
-		snprintf( err, errlen, "record %lld: element %d has length %d, element %d of the same helix length %d: nothing %s", ( long long )h,
-			which, w[ RMA_HIT_HDR + 4 * which + 1 ], first, w[ RMA_HIT_HDR + 4 * first + 1 ], nothing );
-	}
-	else if( r == rma::HW_EXTENT ){
-		const int	k = which < shape.n_elems ? RMA_HIT_HDR + 4 * which : which == shape.n_elems ? shape.ctx_off : shape.ctx_off + 2;
-		char	what[ 32 ];
-		if( which < shape.n_elems )
-			snprintf( what, sizeof( what ), "element %d", which );
-		else
-			snprintf( what, sizeof( what ), "the %s context", which == shape.n_elems ? "left" : "right" );
-		snprintf( err, errlen, "record %lld: %s at offset %d, length %d, outside entry %d's %d bases: nothing %s", ( long long )h,
-			what, w[ k ], w[ k + 1 ], w[ 0 ], db->h_slen[ size_t( w[ 0 ] ) ], nothing );
-	}else
-		snprintf( err, errlen, "record %lld: refused on the device, not on the host (records changed during the call?)", ( long long )h );
-	return 1;
-}
-
-int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits,
-	int64_t n_hits, const uint8_t *letters, void *stream, const std::function<void( const rma::HitWindowPiece & )> &each,
-	char *err, size_t errlen )
-{
-	{
-		std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
-		if( db == nullptr || g_device_dbs.count( db ) == 0 ){
-			snprintf( err, errlen, "rma_replay_device: the database (%p) was not made by rma_db_create_device() or has been destroyed",
-				static_cast<const void *>( db ) );
-			return 1;
-		}
-	}
-	const int	stride = rma_hit_stride( &prog );
-	if( n_hits < 0 || ( n_hits > 0 && d_hits == nullptr ) || n_hits > INT64_MAX / 4 / stride ){
-		snprintf( err, errlen, "rma_replay_device: %lld records: bad arguments", ( long long )n_hits );
-		return 1;
-	}
-	if( n_hits == 0 )
-		return 0;
-	HIPCHK( hipSetDevice( db->device ) );
-	// the records: n_hits records of the replay's program's stride, inside their allocation
-	if( check_device_bytes( d_hits, db->device, 0, n_hits * stride * 4, "the records", err, errlen ) )
-		return 1;
-	if( db->text_hi > db->text_lo && check_device_bytes( db->text, db->device, db->text_lo, db->text_hi, "the database's text", err, errlen ) )
-		return 1;
-	if( scratch_on( scratch, db->device, err, errlen ) )
-		return 1;
-	rma::HitWindowScratch	*s = *scratch;
-	hipStream_t	st = s->stream;
-	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
-	// the letters: the caller's, the readers', or the letters of the database's own codes
-	const uint8_t	*tab = s->d_tab;
-	int	codes = 0;
-	if( letters != nullptr )
-		memcpy( s->h_tab, letters, 256 );
-	else if( db->default_table )
-		for( int b = 0; b < 256; b++ )
-			s->h_tab[ b ] = rma::hitwin_reader_letter( static_cast<unsigned char>( b ) );
-	else{
-		tab = db->d_table;
-		codes = 1;
-	}
-	if( tab == s->d_tab )
-		HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, st ) );
-	// behind the caller's work on its stream (the records) and the database's tables
-	if( stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
-		return 1;
-	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
-	// every record checked before any text is read: all of them here when there is more than one chunk, else
-	// the first chunk's spans do it
-	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
-	if( n_hits > HW_CHUNK )
-		HIPCHK( rma::hit_spans( d_hits, n_hits, stride, shape, db->d_slen, db->d_text_start, db->n_seq, nullptr, nullptr, nullptr,
-			s->d_bad, st ) );
-	const int64_t	piece_records = std::max<int64_t>( 1, HW_PIECE_RECORDS / ( 4 * stride ) );
-	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
-		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
-		const int32_t	*ch = d_hits + c0 * stride;
-		HIPCHK( rma::hit_spans( ch, cn, stride, shape, db->d_slen, db->d_text_start, db->n_seq, s->d_lo, s->d_len, s->d_src,
-			s->d_bad, st ) );
-		size_t	tb = s->tmp_bytes;
-		HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, st ) );
-		HIPCHK( hipMemcpyAsync( s->h_off, s->d_off, size_t( cn + 1 ) * 8, hipMemcpyDeviceToHost, st ) );
-		HIPCHK( hipMemcpyAsync( s->h_lo, s->d_lo, size_t( cn ) * 4, hipMemcpyDeviceToHost, st ) );
-		if( c0 == 0 )
-			HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
-		HIPCHK( hipStreamSynchronize( st ) );
-		if( c0 == 0 && *s->h_bad != ~0ull )
-			return bad_record( s, db, prog, d_hits, int64_t( *s->h_bad ), nullptr, "printed", err, errlen );
-		for( int64_t a = 0; a < cn; ){
-			int64_t	b = a + 1;
-			while( b < cn && b - a < piece_records && s->h_off[ b + 1 ] - s->h_off[ a ] <= HW_PIECE_WINDOW )
-				b++;
-			const int64_t	bytes = s->h_off[ b ] - s->h_off[ a ];
-			HIPCHK( dev_room( &s->d_win, &s->win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
-			HIPCHK( host_room( &s->h_win, &s->h_win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
-			HIPCHK( host_room( &s->h_rec, &s->rec_cap, size_t( b - a ) * stride * 4 ) );
-			HIPCHK( rma::hit_gather( db->text, b - a, s->d_src + a, s->d_off + a, tab, codes, static_cast<uint8_t *>( s->d_win ), st ) );
-			HIPCHK( hipMemcpyAsync( s->h_rec, ch + a * stride, size_t( b - a ) * stride * 4, hipMemcpyDeviceToHost, st ) );
-			if( bytes > 0 )
-				HIPCHK( hipMemcpyAsync( s->h_win, s->d_win, size_t( bytes ), hipMemcpyDeviceToHost, st ) );
-			HIPCHK( hipStreamSynchronize( st ) );
-			s->piece_off.resize( size_t( b - a + 1 ) );
-			for( int64_t i = a; i <= b; i++ )
-				s->piece_off[ size_t( i - a ) ] = s->h_off[ i ] - s->h_off[ a ];
-			each( rma::HitWindowPiece{ static_cast<const int32_t *>( s->h_rec ), c0 + a, b - a, static_cast<const char *>( s->h_win ),
-				s->piece_off.data(), s->h_lo + a, db->h_slen.data(), db->n_seq } );
-			a = b;
-		}
-	}
-	return 0;
-}
-
-// ---------------------------------------------------------------- hit structures as device tensors
-// rma_hit_structures_size() / rma_hit_structures(): the spans, sources and offsets of rm_hitwin_dev.hip in chunks of
-// HW_CHUNK records, the helix check and the fill kernel of rm_hitstruct_dev.hip.  The outputs are the caller's and are
-// written in place: a chunk's offsets count from its first record (the scan's), the window bytes of the chunks
-// before it wait in a word on the device (*d_hs_carry), so no chunk needs the host.  The work runs on a stream of the
-// scanner's own, behind the caller's stream and, when something was written, ahead of what the caller queues next.
-namespace {
-
-// What both calls do first: the database, the records and the scanner's scratch (made on first use).  n_hits == 0
-// needs none of it.
-int hit_structures_args( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, const char *who, char *err, size_t errlen )
-{
-	{
-		std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
-		if( db == nullptr || g_device_dbs.count( db ) == 0 ){
-			snprintf( err, errlen, "%s: the database (%p) was not made by rma_db_create_device() or has been destroyed", who,
-				static_cast<const void *>( db ) );
-			return 1;
-		}
-	}
-	const int	stride = rma_hit_stride( &sc->prog );
-	if( n_hits < 0 || ( n_hits > 0 && d_hits == nullptr ) || n_hits > INT64_MAX / 16 / stride ){
-		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )n_hits );
-		return 1;
-	}
-	if( db->device != sc->device ){
-		snprintf( err, errlen, "%s: the database is on device %d, the scanner on device %d", who, db->device, sc->device );
-		return 1;
-	}
-	HIPCHK( hipSetDevice( sc->device ) );
-	if( n_hits == 0 )
-		return 0;
-	if( check_device_bytes( d_hits, sc->device, 0, n_hits * stride * 4, "the records", err, errlen ) )
-		return 1;
-	if( db->text_hi > db->text_lo && check_device_bytes( db->text, db->device, db->text_lo, db->text_hi, "the database's text", err, errlen ) )
-		return 1;
-	if( scratch_on( &sc->hs_win, sc->device, err, errlen ) )
-		return 1;
-	if( sc->d_hs_table == nullptr ){
-		// the program's table and, behind it, the running total
-		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
-		const size_t	at = ( sizeof( rma::HitStructTable ) + 7 ) & ~size_t( 7 );
-		void	*p = nullptr;
-		HIPCHK( hipMalloc( &p, at + sizeof( int64_t ) ) );
-		sc->d_hs_table = static_cast<rma::HitStructTable *>( p );
-		sc->d_hs_carry = reinterpret_cast<int64_t *>( static_cast<char *>( p ) + at );
-		HIPCHK( hipMemcpy( sc->d_hs_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
-	}
-	return 0;
-}
-
-// One chunk's spans, sources and offsets into the scratch; *bad as hit_spans
-int hit_structures_spans( rma_scanner_t *sc, const rma_db *db, const int32_t *ch, int64_t cn, unsigned long long *bad, char *err, size_t errlen )
-{
-	rma::HitWindowScratch	*s = sc->hs_win;
-	HIPCHK( rma::hit_spans( ch, cn, rma_hit_stride( &sc->prog ), rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq,
-		s->d_lo, s->d_len, s->d_src, bad, s->stream ) );
-	size_t	tb = s->tmp_bytes;
-	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, s->stream ) );
-	return 0;
-}
-
-// Every record checked on the device and the window bytes counted (n_hits > 0, hit_structures_args has passed): one
-// synchronisation.  A call of one chunk leaves that chunk's spans in the scratch.
-int hit_structures_count( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, void *stream, int64_t *total,
-	char *err, size_t errlen )
-{
-	rma::HitWindowScratch	*s = sc->hs_win;
-	hipStream_t	st = s->stream;
-	const int	stride = rma_hit_stride( &sc->prog );
-	// behind the caller's work on its stream (the records) and the database's tables
-	if( stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
-		return 1;
-	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
-	// d_bad[ 0 ]: the least index of a bad record, counted over the call; d_bad[ 2 ]: where the spans of a later chunk,
-	// which count from the chunk's first record, put theirs (the same records, already judged)
-	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
-	HIPCHK( hipMemsetAsync( sc->d_hs_carry, 0, sizeof( int64_t ), st ) );
-	const bool	chunks = n_hits > HW_CHUNK;
-	if( chunks )
-		HIPCHK( rma::hit_spans( d_hits, n_hits, stride, rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq, nullptr, nullptr,
-			nullptr, s->d_bad, st ) );
-	HIPCHK( rma::hit_helix_check( d_hits, n_hits, stride, sc->d_hs_table, s->d_bad, st ) );
-	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
-		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
-		if( hit_structures_spans( sc, db, d_hits + c0 * stride, cn, chunks ? s->d_bad + 2 : s->d_bad, err, errlen ) )
-			return 1;
-		HIPCHK( rma::hit_carry_add( sc->d_hs_carry, s->d_off + cn, st ) );
-	}
-	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad + 1, sc->d_hs_carry, sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipStreamSynchronize( st ) );
-	if( s->h_bad[ 0 ] != ~0ull ){
-		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
-		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), &tab, "written", err, errlen );
-	}
-	*total = int64_t( s->h_bad[ 1 ] );
-	return 0;
-}
-
-}	// namespace
-
-extern "C" int rma_hit_structures_size( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
-	void *stream, int64_t *total, char *err, size_t errlen )
-{
-	*total = 0;
-	if( hit_structures_args( sc, db, d_hits, n_hits, "rma_hit_structures_size", err, errlen ) )
-		return 1;
-	return n_hits == 0 ? 0 : hit_structures_count( sc, db, d_hits, n_hits, stream, total, err, errlen );
-}
-
-extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
-	const uint8_t *letters, int64_t total, int64_t *d_off, int32_t *d_lo, uint8_t *d_base, int16_t *d_elem, int32_t *d_mate,
-	void *stream, char *err, size_t errlen )
-{
-	const char	*who = "rma_hit_structures";
-	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
-		return 1;
-	if( total < 0 || total > INT64_MAX / 16 || d_off == nullptr || ( n_hits > 0 && d_lo == nullptr ) ||
-		( total > 0 && ( d_base == nullptr || d_elem == nullptr || d_mate == nullptr ) ) ){
-		snprintf( err, errlen, "%s: %lld window bytes: bad arguments", who, ( long long )total );
-		return 1;
-	}
-	// the outputs: the caller's, each inside its allocation on the scanner's device
-	if( check_device_bytes( d_off, sc->device, 0, ( n_hits + 1 ) * 8, "the offsets", err, errlen ) ||
-		( n_hits > 0 && check_device_bytes( d_lo, sc->device, 0, n_hits * 4, "the first positions", err, errlen ) ) ||
-		( total > 0 && ( check_device_bytes( d_base, sc->device, 0, total, "the bases", err, errlen ) ||
-			check_device_bytes( d_elem, sc->device, 0, total * 2, "the elements", err, errlen ) ||
-			check_device_bytes( d_mate, sc->device, 0, total * 12, "the mates", err, errlen ) ) ) )
-		return 1;
-	hipStream_t	caller = static_cast<hipStream_t>( stream );
-	int64_t	found = 0;
-	const uint8_t	*tab = nullptr;
-	int	codes = 0;
-	if( n_hits > 0 ){
-		rma::HitWindowScratch	*s = sc->hs_win;
-		// the letters: the caller's, the readers', or the letters of the database's own codes (as rma_replay_device);
-		// on their way ahead of the count, whose synchronisation leaves the page-locked copy free for the next call
-		tab = s->d_tab;
-		if( letters != nullptr )
-			memcpy( s->h_tab, letters, 256 );
-		else if( db->default_table )
-			for( int b = 0; b < 256; b++ )
-				s->h_tab[ b ] = rma::hitwin_reader_letter( static_cast<unsigned char>( b ) );
-		else{
-			tab = db->d_table;
-			codes = 1;
-		}
-		if( tab == s->d_tab )
-			HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, s->stream ) );
-		if( hit_structures_count( sc, db, d_hits, n_hits, stream, &found, err, errlen ) )
-			return 1;
-	}
-	if( found != total ){
-		snprintf( err, errlen, "%s: the windows of the %lld records have %lld bytes, not the %lld of `total`: nothing written", who,
-			( long long )n_hits, ( long long )found, ( long long )total );
-		return 1;
-	}
-	if( n_hits == 0 ){
-		HIPCHK( hipMemsetAsync( d_off, 0, sizeof( int64_t ), caller ) );
-		return 0;
-	}
-	rma::HitWindowScratch	*s = sc->hs_win;
-	hipStream_t	st = s->stream;
-	const int	stride = rma_hit_stride( &sc->prog );
-	HIPCHK( hipMemsetAsync( sc->d_hs_carry, 0, sizeof( int64_t ), st ) );
-	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
-		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
-		const int32_t	*ch = d_hits + c0 * stride;
-		// (a call of one chunk: the count's spans are still there)
-		if( n_hits > HW_CHUNK && hit_structures_spans( sc, db, ch, cn, s->d_bad + 2, err, errlen ) )
-			return 1;
-		const rma::HitStructOut	out{ d_off + c0, d_lo + c0, d_base, d_elem, d_mate };
-		HIPCHK( rma::hit_struct_fill( db->text, ch, cn, stride, rma::hitwin_shape( sc->prog ), sc->d_hs_table, s->d_lo, s->d_src, s->d_off,
-			sc->d_hs_carry, tab, codes, out, c0 + cn == n_hits, st ) );
-		HIPCHK( rma::hit_carry_add( sc->d_hs_carry, s->d_off + cn, st ) );
-	}
-	return stream_after( caller, st, err, errlen );
-}
-
-// ---------------------------------------------------------------- hit records as an alignment
-// rma_hit_alignment_shape() / rma_hit_alignment(): the record check of rm_hitwin_dev.hip over all records, then the
-// widths and fill kernels of rm_hitalign_dev.hip in chunks of HW_CHUNK records, on the stream of the scanner's span
-// scratch, behind the caller's stream and, when something was written, ahead of what the caller queues next.  The
-// call's 102 width words lie where that scratch keeps a chunk's window lengths, which neither kernel needs.
-namespace {
-
-// Every record checked on the device and the widths of the columns reduced over all of them into need[ HA_MAX_COLS ]
-// (n_hits > 0, hit_structures_args has passed): one synchronisation.
-int hit_alignment_widths( rma_scanner_t *sc, const rma_db *db, const int32_t *d_hits, int64_t n_hits, void *stream, int32_t *need,
-	char *err, size_t errlen )
-{
-	rma::HitWindowScratch	*s = sc->hs_win;
-	hipStream_t	st = s->stream;
-	const int	stride = rma_hit_stride( &sc->prog );
-	const rma::HitWinShape	shape = rma::hitwin_shape( sc->prog );
-	int32_t	*d_w = reinterpret_cast<int32_t *>( s->d_len ), *h_w = reinterpret_cast<int32_t *>( s->h_off );
-	// behind the caller's work on its stream (the records) and the database's tables
-	if( stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
-		return 1;
-	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
-	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
-	HIPCHK( hipMemsetAsync( d_w, 0, rma::HA_MAX_COLS * sizeof( int32_t ), st ) );
-	HIPCHK( rma::hit_spans( d_hits, n_hits, stride, shape, db->d_slen, db->d_text_start, db->n_seq, nullptr, nullptr, nullptr, s->d_bad, st ) );
-	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
-		HIPCHK( rma::hit_align_widths( d_hits + c0 * stride, std::min( HW_CHUNK, n_hits - c0 ), stride, shape, d_w, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipMemcpyAsync( h_w, d_w, rma::HA_MAX_COLS * sizeof( int32_t ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipStreamSynchronize( st ) );
-	if( s->h_bad[ 0 ] != ~0ull )
-		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), nullptr, "written", err, errlen );
-	memcpy( need, h_w, rma::HA_MAX_COLS * sizeof( int32_t ) );
-	return 0;
-}
-
-}	// namespace
-
-extern "C" int rma_hit_alignment_shape( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
-	int32_t *n_cols, int32_t *widths, uint8_t *right, int64_t *row_bytes, void *stream, char *err, size_t errlen )
-{
-	const char	*who = "rma_hit_alignment_shape";
-	if( sc == nullptr || n_cols == nullptr || widths == nullptr || row_bytes == nullptr ){
-		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "room for the shape" );
-		return 1;
-	}
-	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
-		return 1;
-	int32_t	need[ rma::HA_MAX_COLS ];
-	memset( need, 0, sizeof( need ) );
-	if( n_hits > 0 && hit_alignment_widths( sc, db, d_hits, n_hits, stream, need, err, errlen ) )
-		return 1;
-	const int	nc = rma::hitalign_n_cols( rma::hitwin_shape( sc->prog ) );
-	*n_cols = nc;
-	if( right != nullptr )
-		rma::hitalign_directions( sc->prog, right );
-	int64_t	w = nc - 1;
-	for( int c = 0; c < rma::HA_MAX_COLS; c++ ){
-		widths[ c ] = c < nc ? need[ c ] : 0;
-		w += widths[ c ];
-	}
-	*row_bytes = w;
-	return 0;
-}
-
-extern "C" int rma_hit_alignment( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
-	const int32_t *widths, const uint8_t *letters, const uint8_t *fill, uint8_t *d_rows, int32_t *d_pos,
-	void *stream, char *err, size_t errlen )
-{
-	const char	*who = "rma_hit_alignment";
-	if( sc == nullptr || widths == nullptr ){
-		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "widths" );
-		return 1;
-	}
-	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
-		return 1;
-	const int	nc = rma::hitalign_n_cols( rma::hitwin_shape( sc->prog ) );
-	for( int c = 0; c < nc; c++ )
-		if( widths[ c ] < 0 ){
-			snprintf( err, errlen, "%s: column %d: width %d: nothing written", who, c, widths[ c ] );
-			return 1;
-		}
-	static const uint8_t	tool_fill[ 3 ] = { '-', '|', '.' };
-	const rma::HitAlignLayout	lay = rma::hitalign_layout( sc->prog, widths, fill != nullptr ? fill : tool_fill );
-	const int64_t	W = lay.row_bytes;
-	if( n_hits == 0 )
-		return 0;
-	if( d_rows == nullptr || W > INT64_MAX / 16 / n_hits ){
-		snprintf( err, errlen, "%s: %lld rows of %lld bytes: bad arguments", who, ( long long )n_hits, ( long long )W );
-		return 1;
-	}
-	// the outputs: the caller's, each inside its allocation on the scanner's device
-	if( W > 0 && ( check_device_bytes( d_rows, sc->device, 0, n_hits * W, "the rows", err, errlen ) ||
-		( d_pos != nullptr && check_device_bytes( d_pos, sc->device, 0, n_hits * W * 4, "the positions", err, errlen ) ) ) )
-		return 1;
-	rma::HitWindowScratch	*s = sc->hs_win;
-	hipStream_t	st = s->stream, caller = static_cast<hipStream_t>( stream );
-	// the letters, as rma_hit_structures takes them: on their way ahead of the check, whose synchronisation leaves the
-	// page-locked copy free for the next call
-	const uint8_t	*tab = s->d_tab;
-	int	codes = 0;
-	if( letters != nullptr )
-		memcpy( s->h_tab, letters, 256 );
-	else if( db->default_table )
-		for( int b = 0; b < 256; b++ )
-			s->h_tab[ b ] = rma::hitwin_reader_letter( static_cast<unsigned char>( b ) );
-	else{
-		tab = db->d_table;
-		codes = 1;
-	}
-	if( tab == s->d_tab )
-		HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, st ) );
-	int32_t	need[ rma::HA_MAX_COLS ];
-	if( hit_alignment_widths( sc, db, d_hits, n_hits, stream, need, err, errlen ) )
-		return 1;
-	for( int c = 0; c < nc; c++ )
-		if( widths[ c ] < need[ c ] ){
-			snprintf( err, errlen, "%s: column %d: width %d given, the records need %d: nothing written", who, c, widths[ c ], need[ c ] );
-			return 1;
-		}
-	const int	stride = rma_hit_stride( &sc->prog );
-	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
-		HIPCHK( rma::hit_align_fill( db->text, d_hits + c0 * stride, std::min( HW_CHUNK, n_hits - c0 ), stride, rma::hitwin_shape( sc->prog ), lay,
-			db->d_slen, db->d_text_start, tab, codes, d_rows + c0 * W, d_pos != nullptr ? d_pos + c0 * W : nullptr, st ) );
-	return stream_after( caller, st, err, errlen );
-}
-
-// ---------------------------------------------------------------- rmprune's rule over records on the device
-// rma_prune_hits(): the kernels of rm_prune_dev.hip on the caller's stream.  The scratch -- the program's table, a
-// call's keys, flags and list of blocks, the entries' name groups -- is the scanner's, made on the first call and
-// grown; a later call on another stream waits for the kernels of the one before it (pr_done).  One wait, for two
-// words: the least index of a refused record and the number of blocks, which sizes the last launch.
-extern "C" int rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
-	const int32_t *group_of_entry, uint8_t *d_keep, void *stream, char *err, size_t errlen )
-{
-	const char	*who = "rma_prune_hits";
-	if( sc == nullptr || db == nullptr ){
-		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : "database" );
-		return 1;
-	}
-	const int	stride = rma_hit_stride( &sc->prog );
-	const rma::PruneTable	tab = rma::prune_table( sc->prog );
-	const int	row = rma::prune_row_words( tab );
-	if( n_hits < 0 || ( n_hits > 0 && ( d_hits == nullptr || d_keep == nullptr ) ) || n_hits > INT64_MAX / 16 / std::max( stride, row ) ){
-		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )n_hits );
-		return 1;
-	}
-	if( db->device != sc->device ){
-		snprintf( err, errlen, "%s: the database is on device %d, the scanner on device %d", who, db->device, sc->device );
-		return 1;
-	}
-	HIPCHK( hipSetDevice( sc->device ) );
-	if( n_hits == 0 )
-		return 0;
-	if( check_device_bytes( d_hits, sc->device, 0, n_hits * stride * 4, "the records", err, errlen ) ||
-		check_device_bytes( d_keep, sc->device, 0, n_hits, "the keep flags", err, errlen ) )
-		return 1;
-	hipStream_t	st = static_cast<hipStream_t>( stream );
-	if( sc->d_pr_table == nullptr ){
-		const size_t	at = align256( sizeof( rma::PruneTable ) );
-		void	*p = nullptr;
-		HIPCHK( hipMalloc( &p, at + 256 ) );
-		sc->d_pr_table = static_cast<rma::PruneTable *>( p );
-		HIPCHK( hipMemcpy( sc->d_pr_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
-		HIPCHK( hipEventCreateWithFlags( &sc->pr_done, hipEventDisableTiming ) );
-		HIPCHK( hipEventRecord( sc->pr_done, st ) );
-	}
-	// behind the kernels of the call before this one (they read the scratch) and the database's tables
-	HIPCHK( hipStreamWaitEvent( st, sc->pr_done, 0 ) );
-	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
-	const size_t	n = size_t( n_hits ), parts = size_t( rma::prune_parts( n_hits ) );
-	const size_t	o_rows = align256( n * 16 ), o_bflag = o_rows + align256( n * size_t( row ) * 4 ), o_part = o_bflag + align256( n ),
-		o_part_x = o_part + align256( parts * 8 ), o_blocks = o_part_x + align256( parts * 8 ), total = o_blocks + align256( n * 8 );
-	HIPCHK( dev_room( &sc->d_pr, &sc->pr_bytes, total ) );
-	HIPCHK( host_room( &sc->h_pr, &sc->h_pr_bytes, 256 ) );
-	char	*d = static_cast<char *>( sc->d_pr ), *dt = reinterpret_cast<char *>( sc->d_pr_table ) + align256( sizeof( rma::PruneTable ) );
-	rma::PruneDev	pd;
-	pd.tab = sc->d_pr_table;
-	pd.groups = nullptr;
-	pd.hdr = reinterpret_cast<int32_t *>( d );
-	pd.rows = reinterpret_cast<int32_t *>( d + o_rows );
-	pd.bflag = reinterpret_cast<uint8_t *>( d + o_bflag );
-	pd.part = reinterpret_cast<long long *>( d + o_part );
-	pd.part_x = reinterpret_cast<long long *>( d + o_part_x );
-	pd.blocks = reinterpret_cast<long long *>( d + o_blocks );
-	pd.bad = reinterpret_cast<unsigned long long *>( dt );
-	pd.n_blocks = reinterpret_cast<long long *>( dt + 8 );
-	if( group_of_entry != nullptr && db->n_seq > 0 ){
-		// (pageable memory: the copy has left the caller's array when the call returns)
-		HIPCHK( dev_room( &sc->d_pr_groups, &sc->pr_groups_bytes, size_t( db->n_seq ) * 4 ) );
-		HIPCHK( hipMemcpyAsync( sc->d_pr_groups, group_of_entry, size_t( db->n_seq ) * 4, hipMemcpyHostToDevice, st ) );
-		pd.groups = static_cast<const int32_t *>( sc->d_pr_groups );
-	}
-	HIPCHK( hipMemsetAsync( pd.bad, 0xff, sizeof( unsigned long long ), st ) );
-	HIPCHK( hipMemsetAsync( pd.n_blocks, 0, sizeof( long long ), st ) );
-	HIPCHK( rma::prune_blocks( d_hits, n_hits, stride, rma::hitwin_shape( sc->prog ), row, db->d_slen, db->n_seq, pd, st ) );
-	unsigned long long	*h = static_cast<unsigned long long *>( sc->h_pr );
-	HIPCHK( hipMemcpyAsync( h, pd.bad, 16, hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipStreamSynchronize( st ) );
-	if( h[ 0 ] != ~0ull ){
-		if( scratch_on( &sc->hs_win, sc->device, err, errlen ) )
-			return 1;
-		return bad_record( sc->hs_win, db, sc->prog, d_hits, int64_t( h[ 0 ] ), nullptr, "judged", err, errlen );
-	}
-	const int64_t	n_blocks = int64_t( h[ 1 ] );
-	if( n_blocks < 1 || n_blocks > n_hits ){
-		snprintf( err, errlen, "%s: %lld blocks of %lld records (records changed during the call?)", who, ( long long )n_blocks, ( long long )n_hits );
-		return 1;
-	}
-	HIPCHK( rma::prune_rezip( n_hits, row, pd, n_blocks, d_keep, st ) );
-	HIPCHK( hipEventRecord( sc->pr_done, st ) );
-	return 0;
-}
 
 // ---------------------------------------------------------------- pinned host memory
 // A packed database in memory whose words are page-locked uploads by DMA, without a staging copy,
@@ -2277,13 +1535,13 @@ extern "C" int rma_scan_records_to_device( rma_scanner_t *sc, int32_t *dst, int6
 	if( words == 0 )
 		return 0;
 	HIPCHK( hipSetDevice( sc->device ) );
-	if( check_device_bytes( dst, sc->device, 0, words * 4, "the destination", err, errlen ) )
+	if( rma::check_device_bytes( dst, sc->device, 0, words * 4, "the destination", err, errlen ) )
 		return 1;
 	hipStream_t	caller = static_cast<hipStream_t>( stream );
-	if( stream_after( sc->stream, caller, err, errlen ) )
+	if( rma::stream_after( sc->stream, caller, err, errlen ) )
 		return 1;
 	HIPCHK( hipMemcpyAsync( dst, sc->d_last, size_t( words ) * 4, hipMemcpyDeviceToDevice, sc->stream ) );
-	return stream_after( caller, sc->stream, err, errlen );
+	return rma::stream_after( caller, sc->stream, err, errlen );
 }
 
 // One scan of eight start positions, so that what the runtime sets up on first use (code objects of
@@ -2334,13 +1592,3 @@ extern "C" int rma_scanner_warmup( rma_scanner_t *sc, char *err, size_t errlen )
 	sc->opt = keep;
 	return rc;
 }
-
-// ---------------------------------------------------------------- for rm_gather.cpp
-int rma_scanner_device( const rma_scanner_t *sc ) { return sc->device; }
-hipStream_t rma_scanner_stream( const rma_scanner_t *sc ) { return sc->stream; }
-int rma_scanner_stride( const rma_scanner_t *sc ) { return sc->dprog.hit_stride; }
-void rma_scanner_last( const rma_scanner_t *sc, const int32_t **d_hits, int64_t *n ) { *d_hits = sc->d_last; *n = sc->n_last; }
-// where the last scan's ordered records are: 0 no scan has ended, 1 in HBM (d_last; also a scan without records), 2 on the host only
-int rma_scanner_last_state( const rma_scanner_t *sc ) { return sc->last_state; }
-bool rma_scanner_last_relabelled( const rma_scanner_t *sc ) { return sc->last_relabelled; }
-void rma_scanner_set_relabelled( rma_scanner_t *sc ) { sc->last_relabelled = true; }
