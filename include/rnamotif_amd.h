@@ -69,7 +69,7 @@ int	rma_scanner_create( const rma_program_t *prog, const rma_efndata_t *efn, int
 int	rma_scanner_set_efn2data( rma_scanner_t *sc, const rma_efn2data_t *efn2, char *err, size_t errlen );
 /* Launch-shape and diagnostic switches (DESIGN.md has the table).  The RNAMOTIF_* environment is read
  * once, by rma_scanner_create(); the switches that may change between scans change through this call
- * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "flush", "efn_light", "host_sort", "timing", "short".
+ * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "struct_wgs", "flush", "efn_light", "host_sort", "timing", "short".
  * None of them changes the records a scan returns. */
 int	rma_scanner_set_option( rma_scanner_t *sc, const char *name, int value, char *err, size_t errlen );
 /* One scan of eight start positions, thrown away: what the runtime sets up on first use (code objects,
@@ -400,6 +400,38 @@ int	rma_hit_alignment( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_h
 int	rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
 		const int32_t *group_of_entry /* host, n_seq, or NULL */, uint8_t *d_keep /* n_hits */,
 		void *stream, char *err, size_t errlen );
+
+/* ---- energies of structures in device tensors: efn() and efn2() of any batch of structures, as the reference's
+ * efn_drv and efn2_drv give them for a .ct file (csrc/rm_structenergy.h has the rule, shared by the host and the
+ * kernels).  The tables are the scanner's: a descriptor's own (rma_scanner_create, rma_scanner_set_efn2data), or
+ * those rma_scanner_load_energy_tables() reads from dir (rma_efndata_load / rma_efn2data_load; which: 1 efn, 2 efn2,
+ * 3 both) and uploads the same way, so that a scanner whose descriptor has no efn() in its score section can evaluate
+ * structures.  Loading changes no scan (a scan's energy kernel runs for the descriptor's call sites only); tables
+ * loaded again replace those that are there; the call is refused while a scan is in flight.
+ * Structure s is the bases [ off[ s ], off[ s + 1 ] ) of d_base and d_pair.  d_base holds letters, as
+ * rma_hit_structures' base; letters: 256 bytes, byte -> letter, or NULL for the readers' letters; a c g t/u in either
+ * case are codes 0..3, every other letter is ambiguous.  d_pair[ ( off[ s ] + i ) * pair_stride ] is the index inside
+ * the structure of the base that i pairs with, or -1 -- rma_hit_structures' mate: with pair_stride 3, column 0 of a
+ * mate tensor is read in place.  Pairs are taken as given, as the drivers take a .ct file: no pair set filters them.
+ * d_efn / d_efn2 (either may be NULL) receive the energies in 1/100 kcal/mol, as the efn words of a hit record:
+ * RMA_EFN_INFINITY / RMA_EFN2_INFINITY where the cores say so, for a structure of no bases, for a structure with
+ * crossing pairs and for one with a pair (i, i+1), which closes no loop.  Asking for an energy whose tables the
+ * scanner does not have is an error before anything is launched.
+ * Pointers are checked as rma_hit_structures checks its outputs.  Every structure is checked on the device, in one
+ * kernel with one wait, before any energy is computed: off[ 0 ] == 0, off ascending, off[ n ] == total; at most 8191
+ * bases (RMA_EFN_LOGINC - 1: no loop size is ever clamped); every partner -1 or inside its structure, not the base
+ * itself, and returned by its partner; at most 50 helices, a pair (i, j) opening a new helix unless (i-1, j+1) is a
+ * pair.  A bad structure fails the call, naming the lowest bad structure's index and the reason, and nothing is
+ * written.  n == 0 does nothing.  The kernels are queued on `stream` (the caller's hipStream_t, NULL = the default
+ * stream) behind what is queued there now and ahead of what is queued there next; the call returns without waiting
+ * for the energy kernel.  Scratch (512 bytes + 4 per structure) is the scanner's, made on the first call and grown.
+ * Option "struct_wgs" (rma_scanner_set_option) sets the number of workgroups of the kernels, 0 for the default. */
+int	rma_scanner_load_energy_tables( rma_scanner_t *sc, const char *dir, int which /* 1 efn, 2 efn2, 3 both */,
+		char *err, size_t errlen );
+int	rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off /* n+1 */, const uint8_t *d_base /* total */,
+		const int32_t *d_pair /* total * pair_stride */, int32_t pair_stride, int64_t n, int64_t total,
+		const uint8_t *letters /* 256, host, or NULL */,
+		int32_t *d_efn /* n or NULL */, int32_t *d_efn2 /* n or NULL */, void *stream, char *err, size_t errlen );
 
 #ifdef __cplusplus
 }

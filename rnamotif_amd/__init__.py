@@ -151,6 +151,8 @@ def lib() -> C.CDLL:
     L.rma_descr_names.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.rma_descr_names.restype = C.c_size_t
     L.rma_prune_hits.argtypes = [vp, vp, vp, C.c_int64, i32p, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_scanner_load_energy_tables.argtypes = [vp, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.rma_structure_energies.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_program_loose.argtypes = [vp]
     L.rma_program_loose.restype = C.c_int
     _lib = L
@@ -482,6 +484,10 @@ class HitStructures:
         mate[mask] = self.mate[at]
         return base, elem, mate, mask
 
+    def energies(self, scanner: "Scanner", letters: Optional[bytes] = None, efn: bool = True, efn2: bool = True):
+        """Scanner.structure_energies() of these windows, each taken whole: column 0 of mate read in place."""
+        return scanner.structure_energies(self.off, self.base, self.mate, letters=letters, efn=efn, efn2=efn2)
+
 
 class HitAlignment:
     """Scanner.align()'s result: n records laid into the columns of an alignment, as `rmfmt -a` lays their printed form.
@@ -738,6 +744,60 @@ class Scanner:
             # (the records are read by a kernel queued on this stream: torch keeps their memory until it has run)
             hits.record_stream(stream)
         return keep
+
+    def load_energy_tables(self, dir: str = EFNDATA_DIR, efn: bool = True, efn2: bool = True) -> None:
+        """The tables of efn() and / or efn2() from a directory onto the scanner's GPU (rma_scanner_load_energy_tables),
+        for structure_energies() of a scanner whose descriptor has no such call in its score section.  No scan changes."""
+        which = (1 if efn else 0) | (2 if efn2 else 0)
+        if which:
+            err = C.create_string_buffer(_ERRLEN)
+            _check(lib().rma_scanner_load_energy_tables(self._h, os.fsencode(dir), which, err, _ERRLEN), err)
+
+    def structure_energies(self, off, base, pair, letters: Optional[bytes] = None, efn: bool = True, efn2: bool = True):
+        """efn() and efn2() of a batch of structures in tensors on the scanner's GPU (rma_structure_energies; the rule is
+        csrc/rm_structenergy.h's), as the reference's efn_drv and efn2_drv give them for a .ct file: (efn, efn2), int32
+        tensors [n] in 1/100 kcal/mol, None for an energy not asked for; 16000 / 9999999 where the energy is infinite
+        (also: no bases, crossing pairs, a pair (i, i+1)).  off: int64 [n+1], structure s is [off[s], off[s+1]) of
+        base and pair; base: uint8 / int8 [T] letters (letters: 256 bytes, byte -> letter, default the readers');
+        pair: int32, [T] -- any stride -- or [T, k] whose column 0 is read in place: the index inside its structure
+        of the base each base pairs with, or -1, as HitStructures.mate.  Pairs are taken as given.  The tables are
+        the descriptor's or those of load_energy_tables().  The tensors are ready on torch's current stream; the call
+        waits once, for the check of every structure.  A malformed structure is refused (RnamotifError naming the
+        lowest bad index and the reason) before anything is written."""
+        import torch
+        for name, t, dtypes in (("off", off, (torch.int64,)), ("base", base, (torch.uint8, torch.int8)), ("pair", pair, (torch.int32,))):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} is a {type(t).__name__}, not a torch.Tensor")
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+                raise ValueError(f"{name} is on {t.device}: the scanner is on cuda:{self.device}")
+            if t.dtype not in dtypes:
+                raise TypeError(f"{name} is {t.dtype}: {' or '.join(str(d) for d in dtypes)} is needed")
+        if off.ndim != 1 or off.numel() < 1:
+            raise ValueError(f"off has shape {tuple(off.shape)}: [n + 1] offsets are needed")
+        if base.ndim != 1 or pair.ndim not in (1, 2) or int(pair.shape[0]) != int(base.shape[0]) or (pair.ndim == 2 and int(pair.shape[1]) < 1):
+            raise ValueError(f"base has shape {tuple(base.shape)}, pair {tuple(pair.shape)}: [T] letters and [T] or [T, k] partners are needed")
+        if letters is not None and len(letters) != 256:
+            raise ValueError(f"letters: 256 bytes are needed, not {len(letters)}")
+        off, base = off.contiguous(), base.contiguous()
+        n, total = int(off.shape[0]) - 1, int(base.shape[0])
+        stride = int(pair.stride(0)) if total > 1 else 1
+        if total > 1 and stride < 1:
+            pair = pair.contiguous()
+            stride = int(pair.stride(0))
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(dev)
+        e = torch.empty(n, dtype=torch.int32, device=dev) if efn else None
+        e2 = torch.empty(n, dtype=torch.int32, device=dev) if efn2 else None
+        if n:
+            err = C.create_string_buffer(_ERRLEN)
+            _check(lib().rma_structure_energies(self._h, off.data_ptr(), base.data_ptr() if total else None,
+                                                pair.data_ptr() if total else None, stride, n, total, letters,
+                                                e.data_ptr() if efn else None, e2.data_ptr() if efn2 else None,
+                                                cur.cuda_stream, err, _ERRLEN), err)
+            # (the tensors are read by kernels queued on this stream: torch keeps their memory until those have run)
+            for t in (off, base, pair):
+                t.record_stream(cur)
+        return e, e2
 
     def set_option(self, name: str, value: int) -> None:
         """A launch-shape / diagnostic switch between scans (rma_scanner_set_option); the RNAMOTIF_*

@@ -1,6 +1,8 @@
 // rm_hitpost.cpp -- the calls of the C ABI (include/rnamotif_amd.h) that consume hit records already on the device,
 // on the host: rma_hit_windows (the device half of rma_replay_device), rma_hit_structures, rma_hit_alignment and
 // rma_prune_hits.  Their kernels are rm_hitwin_dev.hip, rm_hitstruct_dev.hip, rm_hitalign_dev.hip and rm_prune_dev.hip.
+// Behind them rma_structure_energies (rm_structenergy_dev.hip), which consumes what rma_hit_structures makes -- or any
+// structures in device memory -- and rma_scanner_load_energy_tables, which gives a scanner the tables for it.
 // Of a scan they need nothing: a scanner's program and device, a database's tables and text (rm_scanner_impl.h), and
 // scratch of their own.  What they all do first is written once:
 //   record_call_args    the database, the records and the device refused or accepted
@@ -15,6 +17,11 @@
 #include "rm_hitwin_dev.h"
 #include "rm_hitstruct_dev.h"
 #include "rm_hitalign_dev.h"
+#include "rm_efndata.h"
+#define RMD_FN		static inline
+#define RMD_FN_MEMBER	inline
+#include "rm_structenergy.h"
+#include "rm_structenergy_dev.h"
 
 namespace {
 // records of a call go through the kernels HW_CHUNK at a time; windows come to the host (rma_hit_windows) in pieces
@@ -82,6 +89,11 @@ struct rma::HitPost {
 	void	*d_pr = nullptr, *d_pr_groups = nullptr, *h_pr = nullptr;
 	size_t	pr_bytes = 0, pr_groups_bytes = 0, h_pr_bytes = 0;
 	hipEvent_t	pr_done = nullptr;
+	// rma_structure_energies: two result words and the 256 codes of a call's bytes (device and page-locked), the info
+	// word of every structure of a call, and the event behind the last call's kernels
+	void	*d_se = nullptr, *h_se = nullptr, *d_se_info = nullptr;
+	size_t	se_info_bytes = 0;
+	hipEvent_t	se_done = nullptr;
 };
 
 // (the scanner's device is current; the scratch stream is synchronised before anything is freed)
@@ -97,6 +109,11 @@ void rma::hitpost_free( HitPost *p )
 	( void )hipHostFree( p->h_pr );
 	if( p->pr_done )
 		( void )hipEventDestroy( p->pr_done );
+	( void )hipFree( p->d_se );
+	( void )hipFree( p->d_se_info );
+	( void )hipHostFree( p->h_se );
+	if( p->se_done )
+		( void )hipEventDestroy( p->se_done );
 	delete p;
 }
 
@@ -645,5 +662,192 @@ extern "C" int rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int3
 	}
 	HIPCHK( rma::prune_rezip( n_hits, row, pd, n_blocks, d_keep, st ) );
 	HIPCHK( hipEventRecord( p.pr_done, st ) );
+	return 0;
+}
+
+// ---------------------------------------------------------------- energies of structures in device tensors
+// rma_scanner_load_energy_tables(): efn's and efn2's tables from a directory onto the scanner's device, where
+// rma_scanner_create() and rma_scanner_set_efn2data() put a descriptor's.  No scan changes: the scan's energy kernel is
+// launched for a descriptor's call sites only (rm_scanner.cpp launch_efn), and a descriptor with call sites has its
+// tables from the start; tables loaded again replace the ones that are there.
+extern "C" int rma_scanner_load_energy_tables( rma_scanner_t *sc, const char *dir, int which, char *err, size_t errlen )
+{
+	const char	*who = "rma_scanner_load_energy_tables";
+	if( sc == nullptr || which < 1 || which > 3 ){
+		snprintf( err, errlen, "%s: %s", who, sc == nullptr ? "no scanner" : "which: 1 (efn), 2 (efn2) or 3 (both)" );
+		return 1;
+	}
+	if( sc->fly.db != nullptr ){
+		snprintf( err, errlen, "%s: a scan is in flight (rma_scan_begin without rma_scan_end): its energy kernel reads the tables", who );
+		return 1;
+	}
+	// (read first: a directory without the files leaves the scanner as it was)
+	std::unique_ptr<rma_efndata_t>	efn;
+	std::unique_ptr<rma_efn2data_t>	efn2;
+	if( which & 1 ){
+		efn.reset( new rma_efndata_t );
+		if( rma_efndata_load( dir, efn.get(), err, errlen ) )
+			return 1;
+	}
+	if( which & 2 ){
+		efn2.reset( new rma_efn2data_t );
+		if( rma_efn2data_load( dir, efn2.get(), err, errlen ) )
+			return 1;
+	}
+	HIPCHK( hipSetDevice( sc->device ) );
+	// (behind the energy kernels of rma_structure_energies calls that read the tables now)
+	if( sc->post != nullptr && sc->post->se_done != nullptr )
+		HIPCHK( hipEventSynchronize( sc->post->se_done ) );
+	if( efn ){
+		std::vector<int16_t>	t16;
+		std::vector<int32_t>	tlkey;
+		rma::efn_tables16( efn.get(), t16, tlkey );
+		if( sc->d_t16 == nullptr )
+			HIPCHK( hipMalloc( &sc->d_t16, t16.size() * sizeof( int16_t ) ) );
+		HIPCHK( hipMemcpy( sc->d_t16, t16.data(), t16.size() * sizeof( int16_t ), hipMemcpyHostToDevice ) );
+		if( sc->d_tlkey == nullptr )
+			HIPCHK( hipMalloc( &sc->d_tlkey, tlkey.size() * sizeof( int32_t ) ) );
+		HIPCHK( hipMemcpy( sc->d_tlkey, tlkey.data(), tlkey.size() * sizeof( int32_t ), hipMemcpyHostToDevice ) );
+		if( sc->d_loginc == nullptr )
+			HIPCHK( hipMalloc( &sc->d_loginc, RMA_EFN_LOGINC * sizeof( int32_t ) ) );
+		HIPCHK( hipMemcpy( sc->d_loginc, efn->loginc, RMA_EFN_LOGINC * sizeof( int32_t ), hipMemcpyHostToDevice ) );
+		sc->have_efn = true;
+	}
+	if( efn2 && rma_scanner_set_efn2data( sc, efn2.get(), err, errlen ) )
+		return 1;
+	return 0;
+}
+
+namespace {
+
+constexpr size_t	SE_CODES_AT = 256;		// the codes behind the two result words, in both fixed blocks
+
+// the words of a refusal: structure s judged again on the host, by the rule the kernel applied (rm_structenergy.h)
+int bad_structure( const rma::StructBatch &b, int64_t s, hipStream_t st, char *err, size_t errlen )
+{
+	const char	*who = "rma_structure_energies";
+	int64_t	o[ 2 ];
+	HIPCHK( hipMemcpyAsync( o, b.off + s, sizeof( o ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	const long long	lo = o[ 0 ], hi = o[ 1 ], ls = s;
+	const char	*nothing = "nothing written";
+	switch( rmse_check_offsets( lo, hi, s, b.n, b.total ) ){
+	case RMSE_OK :
+		break;
+	case RMSE_OFF_FIRST :
+		snprintf( err, errlen, "%s: structure %lld: off[ 0 ] is %lld, not 0: %s", who, ls, lo, nothing );
+		return 1;
+	case RMSE_OFF_DECREASES :
+		snprintf( err, errlen, "%s: structure %lld: off decreases from %lld to %lld: %s", who, ls, lo, hi, nothing );
+		return 1;
+	case RMSE_OFF_OUTSIDE :
+		snprintf( err, errlen, "%s: structure %lld: bases [%lld, %lld) outside the %lld of `total`: %s", who, ls, lo, hi, ( long long )b.total, nothing );
+		return 1;
+	case RMSE_OFF_LAST :
+		snprintf( err, errlen, "%s: structure %lld: off[ n ] is %lld, not the %lld of `total`: %s", who, ls, hi, ( long long )b.total, nothing );
+		return 1;
+	default :
+		snprintf( err, errlen, "%s: structure %lld: %lld bases, more than %d: %s", who, ls, hi - lo, RMSE_MAX_BASES, nothing );
+		return 1;
+	}
+	const int	len = int( hi - lo );
+	std::vector<int32_t>	pair( size_t( std::max( len, 1 ) ) );
+	if( len > 0 ){
+		HIPCHK( hipMemcpy2DAsync( pair.data(), 4, b.pair + lo * b.pair_stride, size_t( b.pair_stride ) * 4, 4, size_t( len ), hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipStreamSynchronize( st ) );
+	}
+	const rmse_pairs_t	view{ pair.data(), 1 };
+	int	which = 0, info = 0;
+	switch( rmse_check_structure( view, len, &which, &info ) ){
+	case RMSE_PAIR_RANGE :
+		snprintf( err, errlen, "%s: structure %lld: base %d pairs with %d, outside its %d bases: %s", who, ls, which, pair[ size_t( which ) ], len, nothing );
+		return 1;
+	case RMSE_PAIR_SELF :
+		snprintf( err, errlen, "%s: structure %lld: base %d pairs with itself: %s", who, ls, which, nothing );
+		return 1;
+	case RMSE_PAIR_ASYM :
+		snprintf( err, errlen, "%s: structure %lld: base %d pairs with %d, which pairs with %d: %s", who, ls, which, pair[ size_t( which ) ],
+			pair[ size_t( pair[ size_t( which ) ] ) ], nothing );
+		return 1;
+	case RMSE_HELICES :
+		snprintf( err, errlen, "%s: structure %lld: %d helices, more than %d: %s", who, ls, which, RMSE_MAX_HELICES, nothing );
+		return 1;
+	default :
+		snprintf( err, errlen, "%s: structure %lld: refused on the device, not on the host (tensors changed during the call?)", who, ls );
+		return 1;
+	}
+}
+
+}	// namespace
+
+// rma_structure_energies(): the kernels of rm_structenergy_dev.hip on the caller's stream -- the check of every
+// structure, one wait for its two words (the least index of a refused structure, whether some structure needs the
+// large stacks), then the energy kernel's one or two instances, for which the call does not wait.  The scratch -- the
+// two words, the codes of the call's bytes, an info word per structure -- is the scanner's, made on the first call and
+// grown; a later call on another stream waits for the kernels of the one before it (se_done).
+extern "C" int rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off, const uint8_t *d_base, const int32_t *d_pair,
+	int32_t pair_stride, int64_t n, int64_t total, const uint8_t *letters, int32_t *d_efn, int32_t *d_efn2, void *stream,
+	char *err, size_t errlen )
+{
+	const char	*who = "rma_structure_energies";
+	if( sc == nullptr ){
+		snprintf( err, errlen, "%s: no scanner", who );
+		return 1;
+	}
+	// (( n + 1 ) * 8 bytes of offsets, total * pair_stride * 4 of partners)
+	if( n < 0 || total < 0 || pair_stride < 1 || n > INT64_MAX / 16 || total > INT64_MAX / 16 / pair_stride ||
+		( n > 0 && d_off == nullptr ) || ( n > 0 && total > 0 && ( d_base == nullptr || d_pair == nullptr ) ) ){
+		snprintf( err, errlen, "%s: %lld structures of %lld bases, partners every %d words: bad arguments", who, ( long long )n,
+			( long long )total, pair_stride );
+		return 1;
+	}
+	if( n == 0 )
+		return 0;
+	if( ( d_efn != nullptr && !sc->have_efn ) || ( d_efn2 != nullptr && sc->d_efn2 == nullptr ) ){
+		snprintf( err, errlen, "%s: the scanner has no %s tables: its descriptor has no such call, and rma_scanner_load_energy_tables() was not called",
+			who, d_efn != nullptr && !sc->have_efn ? "efn()" : "efn2()" );
+		return 1;
+	}
+	HIPCHK( hipSetDevice( sc->device ) );
+	if( rma::check_device_bytes( d_off, sc->device, 0, ( n + 1 ) * 8, "the offsets", err, errlen ) ||
+		( total > 0 && ( rma::check_device_bytes( d_base, sc->device, 0, total, "the bases", err, errlen ) ||
+			rma::check_device_bytes( d_pair, sc->device, 0, ( ( total - 1 ) * pair_stride + 1 ) * 4, "the partners", err, errlen ) ) ) ||
+		( d_efn != nullptr && rma::check_device_bytes( d_efn, sc->device, 0, n * 4, "the efn energies", err, errlen ) ) ||
+		( d_efn2 != nullptr && rma::check_device_bytes( d_efn2, sc->device, 0, n * 4, "the efn2 energies", err, errlen ) ) )
+		return 1;
+	rma::HitPost	&p = post_of( sc );
+	hipStream_t	st = static_cast<hipStream_t>( stream );
+	if( p.d_se == nullptr ){
+		HIPCHK( hipMalloc( &p.d_se, SE_CODES_AT + 256 ) );
+		HIPCHK( hipHostMalloc( &p.h_se, SE_CODES_AT + 256, hipHostMallocDefault ) );
+		HIPCHK( hipEventCreateWithFlags( &p.se_done, hipEventDisableTiming ) );
+		HIPCHK( hipEventRecord( p.se_done, st ) );
+	}
+	// behind the kernels of the call before this one: they read the scratch
+	HIPCHK( hipStreamWaitEvent( st, p.se_done, 0 ) );
+	HIPCHK( dev_room( &p.d_se_info, &p.se_info_bytes, size_t( n ) * 4 ) );
+	unsigned long long	*d_bad = static_cast<unsigned long long *>( p.d_se ), *h_bad = static_cast<unsigned long long *>( p.h_se );
+	uint8_t	*d_code = static_cast<uint8_t *>( p.d_se ) + SE_CODES_AT, *h_code = static_cast<uint8_t *>( p.h_se ) + SE_CODES_AT;
+	// (the page-locked copy is free: every call before this one has waited behind its upload)
+	for( int b = 0; b < 256; b++ )
+		h_code[ b ] = uint8_t( rmse_letter_code( letters != nullptr ? letters[ b ] : rma::hitwin_reader_letter( static_cast<unsigned char>( b ) ) ) );
+	HIPCHK( hipMemcpyAsync( d_code, h_code, 256, hipMemcpyHostToDevice, st ) );
+	HIPCHK( hipMemsetAsync( d_bad, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( d_bad + 1, 0, sizeof( unsigned long long ), st ) );
+	const rma::StructBatch	batch{ d_off, d_base, d_pair, pair_stride, n, total };
+	int32_t	*d_info = static_cast<int32_t *>( p.d_se_info );
+	const int	cus = sc->grid_blocks / 8, wgs = sc->opt.struct_wgs;
+	HIPCHK( rma::struct_check( batch, d_info, d_bad, wgs, cus, st ) );
+	HIPCHK( hipMemcpyAsync( h_bad, d_bad, 2 * sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( h_bad[ 0 ] != ~0ull )
+		return bad_structure( batch, int64_t( h_bad[ 0 ] ), st, err, errlen );
+	if( d_efn != nullptr || d_efn2 != nullptr ){
+		const rma::StructTables	t{ d_efn != nullptr ? sc->d_t16 : nullptr, sc->d_tlkey, sc->d_loginc, d_efn2 != nullptr ? sc->d_efn2 : nullptr, d_code };
+		HIPCHK( rma::struct_energies( batch, d_info, t, d_efn, d_efn2, 0, wgs, cus, st ) );
+		if( h_bad[ 1 ] != 0 )
+			HIPCHK( rma::struct_energies( batch, d_info, t, d_efn, d_efn2, 1, wgs, cus, st ) );
+	}
+	HIPCHK( hipEventRecord( p.se_done, st ) );
 	return 0;
 }

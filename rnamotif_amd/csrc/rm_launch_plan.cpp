@@ -25,6 +25,7 @@ void Options::latch()
 	glist = env_int( "RNAMOTIF_GLIST", 0 );
 	drain_waves = env_int( "RNAMOTIF_DRAIN_WAVES", 6 );
 	search_wgs = env_int( "RNAMOTIF_SEARCH_WGS", 0 );
+	struct_wgs = std::max( 0, env_int( "RNAMOTIF_STRUCT_WGS", 0 ) );
 	flush = env_int( "RNAMOTIF_FLUSH", -1 );
 	efn_light = env_int( "RNAMOTIF_EFN_LIGHT", -1 );
 	host_sort = env_int( "RNAMOTIF_HOSTSORT", 0 );
@@ -49,6 +50,7 @@ bool Options::set( const std::string &n, int value )
 	else if( n == "glist" ) glist = std::max( 0, value );
 	else if( n == "drain_waves" ) drain_waves = std::max( 0, value );
 	else if( n == "search_wgs" ) search_wgs = std::max( 0, value );
+	else if( n == "struct_wgs" ) struct_wgs = std::max( 0, value );
 	else if( n == "flush" ) flush = value;
 	else if( n == "efn_light" ) efn_light = value;
 	else if( n == "host_sort" ) host_sort = value;
