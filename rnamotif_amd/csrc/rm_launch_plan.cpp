@@ -404,9 +404,8 @@ int plan_launch( const LayoutKey &k, int64_t n_tiles, const ProgramPlan &pp, con
 		p.grid = std::min( p.grid, o.search_wgs * cus );
 	else if( p.walks_nothing )
 		// The instance that walks nothing is compiled for five workgroups a CU (96 registers, a fifth of the LDS) and runs
-		// FLUSH_WGS_PER_CU = 5.  Four measured the same (0.639 against 0.642 ms) and would leave the fifth's share -- 33 KB
-		// of LDS, a wave's registers on every SIMD -- to the drain kernel and the energy kernel of the scanner that had the
-		// step before (two scanners in turns).
+		// FLUSH_WGS_PER_CU = 5: option search_wgs at 3, 4 and 5 gives 0.900, 0.714 and 0.611 ms (trna.descr over 100 x 1 Mbase) --
+		// every wave more hides other waves' waits.
 		p.grid = std::min( p.grid, FLUSH_WGS_PER_CU * cus );
 	// (behind the search instance that walks nothing: workgroups of one wave that find room next to another scanner's search
 	// kernel -- the staged form's 136 KB of LDS wait until that kernel is through)

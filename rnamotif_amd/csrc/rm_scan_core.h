@@ -126,6 +126,62 @@ RMD_FN int rmd_clz64( uint64_t x )	// x != 0
 #endif
 }
 
+// ---------------------------------------------------------------- bit vectors
+// (of the pre-filters of rm_scan_kernel.h: a bit per tile position, 64 pad bits in front)
+RMD_FN uint32_t rmd_alignbit( uint32_t hi, uint32_t lo, uint32_t s )	// bits s .. s+31 of hi:lo, s < 32
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+	return __builtin_amdgcn_alignbit( hi, lo, s );
+#else
+	return uint32_t( ( ( uint64_t( hi ) << 32 ) | lo ) >> ( s & 31u ) );
+#endif
+}
+
+// 64 bits of a bit vector starting at bit q: three dwords through two v_alignbit_b32 (on the host: two 64-bit shifts)
+RMD_FN unsigned long long rmd_bits64( const unsigned long long *row, int q )
+{
+	const uint32_t	*r = reinterpret_cast<const uint32_t *>( row ) + ( q >> 5 );
+	const uint32_t	d0 = r[ 0 ], d1 = r[ 1 ], d2 = r[ 2 ];
+	const uint32_t	lo = rmd_alignbit( d1, d0, uint32_t( q & 31 ) );
+	const uint32_t	hi = rmd_alignbit( d2, d1, uint32_t( q & 31 ) );
+	return ( ( unsigned long long )hi << 32 ) | lo;
+}
+
+// 64 bits of a vector of vec_bits bits from bit x on; outside it: undecided, kept
+RMD_FN unsigned long long rmd_peek( const unsigned long long *v, int x, int vec_bits )
+{
+	return x >= 0 && x + 96 <= vec_bits ? rmd_bits64( v, x ) : ~0ull;
+}
+
+// The OR of rmd_peek( v, x + d ) over d = lo .. hi: bit i says that one of the bits x+lo+i .. x+hi+i of v
+// is set.  The in-range values of x + d are consecutive, so one of them is outside the vector exactly when
+// an end of the range is: all ones then.  Otherwise per chunk of up to 64 values of d two reads -- the
+// window's first 64 bits, and the 64 bits from its last d on, which hold the rest of what it needs and are
+// the furthest the loop over d would read -- and doubling shifts.  An empty range gives 0.
+RMD_FN unsigned long long rmd_or_window( const unsigned long long *v, int x, int lo, int hi, int vec_bits )
+{
+	if( hi < lo )
+		return 0ull;
+	if( x + lo < 0 || x + hi + 96 > vec_bits )
+		return ~0ull;
+	unsigned long long	r = 0;
+	for( int k = lo; k <= hi; k += 64 ){
+		const int	m = hi - k + 1 < 64 ? hi - k + 1 : 64;
+		unsigned long long	w0 = rmd_bits64( v, x + k ), w1 = 0;
+		if( m > 1 )
+			w1 = rmd_bits64( v, x + k + m - 1 ) >> ( 65 - m );		// bits 64 .. 62 + m of the window
+		// (bit i: any of the bits i .. i + m - 1 of w1:w0)
+		for( int have = 1; have < m; ){
+			const int	st = have < m - have ? have : m - have;
+			w0 |= ( w0 >> st ) | ( w1 << ( 64 - st ) );
+			w1 |= w1 >> st;
+			have += st;
+		}
+		r |= w0;
+	}
+	return r;
+}
+
 // ---------------------------------------------------------------- seq= constraints
 // step() semantics (regexp.c:389-664) as a set-of-positions automaton: after each
 // base, `act` holds the pattern positions that just consumed it.

@@ -429,16 +429,6 @@ struct LdsSplit {
 	}
 };
 
-// 64 bits of a bit vector starting at bit q: three dwords through two v_alignbit_b32
-__device__ inline unsigned long long bits64( const unsigned long long *row, int q )
-{
-	const uint32_t	*r = reinterpret_cast<const uint32_t *>( row ) + ( q >> 5 );
-	const uint32_t	d0 = r[ 0 ], d1 = r[ 1 ], d2 = r[ 2 ];
-	const uint32_t	lo = __builtin_amdgcn_alignbit( d1, d0, uint32_t( q & 31 ) );
-	const uint32_t	hi = __builtin_amdgcn_alignbit( d2, d1, uint32_t( q & 31 ) );
-	return ( ( unsigned long long )hi << 32 ) | lo;
-}
-
 // The tail test of rmd_lean_step() from the pre-filter's bit vectors.  pb[c][q] says "the base
 // at q pairs with 5' base c"; when the pair table is symmetric it also says "the base at q,
 // as the 5' partner, pairs with 3' base c".  For a tail helix that allows no mispair and must
@@ -474,7 +464,7 @@ struct TailAccel {
 			const int	q = z + s_lo + j - p_lo + 64;		// bit of 5' position s_lo + j
 			if( c3 > 4 || q < 0 || q + 64 > vec_bits )
 				return false;
-			m &= bits64( pb + c3 * pb_words, q );
+			m &= rmd_bits64( pb + c3 * pb_words, q );
 		}
 		*res = m != 0;
 		return true;
@@ -498,13 +488,13 @@ __device__ inline unsigned long long rows_win( const unsigned long long *rows5, 
 		W = ~0ull;
 		for( int h = 0; h < hl0 && W; h++ ){
 			const int	qq = w0 - h - p_lo + 64;	// bit index into the padded vector
-			W &= qq >= 0 ? bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull;
+			W &= qq >= 0 ? rmd_bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull;
 		}
 	}else{
 		unsigned long long	c1 = 0, c2 = 0, c3 = 0, c4 = 0, first = 0;	// >= 1/2/3/4 mispairs
 		for( int h = 0; h < hl0; h++ ){
 			const int	qq = w0 - h - p_lo + 64;
-			const unsigned long long	mis = ~( qq >= 0 ? bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull );
+			const unsigned long long	mis = ~( qq >= 0 ? rmd_bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull );
 			if( h == 0 )
 				first = mis;
 			c4 |= c3 & mis;
@@ -535,7 +525,7 @@ struct RowEnds {
 		if( stp.rows < 0 )
 			return false;
 		const int	w0 = top - 63, q_hi = w0 - p_lo + 64;
-		if( q_hi + 96 > vec_bits || s5 < p_lo )		// (bits64 reads three dwords from its first bit)
+		if( q_hi + 96 > vec_bits || s5 < p_lo )		// (rmd_bits64 reads three dwords from its first bit)
 			return false;
 		const int	lim = ( stp.ends & RMA_5PAIRED ) ? stp.mplim : ( stp.mplim > 1 ? stp.mplim : 1 );
 		*mask = rows_win( rows + 5 * stp.rows * pb_words, pb_words, tile, p_lo, stp.minlen, lim,
@@ -1448,7 +1438,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				const int	idx = x + P->lit_lo + k, m = rmd_imin( 64, n - k );
 				if( idx < 0 || ( idx >> 6 ) + 2 >= pb_words )
 					return ~0ull;
-				unsigned long long	lo = bits64( occ, idx ), hi = bits64( occ, idx + 64 );
+				unsigned long long	lo = rmd_bits64( occ, idx ), hi = rmd_bits64( occ, idx + 64 );
 				// (bit i: any of the bits i .. i + m - 1 of hi:lo)
 				for( int have = 1; have < m; ){
 					const int	st = rmd_imin( have, m - have );
@@ -1519,7 +1509,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					return ~0ull;
 				unsigned long long	c1 = 0, c2 = 0, c3 = 0, c4 = 0;
 				for( int q = 1; q < nmin; q++ ){
-					const unsigned long long	mis = ~bits64( gv, x + dir * q );
+					const unsigned long long	mis = ~rmd_bits64( gv, x + dir * q );
 					c4 |= c3 & mis;
 					c3 |= c2 & mis;
 					c2 |= c1 & mis;
@@ -1527,12 +1517,12 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				}
 				unsigned long long	ok = ~( badmax == 0 ? c1 : badmax == 1 ? c2 : badmax == 2 ? c3 : c4 );
 				if( first5 )
-					ok &= bits64( gv, x );
+					ok &= rmd_bits64( gv, x );
 				return ok;
 			};
 			// 64 bits of a finished vector from bit x on (outside it: undecided)
 			auto	peek = [ & ]( const unsigned long long *v, int x ) -> unsigned long long {
-				return x >= 0 && x + 96 <= vec_bits ? bits64( v, x ) : ~0ull;
+				return rmd_peek( v, x, vec_bits );
 			};
 			for( int wi = utid; wi < vec_words; wi += UNIT ){
 				const int	x = wi * 64;
@@ -1584,15 +1574,23 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			const int	vec_bits = vec_words * 64;
 			const unsigned	mat2 = rmd_pairsets( P )[ P->rowset_ps[ 0 ] ].mat2;
 			const int	nb = ( ( mat2 >> 20 ) & 31u ) || ( mat2 & 0x0108421u << 4 ) ? 5 : 4;		// (n pairs with nothing in the usual tables)
-			// 64 bits of a vector from bit x on; outside it: undecided, kept
-			auto	peek = [ & ]( const unsigned long long *v, int x ) -> unsigned long long {
-				return x >= 0 && x + 96 <= vec_bits ? bits64( v, x ) : ~0ull;
-			};
-			// the bases at x .. x+63 pair with the ones d further on
+			// the bases at x .. x+63 pair with the ones d further on; outside the vectors: undecided, kept
 			auto	pairs = [ & ]( int x, int d ) -> unsigned long long {
+				// (what peek() gives, with one test per side and every read from a place inside the vectors, so
+				// that the reads are issued together and answered by one wait instead of one each)
+				const bool	in5 = x >= 0 && x + 96 <= vec_bits, in3 = x + d >= 0 && x + d + 96 <= vec_bits;
+				const int	x5 = in5 ? x : 0, x3 = in3 ? x + d : 0;
+				const unsigned long long	out5 = in5 ? 0ull : ~0ull, out3 = in3 ? 0ull : ~0ull;
+				unsigned long long	v5[ 4 ], v3[ 4 ];
+				for( int b = 0; b < 4; b++ ){
+					v5[ b ] = rmd_bits64( tv + b * pb_words, x5 );
+					v3[ b ] = rmd_bits64( pb + b * pb_words, x3 );
+				}
 				unsigned long long	m = 0;
-				for( int b = 0; b < nb; b++ )
-					m |= peek( tv + b * pb_words, x ) & peek( pb + b * pb_words, x + d );
+				for( int b = 0; b < 4; b++ )
+					m |= ( v5[ b ] | out5 ) & ( v3[ b ] | out3 );
+				if( nb == 5 )
+					m |= ( rmd_bits64( tv + 4 * pb_words, x5 ) | out5 ) & ( rmd_bits64( pb + 4 * pb_words, x3 ) | out3 );
 				return m;
 			};
 			if( tid == 0 )
@@ -1625,17 +1623,11 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					unsigned long long	f = ~0ull;
 					if( sb.leaf ){
 						// ... which lie as far in as its helix is longer than the shortest
-						f = 0;
-						for( int t = 0; t <= sb.tmax && ~f; t++ )
-							f |= peek( core, x + t );
+						f = rmd_or_window( core, x, 0, sb.tmax, vec_bits );
 					}
-					if( k < C.n - 1 && f ){
-						// ... and the next group one of this group's lengths later
-						unsigned long long	r = 0;
-						for( int len = sb.len_lo; len <= sb.len_hi && ~r; len++ )
-							r |= peek( nxt, x + len );
-						f &= r;
-					}
+					// ... and the next group one of this group's lengths later
+					if( k < C.n - 1 )
+						f &= rmd_or_window( nxt, x, sb.len_lo, sb.len_hi, vec_bits );
 					dst[ wi ] = f;
 				}
 				__syncthreads();
@@ -1644,10 +1636,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			const unsigned long long	*const g1 = tv + ( 5 + ( cur ^ 1 ) ) * pb_words;
 			for( int wi = tid; wi < vec_words; wi += BLOCK ){
 				const int	x = wi * 64;
-				unsigned long long	r = 0;
-				for( int h = C.s_lo; h <= C.s_hi && ~r; h++ )
-					r |= peek( g1, x + h );
-				xv[ wi ] = r & lit_starts( x );
+				xv[ wi ] = rmd_or_window( g1, x, C.s_lo, C.s_hi, vec_bits ) & lit_starts( x );
 			}
 			__syncthreads();
 		}
@@ -1688,7 +1677,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 							// ... and end positions before which no third strand can stand (bit i: end hi - r0 - 63 + i)
 							const int	bq = hi - r0 - 63 - p_lo + 64;
 							if( bq >= 0 && bq + 96 <= vec_words * 64 )
-								W &= bits64( xv + 3 * pb_words, bq );
+								W &= rmd_bits64( xv + 3 * pb_words, bq );
 						}
 					}
 					while( __ballot( W != 0 ) ){
@@ -1761,7 +1750,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					unsigned	m = 0;
 					if( rel_lo < n_pos ){
 						// (n_pos covers what the position-by-position test asks: inside the tile, the entry and the slice)
-						m = unsigned( bits64( src, z0 + rel_lo - p_lo + 64 ) ) & 0xffffu;
+						m = unsigned( rmd_bits64( src, z0 + rel_lo - p_lo + 64 ) ) & 0xffffu;
 						if( n_pos - rel_lo < 16 )
 							m &= ( 1u << ( n_pos - rel_lo ) ) - 1u;
 					}
@@ -1824,7 +1813,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 						pk_lo = pk_q0 + utid * 16;
 						pk_m = 0;
 						if( pk_lo < n_pos ){
-							pk_m = unsigned( bits64( sv, z0 + pk_lo - p_lo + 64 ) ) & 0xffffu;
+							pk_m = unsigned( rmd_bits64( sv, z0 + pk_lo - p_lo + 64 ) ) & 0xffffu;
 							if( n_pos - pk_lo < 16 )
 								pk_m &= ( 1u << ( n_pos - pk_lo ) ) - 1u;
 						}
@@ -1982,7 +1971,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				const int	rel_lo = q0 + utid * 16;
 				unsigned	m = 0;
 				if( rel_lo < n_pos ){
-					m = unsigned( bits64( lsv, z0 + rel_lo - p_lo + 64 ) ) & 0xffffu;
+					m = unsigned( rmd_bits64( lsv, z0 + rel_lo - p_lo + 64 ) ) & 0xffffu;
 					if( n_pos - rel_lo < 16 )
 						m &= ( 1u << ( n_pos - rel_lo ) ) - 1u;
 				}
@@ -2139,17 +2128,11 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 												// ... and one of those ends must have the next stem-loop's core at the right distance
 												// behind it (bit i of Wd: end w0 + i)
 												const rmd_chain_t	&C = P->chain;
-												unsigned long long	cw = 0;
-												bool	all = true;
-												for( int g = C.hn_glo + 1; g <= C.hn_ghi + 1 + C.hn_tmax; g++ ){
-													const int	x = w0 + g - p_lo + 64;
-													if( x < 0 || x + 96 > vec_words * 64 )
-														all = false;		// (undecided)
-													else
-														cw |= bits64( tv + ( 7 + C.hn_slot ) * pb_words, x );
-												}
+												const int	x = w0 - p_lo + 64, g_lo = C.hn_glo + 1, g_hi = C.hn_ghi + 1 + C.hn_tmax;
+												// (a distance that leaves the vector: undecided)
+												const bool	all = g_hi < g_lo || ( x + g_lo >= 0 && x + g_hi + 96 <= vec_words * 64 );
 												if( all )
-													Wd &= cw;
+													Wd &= rmd_or_window( tv + ( 7 + C.hn_slot ) * pb_words, x, g_lo, g_hi, vec_words * 64 );
 												// (bit j of the mask: end bot + j)
 												if( all && top - bot < 32 )
 													ends_left = unsigned( Wd >> ( bot - w0 ) );
