@@ -31,6 +31,7 @@ extern "C" {
 typedef struct rma_descr	rma_descr_t;	/* compiled descriptor + score program (host)	*/
 typedef struct rma_scanner	rma_scanner_t;	/* motif program + buffers on one GPU		*/
 typedef struct rma_db		rma_db_t;	/* packed sequences resident in HBM		*/
+typedef struct rma_score	rma_score_t;	/* a score section's MAIN as an image for the device	*/
 typedef struct rma_replay	rma_replay_t;	/* score VM + hit printer state			*/
 
 const char	*rma_version( void );
@@ -69,7 +70,7 @@ int	rma_scanner_create( const rma_program_t *prog, const rma_efndata_t *efn, int
 int	rma_scanner_set_efn2data( rma_scanner_t *sc, const rma_efn2data_t *efn2, char *err, size_t errlen );
 /* Launch-shape and diagnostic switches (DESIGN.md has the table).  The RNAMOTIF_* environment is read
  * once, by rma_scanner_create(); the switches that may change between scans change through this call
- * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "struct_wgs", "flush", "efn_light", "host_sort", "timing", "short".
+ * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "struct_wgs", "score_budget", "flush", "efn_light", "host_sort", "timing", "short".
  * None of them changes the records a scan returns. */
 int	rma_scanner_set_option( rma_scanner_t *sc, const char *name, int value, char *err, size_t errlen );
 /* One scan of eight start positions, thrown away: what the runtime sets up on first use (code objects,
@@ -432,6 +433,44 @@ int	rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off /* n+1 */, c
 		const int32_t *d_pair /* total * pair_stride */, int32_t pair_stride, int64_t n, int64_t total,
 		const uint8_t *letters /* 256, host, or NULL */,
 		int32_t *d_efn /* n or NULL */, int32_t *d_efn2 /* n or NULL */, void *stream, char *err, size_t errlen );
+
+/* ---- the score section on the device: which records are hits, and their SCORE (csrc/rm_score_core.h has the rule,
+ * one function shared by the host and the kernel; csrc/rm_score_image.h the image it runs and its limits).
+ * rma_score_open() compiles a private copy of d (d itself is not touched), runs BEGIN on it and translates MAIN into
+ * an image.  It refuses with words, and makes no image, where records cannot be judged one by one on the device:
+ * MAIN is not independent from hit to hit (ScoreVM::hit_independent's reason: HOLD / RELEASE, a variable carried from
+ * one hit to the next); MAIN calls sprintf(), bits() or mismatches( string, pattern ), uses =~ or !~, or reads NAME;
+ * the descriptor is loose (rma_program_loose() > 0: its records are not yet the reference's candidates); the image
+ * is larger than the limits of rm_score_image.h, or would leave no room in LDS for one wave.  A descriptor without a
+ * MAIN program opens: every record is accepted, with SCORE as BEGIN left it (kind 0 unless BEGIN assigns it). */
+int	rma_score_open( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen );
+void	rma_score_close( rma_score_t *sp );
+/* What an image and its kernel take (profiles/score_device.py): info[ 0 ] bytes of the image, [ 1 ] instructions,
+ * [ 2 ] variables, [ 3 ] slots of the operand stack, [ 4 ] bytes of LDS a wave's stack and variables take, [ 5 ] waves of
+ * a workgroup, [ 6 ] bytes of dynamic LDS of a workgroup; from the runtime, -1 each where no device answers: [ 7 ] bytes
+ * of private memory a lane of rma_score_kernel has, [ 8 ] its static LDS, [ 9 ] its registers. */
+void	rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] );
+/* rma_score_hits(): MAIN on each of the n_hits records at d_hits, one record per lane.  d_accept[ h ] = 1 where record h
+ * is a hit (ACCEPT, or MAIN's end is never reached without one), 0 where MAIN rejects it; d_score[ h ] the SCORE the
+ * printer would read, an int as its exact double, d_kind[ h ] 0 for none, 1 for an int, 2 for a float (either may be
+ * NULL); a rejected record has score 0.0 of kind 0.  Doubles are the host VM's bit for bit.
+ * Arguments as rma_hit_structures takes them: any rows of a scan's records in any order; db made by
+ * rma_db_create_device*() (its text is read in place, through `letters` -- 256 bytes, none 0, or NULL -- as
+ * rma_replay_device() reads it); the pointers checked against their allocations on the scanner's device; the
+ * program of sp must be the scanner's, byte for byte.  Every record is checked on the device by rma_replay_device()'s
+ * rule before anything it points to is read; a bad record fails the call, naming its index.  A record on which MAIN
+ * stops fails the call too: err names the lowest such record, file and line of the instruction and the reason in the
+ * host VM's words -- type mismatch, undefined variable, bad pos / len, integer division by zero, '$' outside a
+ * reference, element stack overflow ... -- or one of the three stops the host VM has not: string + string (needs a
+ * buffer), a string in SCORE at ACCEPT, and more instructions for one record than option "score_budget"
+ * (rma_scanner_set_option; 2^20 unless set) allows, so that no score program can hold the device.
+ * After a failed call the outputs hold what they held before: results go to scratch of the scanner's (10 bytes a
+ * record, made on the first call and grown) and are copied once the check has passed.  The work runs on a stream of
+ * the scanner's own, behind what is queued on `stream` (the caller's hipStream_t, NULL = the default stream) and
+ * ahead of what is queued there next; the call waits once.  n_hits == 0 does nothing. */
+int	rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *letters /* 256 or NULL */, uint8_t *d_accept /* n */, double *d_score /* n or NULL */,
+		int8_t *d_kind /* n or NULL: 0 none, 1 int, 2 float */, void *stream, char *err, size_t errlen );
 
 #ifdef __cplusplus
 }

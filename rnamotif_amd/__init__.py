@@ -153,6 +153,12 @@ def lib() -> C.CDLL:
     L.rma_prune_hits.argtypes = [vp, vp, vp, C.c_int64, i32p, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_scanner_load_energy_tables.argtypes = [vp, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
     L.rma_structure_energies.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_score_open.argtypes = [vp, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.rma_score_close.argtypes = [vp]
+    L.rma_score_close.restype = None
+    L.rma_score_info.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rma_score_info.restype = None
+    L.rma_score_hits.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_program_loose.argtypes = [vp]
     L.rma_program_loose.restype = C.c_int
     _lib = L
@@ -454,6 +460,68 @@ def _record_args(db, hits, device, stride, whose, text_hint, letters=None):
     return hits.contiguous(), int(hits.shape[0]), dev, torch.cuda.current_stream(dev), letters
 
 
+class ScoreProgram:
+    """The MAIN program of a descriptor's score section as an image the GPU runs, one record per lane
+    (rma_score_open; Scanner.score() takes it).  Raises RnamotifError with the reason where the program cannot be
+    judged record by record on the device: HOLD / RELEASE or a variable carried from one hit to the next, sprintf(),
+    bits(), mismatches( string, pattern ), =~ / !~, a read of NAME, a loose descriptor, an image beyond the limits of
+    csrc/rm_score_image.h.  The descriptor itself is not touched: the image is made from a private copy."""
+
+    def __init__(self, descr: Descriptor):
+        h = C.c_void_p()
+        err = C.create_string_buffer(_ERRLEN)
+        _check(lib().rma_score_open(descr._h, C.byref(h), err, _ERRLEN), err)
+        self._h = h
+        self.descr = descr
+
+    @staticmethod
+    def reason(descr: Descriptor) -> Optional[str]:
+        """Why ScoreProgram(descr) would refuse, or None where it opens."""
+        try:
+            ScoreProgram(descr).close()
+        except RnamotifError as e:
+            return str(e)
+        return None
+
+    def info(self) -> dict:
+        """The image's and its kernel's sizes (rma_score_info); the last three are -1 where no GPU answers."""
+        a = (C.c_int32 * 10)()
+        lib().rma_score_info(self._h, a)
+        return dict(zip(("image_bytes", "instructions", "variables", "stack_slots", "wave_lds_bytes", "waves_per_workgroup",
+                         "workgroup_lds_bytes", "private_bytes", "static_lds_bytes", "registers"), (int(x) for x in a)))
+
+    def close(self) -> None:
+        if self._h:
+            lib().rma_score_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HitScores:
+    """Scanner.score()'s result, tensors on the scanner's device, ready on torch's current stream.
+
+    accept  torch.bool [n]   the record is a hit: MAIN accepts it
+    score   float64 [n]      its SCORE, an int as its exact double; 0.0 for a rejected record
+    kind    int8 [n]         0: no SCORE, 1: an int, 2: a float; 0 for a rejected record"""
+
+    def __init__(self, accept, score, kind):
+        self.accept, self.score, self.kind = accept, score, kind
+
+    def text(self, h: int) -> bytes:
+        """The nine bytes HitPrinter::print puts behind the name for record h: " %8d" of an int SCORE, " %8.3lf" of a
+        float, " %8.3lf" of 0.0 where there is none."""
+        k = int(self.kind[h])
+        v = float(self.score[h])
+        if k == 1:
+            return b" %8d" % int(v)
+        return (" %8.3f" % (v if k == 2 else 0.0)).encode()
+
+
 class HitStructures:
     """Scanner.hit_structures()'s result: the windows of n records, base by base, as tensors on the scanner's device.
 
@@ -744,6 +812,36 @@ class Scanner:
             # (the records are read by a kernel queued on this stream: torch keeps their memory until it has run)
             hits.record_stream(stream)
         return keep
+
+    def score(self, db: Database, hits, program: ScoreProgram, letters: Optional[bytes] = None, out=None) -> HitScores:
+        """The score section's MAIN on each of these records, on the GPU (rma_score_hits; the rule is
+        csrc/rm_score_core.h's, what ScoreVM::run does on the host): a HitScores -- which records are hits, and the
+        SCORE of each -- so that hits[scores.accept] goes on to prune(), hit_structures(), align() without a trip to
+        the host.  hits: int32 CUDA tensor [n, hit_stride] on the scanner's device, any rows of a scan's records in any
+        order; db: the database_from_tensor() / database_from_fasta_tensor() database they are of; program:
+        ScoreProgram(descr) of this scanner's descriptor; letters as Replay.device() takes them.  out: (accept, score,
+        kind) tensors to write instead of new ones.  The call waits once.  A malformed record, and a record on which
+        MAIN stops -- type mismatch, undefined variable, bad pos or len, integer division by zero, string + string,
+        more than option "score_budget" (2^20) instructions ... -- raise RnamotifError naming the lowest such record;
+        nothing is written then."""
+        import torch
+        hits, n, dev, stream, letters = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner",
+                                                    "its records are scored by Replay.batch() or pack()", letters)
+        if not isinstance(program, ScoreProgram) or not program._h:
+            raise ValueError("program: an open ScoreProgram is needed")
+        if out is None:
+            out = (torch.empty(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.float64, device=dev),
+                   torch.zeros(n, dtype=torch.int8, device=dev))
+        for t, dt, what in zip(out, (torch.bool, torch.float64, torch.int8), ("accept", "score", "kind")):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (n,) or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"out: {what} must be a contiguous {dt} tensor [{n}] on {dev}")
+        if n:
+            err = C.create_string_buffer(_ERRLEN)
+            _check(lib().rma_score_hits(self._h, program._h, db._h, hits.data_ptr(), n, letters, out[0].data_ptr(),
+                                        out[1].data_ptr(), out[2].data_ptr(), stream.cuda_stream, err, _ERRLEN), err)
+            # (the records are read by a kernel queued behind this stream: torch keeps their memory until it has run)
+            hits.record_stream(stream)
+        return HitScores(*out)
 
     def load_energy_tables(self, dir: str = EFNDATA_DIR, efn: bool = True, efn2: bool = True) -> None:
         """The tables of efn() and / or efn2() from a directory onto the scanner's GPU (rma_scanner_load_energy_tables),

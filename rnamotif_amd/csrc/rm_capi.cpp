@@ -8,6 +8,7 @@
 #include "rm_stream.h"
 #include "rm_hitsort.h"
 #include "rm_hitwin.h"
+#include "rm_score_image.h"
 #include <cctype>
 #include <cstddef>
 #include <cstring>
@@ -112,6 +113,28 @@ extern "C" int rma_program_loose( const rma_program_t *p )
 			n++;
 	return n;
 }
+
+extern "C" int rma_score_open( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen )
+{
+	if( out != nullptr )
+		*out = nullptr;
+	if( d == nullptr || out == nullptr )
+		return set_err( err, errlen, "rma_score_open: no descriptor" );
+	try{
+		std::unique_ptr<rma_score>	sp( new rma_score );
+		const std::string	why = rma::score_image_make( *d->pr.descr, *d->pr.prog, &sp->img );
+		if( !why.empty() )
+			return set_err( err, errlen, why.c_str() );
+		*out = sp.release();
+		return 0;
+	}catch( rma::Error &e ){
+		return set_err( err, errlen, e.what() );
+	}catch( std::exception &e ){
+		return set_err( err, errlen, e.what() );
+	}
+}
+
+extern "C" void rma_score_close( rma_score_t *sp ) { delete sp; }
 
 extern "C" int rma_replay_open( rma_descr_t *d, const char *path, rma_replay_t **out, char *err, size_t errlen )
 {

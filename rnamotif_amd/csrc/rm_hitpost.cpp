@@ -4,7 +4,8 @@
 // Behind them rma_structure_energies (rm_structenergy_dev.hip), which consumes what rma_hit_structures makes -- or any
 // structures in device memory -- and rma_scanner_load_energy_tables, which gives a scanner the tables for it.
 // Of a scan they need nothing: a scanner's program and device, a database's tables and text (rm_scanner_impl.h), and
-// scratch of their own.  What they all do first is written once:
+// scratch of their own.  Last rma_score_hits (rm_score_dev.hip): the score section's MAIN over records, the rule of
+// rm_score_core.h on an image of rm_score_image.h.  What they all do first is written once:
 //   record_call_args    the database, the records and the device refused or accepted
 //   letters_on_device   the table the window bytes go through
 //   check_records       behind the caller's stream, the bad-record word reset, every record judged by the span kernel
@@ -22,6 +23,8 @@
 #define RMD_FN_MEMBER	inline
 #include "rm_structenergy.h"
 #include "rm_structenergy_dev.h"
+#include "rm_score_core.h"
+#include "rm_score_dev.h"
 
 namespace {
 // records of a call go through the kernels HW_CHUNK at a time; windows come to the host (rma_hit_windows) in pieces
@@ -94,6 +97,11 @@ struct rma::HitPost {
 	void	*d_se = nullptr, *h_se = nullptr, *d_se_info = nullptr;
 	size_t	se_info_bytes = 0;
 	hipEvent_t	se_done = nullptr;
+	// rma_score_hits: two result words, a stopped record's result and a call's accept flags, kinds and scores; two
+	// page-locked words and a result; the image that is on the device now (its serial) and its bytes
+	void	*d_sc = nullptr, *h_sc = nullptr, *d_sc_image = nullptr;
+	size_t	sc_bytes = 0, sc_image_bytes = 0;
+	uint64_t	sc_serial = 0;
 };
 
 // (the scanner's device is current; the scratch stream is synchronised before anything is freed)
@@ -114,6 +122,9 @@ void rma::hitpost_free( HitPost *p )
 	( void )hipHostFree( p->h_se );
 	if( p->se_done )
 		( void )hipEventDestroy( p->se_done );
+	( void )hipFree( p->d_sc );
+	( void )hipFree( p->d_sc_image );
+	( void )hipHostFree( p->h_sc );
 	delete p;
 }
 
@@ -850,4 +861,132 @@ extern "C" int rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off, 
 	}
 	HIPCHK( hipEventRecord( p.se_done, st ) );
 	return 0;
+}
+
+// ---------------------------------------------------------------- the score section over records on the device
+// rma_score_hits(): rma_score_kernel (rm_score_dev.hip) in chunks of HW_CHUNK records on the stream of the scanner's span
+// scratch, behind the caller's stream.  The kernel checks each record by the span rule before it runs MAIN on it, so
+// the call has no pass of its own for the check.  Results go to scratch of the scanner's; one wait learns the least
+// index of a bad and of a stopped record; then the results are copied to the caller's tensors, ahead of what the caller
+// queues next.  For a stopped record the kernel runs once more, on that record alone, to fetch the stop's particulars.
+namespace {
+constexpr size_t	SC_DETAIL_AT = 64, SC_RESULTS_AT = 256;
+}
+
+extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, uint8_t *d_accept, double *d_score, int8_t *d_kind, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_score_hits";
+	if( sc == nullptr || sp == nullptr || db == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : sp == nullptr ? "score program" : "database" );
+		return 1;
+	}
+	// (both are memcpy copies of a descriptor's program: padding bytes included, equal where the descriptor's are)
+	if( memcmp( sp->img.prog.get(), &sc->prog, sizeof( rma_program_t ) ) != 0 ){
+		snprintf( err, errlen, "%s: the score program was opened for another descriptor than the scanner's (their programs differ): nothing written", who );
+		return 1;
+	}
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	if( n_hits == 0 )
+		return 0;
+	if( d_accept == nullptr ){
+		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )n_hits );
+		return 1;
+	}
+	if( rma::check_device_bytes( d_accept, sc->device, 0, n_hits, "the accept flags", err, errlen ) ||
+		( d_score != nullptr && rma::check_device_bytes( d_score, sc->device, 0, n_hits * 8, "the scores", err, errlen ) ) ||
+		( d_kind != nullptr && rma::check_device_bytes( d_kind, sc->device, 0, n_hits, "the kinds", err, errlen ) ) )
+		return 1;
+	if( letters != nullptr )
+		for( int b = 0; b < 256; b++ )
+			if( letters[ b ] == 0 ){
+				snprintf( err, errlen, "%s: the letters give byte %d the letter 0, which ends a string of the score section: nothing written", who, b );
+				return 1;
+			}
+	const RmsImage	*m = sp->img.image();
+	if( rma::score_waves( m->bytes, m->stack, m->n_vars ) < 1 ){
+		snprintf( err, errlen, "%s: the image leaves no room for a wave", who );
+		return 1;
+	}
+	rma::HitPost	&p = *sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream, caller = static_cast<hipStream_t>( stream );
+	const size_t	n = size_t( n_hits ), flags = ( n + 7 ) & ~size_t( 7 ), want = SC_RESULTS_AT + 2 * flags + 8 * n;
+	if( want > p.sc_bytes )		// (the copies of the call before this one may still read the block that goes)
+		HIPCHK( hipStreamSynchronize( st ) );
+	HIPCHK( dev_room( &p.d_sc, &p.sc_bytes, want ) );
+	if( p.h_sc == nullptr )
+		HIPCHK( hipHostMalloc( &p.h_sc, SC_RESULTS_AT, hipHostMallocDefault ) );
+	if( p.sc_serial != sp->img.serial ){
+		HIPCHK( hipStreamSynchronize( st ) );
+		HIPCHK( dev_room( &p.d_sc_image, &p.sc_image_bytes, size_t( m->bytes ) ) );
+		HIPCHK( hipMemcpy( p.d_sc_image, m, size_t( m->bytes ), hipMemcpyHostToDevice ) );
+		p.sc_serial = sp->img.serial;
+	}
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	if( letters_on_device( s, db, letters, &tab, &codes, err, errlen ) ||
+		check_records( s, db, sc->prog, d_hits, n_hits, stream, false, nullptr, 0, err, errlen ) )
+		return 1;
+	char	*base = static_cast<char *>( p.d_sc );
+	unsigned long long	*d_words = reinterpret_cast<unsigned long long *>( base ), *h_words = static_cast<unsigned long long *>( p.h_sc );
+	RmsResult	*d_detail = reinterpret_cast<RmsResult *>( base + SC_DETAIL_AT );
+	RmsResult	*h_detail = reinterpret_cast<RmsResult *>( static_cast<char *>( p.h_sc ) + SC_DETAIL_AT );
+	uint8_t	*acc = reinterpret_cast<uint8_t *>( base + SC_RESULTS_AT );
+	int8_t	*kind = reinterpret_cast<int8_t *>( acc + flags );
+	double	*score = reinterpret_cast<double *>( acc + 2 * flags );
+	HIPCHK( hipMemsetAsync( d_words, 0xff, 2 * sizeof( unsigned long long ), st ) );
+	const int	stride = rma_hit_stride( &sc->prog );
+	auto batch = [&]( int64_t c0, int64_t cn, RmsResult *detail ){
+		return rma::ScoreBatch{ p.d_sc_image, m->bytes, m->stack, m->n_vars, d_hits + c0 * stride, ( long long )cn, ( long long )c0, stride,
+			rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq, db->text, tab, codes, sc->opt.score_budget,
+			acc + c0, score + c0, kind + c0, d_words, d_words + 1, detail };
+	};
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
+		HIPCHK( rma::score_records( batch( c0, std::min( HW_CHUNK, n_hits - c0 ), nullptr ), st ) );
+	HIPCHK( hipMemcpyAsync( h_words, d_words, 2 * sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( h_words[ 0 ] != ~0ull )
+		return bad_record( s, db, sc->prog, d_hits, int64_t( h_words[ 0 ] ), nullptr, "scored", err, errlen );
+	if( h_words[ 1 ] != ~0ull ){
+		const int64_t	h = int64_t( h_words[ 1 ] );
+		memset( h_detail, 0, sizeof( RmsResult ) );
+		HIPCHK( hipMemsetAsync( d_detail, 0, sizeof( RmsResult ), st ) );
+		HIPCHK( rma::score_records( batch( h, 1, d_detail ), st ) );
+		HIPCHK( hipMemcpyAsync( h_detail, d_detail, sizeof( RmsResult ), hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipStreamSynchronize( st ) );
+		snprintf( err, errlen, "%s: record %lld: %s: nothing written", who, ( long long )h, rma::score_stop_text( sp->img, *h_detail ).c_str() );
+		return 1;
+	}
+	HIPCHK( hipMemcpyAsync( d_accept, acc, n, hipMemcpyDeviceToDevice, st ) );
+	if( d_score != nullptr )
+		HIPCHK( hipMemcpyAsync( d_score, score, 8 * n, hipMemcpyDeviceToDevice, st ) );
+	if( d_kind != nullptr )
+		HIPCHK( hipMemcpyAsync( d_kind, kind, n, hipMemcpyDeviceToDevice, st ) );
+	return rma::stream_after( caller, st, err, errlen );
+}
+
+extern "C" void rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] )
+{
+	if( sp == nullptr ){
+		for( int i = 0; i < 10; i++ )
+			info[ i ] = -1;
+		return;
+	}
+	const RmsImage	*m = sp->img.image();
+	const int	waves = rma::score_waves( m->bytes, m->stack, m->n_vars ), wave = rms_wave_bytes( m->stack, m->n_vars );
+	info[ 0 ] = m->bytes;
+	info[ 1 ] = m->n_inst;
+	info[ 2 ] = m->n_vars;
+	info[ 3 ] = m->stack;
+	info[ 4 ] = wave;
+	info[ 5 ] = waves;
+	info[ 6 ] = m->bytes + RMS_LDS_TABLES + waves * wave;
+	int	priv = -1, lds = -1, regs = -1;
+	if( rma::score_kernel_attributes( &priv, &lds, &regs ) != hipSuccess )
+		( void )hipGetLastError();
+	info[ 7 ] = priv;
+	info[ 8 ] = lds;
+	info[ 9 ] = regs;
 }

@@ -188,7 +188,7 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 	rma_scanner	*sc = new rma_scanner;
 	// every early return below releases the scanner and what it holds by then
 	struct ScGuard { rma_scanner *p; ~ScGuard(){ if( p ) rma_scanner_destroy( p ); } }	guard{ sc };
-	sc->prog = *prog;
+	memcpy( &sc->prog, prog, sizeof( rma_program_t ) );	// (every byte, padding too: rma_score_hits compares the bytes with an image's copy)
 	sc->opt.latch();
 	// (host work first: a descriptor outside the device limits is refused with its reason whether
 	// or not a device is there to refuse it for)
@@ -277,7 +277,7 @@ extern "C" int rma_scanner_set_option( rma_scanner_t *sc, const char *name, int 
 		sc->last_relabelled = false;
 	}else if( !sc->opt.set( n, value ) ){
 		snprintf( err, errlen, "rma_scanner_set_option: no option '%s' that can change after creation "
-			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, struct_wgs, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
+			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, struct_wgs, score_budget, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
 		return 1;
 	}
 	return 0;

@@ -640,10 +640,13 @@ void ScoreVM::dump( FILE *fp )	// RM_dumpscore :563, dumpinst :3576
 // evaluation stack.  The stack is empty at every statement boundary (FJP and CLS reset it), so the
 // states that meet at a label differ in the variables only -- and, inside an expression, in the top
 // of the stack after && / || (joined to "unknown" when the operands' types differ).
-bool ScoreVM::hit_independent( std::string *why ) const
+bool ScoreVM::hit_independent( std::string *why, int *deepest ) const
 {
 	auto no = [&]( const std::string &m ){ if( why ) *why = m; return false; };
 	const std::vector<Inst>	&pr = progs_[ P_MAIN ];
+	size_t	deep = 0;
+	if( deepest )
+		*deepest = 0;
 	if( pr.empty() )
 		return true;
 	enum { TY_TOP = 100, TY_MARK = 101 };		// unknown; a MRK slot
@@ -971,6 +974,7 @@ bool ScoreVM::hit_independent( std::string *why ) const
 		}
 		if( !trouble.empty() )
 			break;
+		deep = std::max( deep, k.size() );
 		if( jump >= 0 ){
 			State	j = s;
 			merge( jump, j );
@@ -980,6 +984,8 @@ bool ScoreVM::hit_independent( std::string *why ) const
 	}
 	if( !trouble.empty() )
 		return no( trouble );
+	if( deepest )
+		*deepest = int( deep );
 	return true;
 }
 

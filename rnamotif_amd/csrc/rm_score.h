@@ -69,8 +69,11 @@ public:
 	// assigned before MAIN -- or the printer, for SCORE -- reads it, on every path; a variable whose type
 	// the first assignment would latch (undefined after BEGIN) gets the same type from every assignment;
 	// END reads nothing MAIN writes.  Conservative: anything the analysis cannot follow says no (*why).
-	// To be called after linkscore() and after BEGIN has run.
-	bool	hit_independent( std::string *why ) const;
+	// To be called after linkscore() and after BEGIN has run.  deepest (may be null): the most slots of the evaluation
+	// stack, marks included, that MAIN can hold at once -- the walk visits every state MAIN can reach.
+	bool	hit_independent( std::string *why, int *deepest = nullptr ) const;
+	// the instructions of a program (rm_score_image.cpp translates MAIN's)
+	const std::vector<Inst>	&program( int p ) const { return progs_[ p ]; }
 
 	const std::vector<EfnCall>	&efn_calls() const { return efn_calls_; }
 	bool	has_main() const { return !progs_[ P_MAIN ].empty(); }

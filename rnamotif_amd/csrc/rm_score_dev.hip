@@ -1,0 +1,110 @@
+// rm_score_dev.hip -- see rm_score_dev.h.  Compiled with -ffp-contract=off: a double comes out bit for bit as on the host.
+#include <hip/hip_runtime.h>
+#define RMS_POD_ONLY
+#define RMD_FN		static __device__ inline
+#define RMD_FN_MEMBER	__device__ inline
+#include "rm_score_core.h"
+#include "rm_score_dev.h"
+
+namespace rma {
+
+namespace {
+
+constexpr int	SC_MAX_WAVES = 4;
+
+// the letters Replay.device() reads: the table's (of a code: its letter), on strand 1 the complement, read downwards
+struct ScoreBases {
+	const uint8_t	*text;		// the entry's first byte
+	const uint8_t	*let, *cmp;	// in LDS
+	int	comp, slen;
+	__device__ unsigned char	operator()( int i ) const
+	{
+		if( unsigned( i ) >= unsigned( slen ) )
+			return 'n';
+		return comp ? cmp[ text[ slen - 1 - i ] ] : let[ text[ i ] ];
+	}
+};
+
+__global__ void __launch_bounds__( SC_MAX_WAVES * 64 )
+rma_score_kernel( ScoreBatch b )
+{
+	extern __shared__ __attribute__(( aligned( 16 ) )) uint64_t	lds[];
+	const int	t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	const int	image_words = b.image_bytes / 8;
+	for( int i = t; i < image_words; i += blockDim.x )
+		lds[ i ] = static_cast<const uint64_t *>( b.image )[ i ];
+	uint8_t	*let = reinterpret_cast<uint8_t *>( lds + image_words ), *cmp = let + 256;
+	for( int i = t; i < 256; i += blockDim.x ){
+		const unsigned char	v = b.table[ i ];
+		const unsigned char	l = b.codes ? hitwin_code_letter( v ) : v;
+		let[ i ] = l;
+		cmp[ i ] = hitwin_wc_cmp( l );
+	}
+	__syncthreads();
+	const RmsImage	*m = reinterpret_cast<const RmsImage *>( lds );
+	const long long	h = blockIdx.x * ( long long )blockDim.x + t;
+	if( h >= b.n )
+		return;
+	const int32_t	*w = b.hits + h * b.stride;
+	RmsResult	r;
+	r.outcome = RMS_REJECT;
+	r.kind = RMS_KIND_NONE;
+	r.score = 0.0;
+	int32_t	lo, hi;
+	int	which;
+	if( hitwin_span( w, b.shape, b.n_seq, b.slen, &lo, &hi, &which ) != HW_OK )
+		atomicMin( b.bad, static_cast<unsigned long long>( b.first + h ) );
+	else{
+		const int	wave_words = rms_wave_bytes( b.stack, b.n_vars ) / 4;
+		int32_t	*planes = reinterpret_cast<int32_t *>( cmp + 256 ) + wave * wave_words;
+		const RmsMem<64>	mem{ planes + lane, reinterpret_cast<uint8_t *>( planes + ( b.stack + b.n_vars ) * 3 * 64 ) + lane, b.stack, b.n_vars };
+		const int	seq = w[ 0 ], slen = b.slen[ seq ];
+		const ScoreBases	bases{ b.text + b.start[ seq ], let, cmp, w[ 1 ], slen };
+		rms_run( m, w, slen, bases, mem, b.budget, &r );
+		if( r.outcome == RMS_STOPPED ){
+			atomicMin( b.stopped, static_cast<unsigned long long>( b.first + h ) );
+			if( b.detail != nullptr )
+				*b.detail = r;
+		}
+	}
+	const bool	ok = r.outcome == RMS_ACCEPT;
+	b.accept[ h ] = ok ? 1 : 0;
+	b.score[ h ] = ok ? r.score : 0.0;
+	b.kind[ h ] = ok ? int8_t( r.kind ) : int8_t( 0 );
+}
+
+}	// namespace
+
+int score_waves( int image_bytes, int stack, int n_vars )
+{
+	const int	room = RMS_LDS_BYTES - RMS_LDS_TABLES - image_bytes, wave = rms_wave_bytes( stack, n_vars );
+	const int	n = room < wave ? 0 : room / wave;
+	return n > SC_MAX_WAVES ? SC_MAX_WAVES : n;
+}
+
+hipError_t score_records( const ScoreBatch &b, hipStream_t s )
+{
+	if( b.n <= 0 )
+		return hipSuccess;
+	const int	waves = score_waves( b.image_bytes, b.stack, b.n_vars );
+	if( waves < 1 || b.image_bytes % 8 != 0 || b.stack < 1 || b.n_vars < 1 )
+		return hipErrorInvalidValue;
+	const int	block = waves * 64;
+	const size_t	lds = size_t( b.image_bytes ) + RMS_LDS_TABLES + size_t( waves ) * size_t( rms_wave_bytes( b.stack, b.n_vars ) );
+	hipLaunchKernelGGL( rma_score_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
+	return hipGetLastError();
+}
+
+hipError_t score_kernel_attributes( int *private_bytes, int *static_lds, int *regs )
+{
+	hipFuncAttributes	a;
+	const hipError_t	e = hipFuncGetAttributes( &a, reinterpret_cast<const void *>( rma_score_kernel ) );
+	if( e == hipSuccess ){
+		*private_bytes = int( a.localSizeBytes );
+		*static_lds = int( a.sharedSizeBytes );
+		*regs = a.numRegs;
+	}
+	return e;
+}
+
+}	// namespace rma
