@@ -18,6 +18,7 @@
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -121,14 +122,11 @@ struct rma_comm {
 	ncclComm_t	comm = nullptr;		// RCCL's communicator when the transport is RCCL's (destroyed with this)
 	rma_transport_t	tr{};
 	int	rank = 0, world = 1, device = 0;
-	long long	*d_counts = nullptr;	// [2 * world + 2]: the ranks' counts, the ranks' flags, this rank's own count and flag
-	long long	*h_counts = nullptr;	// pinned, [2 * world]
-	int32_t	*d_index = nullptr;
-	size_t	index_cap = 0;
-	int32_t	*d_all = nullptr;		// root: every rank's records, rank by rank
-	size_t	all_cap = 0;			// words
-	int32_t	*h_all = nullptr;		// pinned
-	size_t	h_cap = 0;
+	rma::DevMem	counts;			// long long [2 * world + 2]: the ranks' counts, the ranks' flags, this rank's own count and flag
+	rma::PinMem	counts_host;		// long long [2 * world]
+	rma::DevMem	index;			// int32_t: the entry numbers of a gather
+	rma::DevMem	all;			// root: every rank's records, rank by rank
+	rma::PinMem	all_host;
 	// what every rank knows the root's buffers to hold at least (words): the largest total any gather has had,
 	// times one and a half -- when a gather exceeds it, the root must allocate, and every rank waits for its word
 	size_t	agreed_cap = 0;
@@ -152,18 +150,15 @@ extern "C" int rma_comm_unique_id( uint8_t id[ RMA_COMM_ID_BYTES ], char *err, s
 	return 0;
 }
 
+// a communicator under construction: destroyed on every way out but release()
+using CommPtr = std::unique_ptr<rma_comm, void ( * )( rma_comm * )>;
+
 extern "C" void rma_comm_destroy( rma_comm_t *c )
 {
 	if( c == nullptr )
 		return;
+	// (every gather ends with its stream synchronised: nothing is in flight on the buffers)
 	( void )hipSetDevice( c->device );
-	( void )hipFree( c->d_counts );
-	( void )hipFree( c->d_index );
-	( void )hipFree( c->d_all );
-	if( c->h_counts )
-		( void )hipHostFree( c->h_counts );
-	if( c->h_all )
-		( void )hipHostFree( c->h_all );
 	if( c->comm != nullptr )
 		if( Rccl *R = rccl() )
 			( void )R->CommDestroy( c->comm );
@@ -178,15 +173,14 @@ static int comm_new( int rank, int world, int device, rma_comm **out, char *err,
 		return 1;
 	}
 	HIPCHK( hipSetDevice( device ) );
-	rma_comm	*c = new rma_comm;
-	struct Guard { rma_comm *p; ~Guard(){ if( p ) rma_comm_destroy( p ); } }	guard{ c };
+	CommPtr	guard( new rma_comm, rma_comm_destroy );
+	rma_comm	*c = guard.get();
 	c->rank = rank;
 	c->world = world;
 	c->device = device;
-	HIPCHK( hipMalloc( &c->d_counts, size_t( 2 * world + 2 ) * sizeof( long long ) ) );
-	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &c->h_counts ), size_t( 2 * world ) * sizeof( long long ), hipHostMallocDefault ) );
-	guard.p = nullptr;
-	*out = c;
+	HIPCHK( c->counts.exact( size_t( 2 * world + 2 ) * sizeof( long long ) ) );
+	HIPCHK( c->counts_host.exact( size_t( 2 * world ) * sizeof( long long ) ) );
+	*out = guard.release();
 	return 0;
 }
 
@@ -197,7 +191,7 @@ extern "C" int rma_comm_create( const uint8_t id[ RMA_COMM_ID_BYTES ], int rank,
 	*out = nullptr;
 	if( comm_new( rank, world, device, &c, err, errlen ) )
 		return 1;
-	struct Guard { rma_comm *p; ~Guard(){ if( p ) rma_comm_destroy( p ); } }	guard{ c };
+	CommPtr	guard( c, rma_comm_destroy );
 	if( world > 1 ){
 		Rccl	*R = rccl();
 		if( R == nullptr )
@@ -207,8 +201,7 @@ extern "C" int rma_comm_create( const uint8_t id[ RMA_COMM_ID_BYTES ], int rank,
 		NCCLCHK( R->CommInitRank( &c->comm, world, u, rank ) );
 		c->tr = rma_transport_t{ rccl_all_gather, rccl_send, rccl_recv, rccl_group_start, rccl_group_end, rccl_error_string, rccl_comm_count, c->comm };
 	}
-	guard.p = nullptr;
-	*out = c;
+	*out = guard.release();
 	return 0;
 }
 
@@ -251,7 +244,8 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 		return 1;
 	}
 	HIPCHK( hipSetDevice( c->device ) );
-	hipStream_t	s = sc->stream;
+	hipStream_t	s = sc->stream.get();
+	long long	*d_counts = c->counts.as<long long>(), *h_counts = c->counts_host.as<long long>();
 	const int	stride = sc->dprog.hit_stride;
 	const int32_t	*d_mine = sc->d_last;
 	const int64_t	n_mine = sc->n_last;
@@ -266,20 +260,15 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 	// records finds them relabelled)
 	if( trouble.empty() && n_mine > 0 && !sc->last_relabelled ){
 		hipError_t	e = hipSuccess;
-		if( size_t( n_index ) > c->index_cap ){
+		if( size_t( n_index ) * sizeof( int32_t ) > c->index.bytes() ){
 			e = hipStreamSynchronize( s );
-			( void )hipFree( c->d_index );
-			c->d_index = nullptr;
-			c->index_cap = 0;
 			if( e == hipSuccess )
-				e = hipMalloc( &c->d_index, size_t( n_index ) * 2 * sizeof( int32_t ) );
-			if( e == hipSuccess )
-				c->index_cap = size_t( n_index ) * 2;
+				e = c->index.exact( size_t( n_index ) * 2 * sizeof( int32_t ) );
 		}
 		if( e == hipSuccess )
-			e = hipMemcpyAsync( c->d_index, global_index, size_t( n_index ) * sizeof( int32_t ), hipMemcpyHostToDevice, s );
+			e = hipMemcpyAsync( c->index.as<void>(), global_index, size_t( n_index ) * sizeof( int32_t ), hipMemcpyHostToDevice, s );
 		if( e == hipSuccess )
-			e = rma::relabel_entries( const_cast<int32_t *>( d_mine ), n_mine, stride, c->d_index, n_index, s );
+			e = rma::relabel_entries( const_cast<int32_t *>( d_mine ), n_mine, stride, c->index.as<int32_t>(), n_index, s );
 		if( e == hipSuccess )
 			sc->last_relabelled = true;
 		else
@@ -288,23 +277,23 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 	// how many records every rank holds, and whether every rank is fit to go on: one all-gather of two words
 	long long	mine[ 2 ] = { trouble.empty() ? ( long long )n_mine : 0, trouble.empty() ? 0 : 1 };
 	if( c->world > 1 ){
-		HIPCHK( hipMemcpyAsync( c->d_counts + 2 * c->world, mine, sizeof( mine ), hipMemcpyHostToDevice, s ) );
-		TRCHK( c->tr.all_gather( c->tr.ctx, c->d_counts + 2 * c->world, c->d_counts, 2, s ) );
-		HIPCHK( hipMemcpyAsync( c->h_counts, c->d_counts, size_t( 2 * c->world ) * sizeof( long long ), hipMemcpyDeviceToHost, s ) );
+		HIPCHK( hipMemcpyAsync( d_counts + 2 * c->world, mine, sizeof( mine ), hipMemcpyHostToDevice, s ) );
+		TRCHK( c->tr.all_gather( c->tr.ctx, d_counts + 2 * c->world, d_counts, 2, s ) );
+		HIPCHK( hipMemcpyAsync( h_counts, d_counts, size_t( 2 * c->world ) * sizeof( long long ), hipMemcpyDeviceToHost, s ) );
 		HIPCHK( hipStreamSynchronize( s ) );		// (the one wait before the exchange: its sizes)
 	}else{
-		c->h_counts[ 0 ] = mine[ 0 ];
-		c->h_counts[ 1 ] = mine[ 1 ];
+		h_counts[ 0 ] = mine[ 0 ];
+		h_counts[ 1 ] = mine[ 1 ];
 	}
 	int64_t	total = 0;
 	int	unfit = -1;
 	std::vector<long long>	cnt( size_t( c->world ), 0 );		// (h_counts is used again below)
 	for( int r = 0; r < c->world; r++ ){
-		cnt[ size_t( r ) ] = c->h_counts[ 2 * r ];
+		cnt[ size_t( r ) ] = h_counts[ 2 * r ];
 		if( counts )
 			counts[ r ] = cnt[ size_t( r ) ];
 		total += cnt[ size_t( r ) ];
-		if( c->h_counts[ 2 * r + 1 ] != 0 && unfit < 0 )
+		if( h_counts[ 2 * r + 1 ] != 0 && unfit < 0 )
 			unfit = r;
 	}
 	if( unfit >= 0 ){
@@ -321,25 +310,13 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 	const size_t	words = size_t( total ) * stride;
 	const bool	grows = words > c->agreed_cap;
 	std::string	alloc_trouble;
-	if( c->rank == root && ( words > c->all_cap || words > c->h_cap ) ){
+	const size_t	bytes = words * sizeof( int32_t );
+	if( c->rank == root && ( bytes > c->all.bytes() || bytes > c->all_host.bytes() ) ){
 		hipError_t	e = hipSuccess;
-		if( words > c->all_cap ){
-			( void )hipFree( c->d_all );
-			c->d_all = nullptr;
-			c->all_cap = 0;
-			e = hipMalloc( &c->d_all, ( words + words / 2 ) * sizeof( int32_t ) );
-			if( e == hipSuccess )
-				c->all_cap = words + words / 2;
-		}
-		if( e == hipSuccess && words > c->h_cap ){
-			if( c->h_all )
-				( void )hipHostFree( c->h_all );
-			c->h_all = nullptr;
-			c->h_cap = 0;
-			e = hipHostMalloc( reinterpret_cast<void **>( &c->h_all ), ( words + words / 2 ) * sizeof( int32_t ), hipHostMallocDefault );
-			if( e == hipSuccess )
-				c->h_cap = words + words / 2;
-		}
+		if( bytes > c->all.bytes() )
+			e = c->all.exact( ( words + words / 2 ) * sizeof( int32_t ) );
+		if( e == hipSuccess && bytes > c->all_host.bytes() )
+			e = c->all_host.exact( ( words + words / 2 ) * sizeof( int32_t ) );
 		if( e != hipSuccess ){
 			( void )hipGetLastError();
 			alloc_trouble = std::string( "rma_gather_hits: the root's buffers for " ) + std::to_string( ( long long )total ) + " records: " + hipGetErrorString( e );
@@ -349,11 +326,11 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 		c->agreed_cap = words + words / 2;
 		if( c->world > 1 ){
 			long long	flag[ 2 ] = { alloc_trouble.empty() ? 0 : 1, 0 };
-			HIPCHK( hipMemcpyAsync( c->d_counts + 2 * c->world, flag, sizeof( flag ), hipMemcpyHostToDevice, s ) );
-			TRCHK( c->tr.all_gather( c->tr.ctx, c->d_counts + 2 * c->world, c->d_counts, 2, s ) );
-			HIPCHK( hipMemcpyAsync( c->h_counts, c->d_counts, size_t( 2 * c->world ) * sizeof( long long ), hipMemcpyDeviceToHost, s ) );
+			HIPCHK( hipMemcpyAsync( d_counts + 2 * c->world, flag, sizeof( flag ), hipMemcpyHostToDevice, s ) );
+			TRCHK( c->tr.all_gather( c->tr.ctx, d_counts + 2 * c->world, d_counts, 2, s ) );
+			HIPCHK( hipMemcpyAsync( h_counts, d_counts, size_t( 2 * c->world ) * sizeof( long long ), hipMemcpyDeviceToHost, s ) );
 			HIPCHK( hipStreamSynchronize( s ) );
-			if( c->h_counts[ 2 * root ] != 0 && alloc_trouble.empty() )
+			if( h_counts[ 2 * root ] != 0 && alloc_trouble.empty() )
 				alloc_trouble = "rma_gather_hits: rank " + std::to_string( root ) + " (the root) has no room for " + std::to_string( ( long long )total ) + " records";
 		}
 	}
@@ -383,17 +360,18 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 	}
 	if( xch.empty() ){
 		if( c->rank == root ){
+			int32_t	*d_all = c->all.as<int32_t>();
 			size_t	at = 0;
 			for( int r = 0; r < c->world && xch.empty(); r++ ){
 				const size_t	w = size_t( cnt[ size_t( r ) ] ) * stride;
 				if( w == 0 )
 					continue;
 				if( r == root ){
-					const hipError_t	e = hipMemcpyAsync( c->d_all + at, d_mine, w * sizeof( int32_t ), hipMemcpyDeviceToDevice, s );
+					const hipError_t	e = hipMemcpyAsync( d_all + at, d_mine, w * sizeof( int32_t ), hipMemcpyDeviceToDevice, s );
 					if( e != hipSuccess )
 						note_hip( "the root's own records", e );
 				}else{
-					const int	r_ = c->tr.recv( c->tr.ctx, c->d_all + at, w, r, s );
+					const int	r_ = c->tr.recv( c->tr.ctx, d_all + at, w, r, s );
 					if( r_ != 0 )
 						note( "receive", r_ );
 				}
@@ -416,9 +394,9 @@ extern "C" int rma_gather_hits( rma_comm_t *c, rma_scanner_t *sc, const int32_t 
 		return 1;
 	}
 	if( c->rank == root ){
-		HIPCHK( hipMemcpyAsync( c->h_all, c->d_all, size_t( total ) * stride * sizeof( int32_t ), hipMemcpyDeviceToHost, s ) );
+		HIPCHK( hipMemcpyAsync( c->all_host.as<void>(), c->all.as<void>(), bytes, hipMemcpyDeviceToHost, s ) );
 		HIPCHK( hipStreamSynchronize( s ) );
-		*hits = c->h_all;
+		*hits = c->all_host.as<int32_t>();
 		*n_hits = total;
 	}else
 		HIPCHK( hipStreamSynchronize( s ) );	// (the records have left before the scanner's next scan overwrites them)

@@ -12,13 +12,13 @@
 #include <algorithm>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <vector>
 #include "rm_scanner_impl.h"
 #include "rm_hitpost.h"
 #include "rm_hitwin_dev.h"
 #include "rm_hitstruct_dev.h"
 #include "rm_hitalign_dev.h"
-#include "rm_efndata.h"
 #define RMD_FN		static inline
 #define RMD_FN_MEMBER	inline
 #include "rm_structenergy.h"
@@ -32,33 +32,14 @@ namespace {
 constexpr int64_t	HW_CHUNK = int64_t( 1 ) << 17;
 constexpr int64_t	HW_PIECE_WINDOW = int64_t( 16 ) << 20, HW_PIECE_RECORDS = int64_t( 8 ) << 20;
 
-// *p has room for `want` bytes, device or page-locked memory: what is there, or a new piece a quarter larger
-hipError_t room( void **p, size_t *cap, size_t want, bool host )
-{
-	if( *cap >= want )
-		return hipSuccess;
-	if( *p != nullptr )
-		( void )( host ? hipHostFree( *p ) : hipFree( *p ) );
-	*p = nullptr;
-	*cap = 0;
-	want += want / 4;
-	hipError_t	e = host ? hipHostMalloc( p, want, hipHostMallocDefault ) : hipMalloc( p, want );
-	if( e == hipSuccess )
-		*cap = want;
-	return e;
-}
-hipError_t dev_room( void **p, size_t *cap, size_t want ) { return room( p, cap, want, false ); }
-hipError_t host_room( void **p, size_t *cap, size_t want ) { return room( p, cap, want, true ); }
 }	// namespace
 
-// the two fixed blocks (rm_hitpost.h), the scan's room, windows; page-locked: records, windows
+// the two fixed blocks (rm_hitpost.h), the scan's room, windows; page-locked: the fixed block, records, windows
 struct rma::HitWindowScratch : rma::HitWinFixed {
 	int	device = -1;
-	hipStream_t	stream = nullptr;
-	void	*d_fixed = nullptr, *d_tmp = nullptr, *d_win = nullptr;
-	size_t	fixed_bytes = 0, tmp_bytes = 0, win_cap = 0;
-	void	*h_fixed = nullptr, *h_rec = nullptr, *h_win = nullptr;
-	size_t	h_fixed_bytes = 0, rec_cap = 0, h_win_cap = 0;
+	Stream	stream;
+	DevMem	d_fixed, d_tmp, d_win;
+	PinMem	h_fixed, h_rec, h_win;
 	std::vector<int64_t>	piece_off;
 };
 
@@ -67,64 +48,45 @@ void rma::hitwin_scratch_free( HitWindowScratch *s )
 	if( s == nullptr )
 		return;
 	( void )hipSetDevice( s->device );
-	if( s->stream != nullptr )
-		( void )hipStreamSynchronize( s->stream );
-	for( void *p : { s->d_fixed, s->d_tmp, s->d_win } )
-		if( p != nullptr )
-			( void )hipFree( p );
-	for( void *p : { s->h_fixed, s->h_rec, s->h_win } )
-		if( p != nullptr )
-			( void )hipHostFree( p );
-	if( s->stream != nullptr )
-		( void )hipStreamDestroy( s->stream );
+	if( s->stream.get() != nullptr )
+		( void )hipStreamSynchronize( s->stream.get() );
 	delete s;
 }
 
-// What a scanner keeps for these calls, made by the first that needs it.
+// What a scanner keeps for these calls, made by the first that needs it.  Each call's fixed pieces are there together or
+// not at all (its first use builds them in locals and moves them in); the pieces that grow are asked for room per call.
 struct rma::HitPost {
 	// rma_hit_structures, rma_hit_alignment: the span scratch and stream, the program's table and, behind it, the running total
 	HitWindowScratch	*win = nullptr;
-	HitStructTable	*d_hs_table = nullptr;
-	int64_t	*d_hs_carry = nullptr;
-	// rma_prune_hits: the program's table (two result words behind it), the keys, flags and block list of a call, the
-	// entries' name groups, two page-locked words, and the event behind the last call's kernels
-	PruneTable	*d_pr_table = nullptr;
-	void	*d_pr = nullptr, *d_pr_groups = nullptr, *h_pr = nullptr;
-	size_t	pr_bytes = 0, pr_groups_bytes = 0, h_pr_bytes = 0;
-	hipEvent_t	pr_done = nullptr;
-	// rma_structure_energies: two result words and the 256 codes of a call's bytes (device and page-locked), the info
-	// word of every structure of a call, and the event behind the last call's kernels
-	void	*d_se = nullptr, *h_se = nullptr, *d_se_info = nullptr;
-	size_t	se_info_bytes = 0;
-	hipEvent_t	se_done = nullptr;
+	DevMem	hs;
+	static constexpr size_t	HS_CARRY_AT = ( sizeof( HitStructTable ) + 7 ) & ~size_t( 7 );
+	HitStructTable	*hs_table() const { return hs.as<HitStructTable>(); }
+	int64_t	*hs_carry() const { return reinterpret_cast<int64_t *>( hs.as<char>() + HS_CARRY_AT ); }
+	// rma_prune_hits: the program's table (two result words behind it), two page-locked words and the event behind the
+	// last call's kernels; the keys, flags and block list of a call, the entries' name groups
+	DevMem	pr_table;
+	PinMem	h_pr;
+	Event	pr_done;
+	DevMem	d_pr, d_pr_groups;
+	// rma_structure_energies: two result words and the 256 codes of a call's bytes (device and page-locked) and the
+	// event behind the last call's kernels; the info word of every structure of a call
+	DevMem	d_se;
+	PinMem	h_se;
+	Event	se_done;
+	DevMem	d_se_info;
 	// rma_score_hits: two result words, a stopped record's result and a call's accept flags, kinds and scores; two
-	// page-locked words and a result; the image that is on the device now (its serial) and its bytes
-	void	*d_sc = nullptr, *h_sc = nullptr, *d_sc_image = nullptr;
-	size_t	sc_bytes = 0, sc_image_bytes = 0;
+	// page-locked words and a result; the image that is on the device now (its serial; 0: none) and its bytes
+	DevMem	d_sc, d_sc_image;
+	PinMem	h_sc;
 	uint64_t	sc_serial = 0;
 };
 
-// (the scanner's device is current; the scratch stream is synchronised before anything is freed)
+// (the scanner's device is current; the scratch stream is synchronised before anything goes)
 void rma::hitpost_free( HitPost *p )
 {
 	if( p == nullptr )
 		return;
 	hitwin_scratch_free( p->win );
-	( void )hipFree( p->d_hs_table );		// (the running total lies behind the table)
-	( void )hipFree( p->d_pr_table );
-	( void )hipFree( p->d_pr );
-	( void )hipFree( p->d_pr_groups );
-	( void )hipHostFree( p->h_pr );
-	if( p->pr_done )
-		( void )hipEventDestroy( p->pr_done );
-	( void )hipFree( p->d_se );
-	( void )hipFree( p->d_se_info );
-	( void )hipHostFree( p->h_se );
-	if( p->se_done )
-		( void )hipEventDestroy( p->se_done );
-	( void )hipFree( p->d_sc );
-	( void )hipFree( p->d_sc_image );
-	( void )hipHostFree( p->h_sc );
 	delete p;
 }
 
@@ -135,22 +97,25 @@ static rma::HitPost &post_of( rma_scanner_t *sc )
 	return *sc->post;
 }
 
+// *scratch is a complete scratch on `device`: the one that is there, or a new one in its place
 static int scratch_on( rma::HitWindowScratch **scratch, int device, char *err, size_t errlen )
 {
 	if( *scratch != nullptr && ( *scratch )->device == device )
 		return 0;
 	rma::hitwin_scratch_free( *scratch );
-	*scratch = new rma::HitWindowScratch;
-	rma::HitWindowScratch	*s = *scratch;
+	*scratch = nullptr;
+	std::unique_ptr<rma::HitWindowScratch, void ( * )( rma::HitWindowScratch * )>	made( new rma::HitWindowScratch, rma::hitwin_scratch_free );
+	rma::HitWindowScratch	*s = made.get();
 	s->device = device;
-	HIPCHK( hipStreamCreateWithFlags( &s->stream, hipStreamNonBlocking ) );
-	HIPCHK( dev_room( &s->d_fixed, &s->fixed_bytes, s->carve_dev( nullptr, size_t( HW_CHUNK ) ) ) );
-	s->carve_dev( s->d_fixed, size_t( HW_CHUNK ) );
+	HIPCHK( s->stream.create( hipStreamNonBlocking ) );
+	HIPCHK( s->d_fixed.room( s->carve_dev( nullptr, size_t( HW_CHUNK ) ) ) );
+	s->carve_dev( s->d_fixed.as<void>(), size_t( HW_CHUNK ) );
 	size_t	tmp = 0;
-	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, HW_CHUNK + 1, nullptr, &tmp, s->stream ) );
-	HIPCHK( dev_room( &s->d_tmp, &s->tmp_bytes, std::max<size_t>( tmp, 256 ) ) );
-	HIPCHK( host_room( &s->h_fixed, &s->h_fixed_bytes, s->carve_host( nullptr, size_t( HW_CHUNK ) ) ) );
-	s->carve_host( s->h_fixed, size_t( HW_CHUNK ) );
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, HW_CHUNK + 1, nullptr, &tmp, s->stream.get() ) );
+	HIPCHK( s->d_tmp.room( std::max<size_t>( tmp, 256 ) ) );
+	HIPCHK( s->h_fixed.room( s->carve_host( nullptr, size_t( HW_CHUNK ) ) ) );
+	s->carve_host( s->h_fixed.as<void>(), size_t( HW_CHUNK ) );
+	*scratch = made.release();
 	return 0;
 }
 
@@ -211,7 +176,7 @@ int letters_on_device( rma::HitWindowScratch *s, const rma_db *db, const uint8_t
 		*codes = 1;
 		return 0;
 	}
-	HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, s->stream ) );
+	HIPCHK( hipMemcpyAsync( s->d_tab, s->h_tab, 256, hipMemcpyHostToDevice, s->stream.get() ) );
 	return 0;
 }
 
@@ -222,10 +187,10 @@ int letters_on_device( rma::HitWindowScratch *s, const rma_db *db, const uint8_t
 int check_records( rma::HitWindowScratch *s, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits, int64_t n_hits,
 	void *stream, bool whole, void *zero, size_t zero_bytes, char *err, size_t errlen )
 {
-	hipStream_t	st = s->stream;
+	hipStream_t	st = s->stream.get();
 	if( rma::stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
 		return 1;
-	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	HIPCHK( hipStreamWaitEvent( st, db->ready.get(), 0 ) );
 	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
 	if( zero != nullptr )
 		HIPCHK( hipMemsetAsync( zero, 0, zero_bytes, st ) );
@@ -243,8 +208,8 @@ static int bad_record( rma::HitWindowScratch *s, const rma_db *db, const rma_pro
 {
 	const int	stride = rma_hit_stride( &prog );
 	std::vector<int32_t>	w( static_cast<size_t>( stride ) );
-	HIPCHK( hipMemcpyAsync( w.data(), d_hits + h * stride, size_t( stride ) * 4, hipMemcpyDeviceToHost, s->stream ) );
-	HIPCHK( hipStreamSynchronize( s->stream ) );
+	HIPCHK( hipMemcpyAsync( w.data(), d_hits + h * stride, size_t( stride ) * 4, hipMemcpyDeviceToHost, s->stream.get() ) );
+	HIPCHK( hipStreamSynchronize( s->stream.get() ) );
 	int32_t	lo, hi;
 	int	which;
 	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
@@ -292,7 +257,7 @@ int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rm
 	if( scratch_on( scratch, db->device, err, errlen ) )
 		return 1;
 	rma::HitWindowScratch	*s = *scratch;
-	hipStream_t	st = s->stream;
+	hipStream_t	st = s->stream.get();
 	const rma::HitWinShape	shape = rma::hitwin_shape( prog );
 	const uint8_t	*tab = nullptr;
 	int	codes = 0;
@@ -308,8 +273,8 @@ int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rm
 		const int32_t	*ch = d_hits + c0 * stride;
 		HIPCHK( rma::hit_spans( ch, cn, stride, shape, db->d_slen, db->d_text_start, db->n_seq, s->d_lo, s->d_len, s->d_src,
 			s->d_bad, st ) );
-		size_t	tb = s->tmp_bytes;
-		HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, st ) );
+		size_t	tb = s->d_tmp.bytes();
+		HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp.as<void>(), &tb, st ) );
 		HIPCHK( hipMemcpyAsync( s->h_off, s->d_off, size_t( cn + 1 ) * 8, hipMemcpyDeviceToHost, st ) );
 		HIPCHK( hipMemcpyAsync( s->h_lo, s->d_lo, size_t( cn ) * 4, hipMemcpyDeviceToHost, st ) );
 		if( c0 == 0 )
@@ -322,18 +287,18 @@ int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rm
 			while( b < cn && b - a < piece_records && s->h_off[ b + 1 ] - s->h_off[ a ] <= HW_PIECE_WINDOW )
 				b++;
 			const int64_t	bytes = s->h_off[ b ] - s->h_off[ a ];
-			HIPCHK( dev_room( &s->d_win, &s->win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
-			HIPCHK( host_room( &s->h_win, &s->h_win_cap, size_t( std::max<int64_t>( bytes, 256 ) ) ) );
-			HIPCHK( host_room( &s->h_rec, &s->rec_cap, size_t( b - a ) * stride * 4 ) );
-			HIPCHK( rma::hit_gather( db->text, b - a, s->d_src + a, s->d_off + a, tab, codes, static_cast<uint8_t *>( s->d_win ), st ) );
-			HIPCHK( hipMemcpyAsync( s->h_rec, ch + a * stride, size_t( b - a ) * stride * 4, hipMemcpyDeviceToHost, st ) );
+			HIPCHK( s->d_win.room( size_t( std::max<int64_t>( bytes, 256 ) ) ) );
+			HIPCHK( s->h_win.room( size_t( std::max<int64_t>( bytes, 256 ) ) ) );
+			HIPCHK( s->h_rec.room( size_t( b - a ) * stride * 4 ) );
+			HIPCHK( rma::hit_gather( db->text, b - a, s->d_src + a, s->d_off + a, tab, codes, s->d_win.as<uint8_t>(), st ) );
+			HIPCHK( hipMemcpyAsync( s->h_rec.as<void>(), ch + a * stride, size_t( b - a ) * stride * 4, hipMemcpyDeviceToHost, st ) );
 			if( bytes > 0 )
-				HIPCHK( hipMemcpyAsync( s->h_win, s->d_win, size_t( bytes ), hipMemcpyDeviceToHost, st ) );
+				HIPCHK( hipMemcpyAsync( s->h_win.as<void>(), s->d_win.as<void>(), size_t( bytes ), hipMemcpyDeviceToHost, st ) );
 			HIPCHK( hipStreamSynchronize( st ) );
 			s->piece_off.resize( size_t( b - a + 1 ) );
 			for( int64_t i = a; i <= b; i++ )
 				s->piece_off[ size_t( i - a ) ] = s->h_off[ i ] - s->h_off[ a ];
-			each( rma::HitWindowPiece{ static_cast<const int32_t *>( s->h_rec ), c0 + a, b - a, static_cast<const char *>( s->h_win ),
+			each( rma::HitWindowPiece{ s->h_rec.as<int32_t>(), c0 + a, b - a, s->h_win.as<char>(),
 				s->piece_off.data(), s->h_lo + a, db->h_slen.data(), db->n_seq } );
 			a = b;
 		}
@@ -363,15 +328,13 @@ int hit_structures_args( rma_scanner_t *sc, const rma_db *db, const int32_t *d_h
 	rma::HitPost	&p = post_of( sc );
 	if( scratch_on( &p.win, sc->device, err, errlen ) )
 		return 1;
-	if( p.d_hs_table == nullptr ){
+	if( !p.hs ){
 		// the program's table and, behind it, the running total
 		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
-		const size_t	at = ( sizeof( rma::HitStructTable ) + 7 ) & ~size_t( 7 );
-		void	*m = nullptr;
-		HIPCHK( hipMalloc( &m, at + sizeof( int64_t ) ) );
-		p.d_hs_table = static_cast<rma::HitStructTable *>( m );
-		p.d_hs_carry = reinterpret_cast<int64_t *>( static_cast<char *>( m ) + at );
-		HIPCHK( hipMemcpy( p.d_hs_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
+		rma::DevMem	m;
+		HIPCHK( m.exact( rma::HitPost::HS_CARRY_AT + sizeof( int64_t ) ) );
+		HIPCHK( hipMemcpy( m.as<void>(), &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
+		p.hs = std::move( m );
 	}
 	return 0;
 }
@@ -381,9 +344,9 @@ int hit_structures_spans( rma_scanner_t *sc, const rma_db *db, const int32_t *ch
 {
 	rma::HitWindowScratch	*s = sc->post->win;
 	HIPCHK( rma::hit_spans( ch, cn, rma_hit_stride( &sc->prog ), rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq,
-		s->d_lo, s->d_len, s->d_src, bad, s->stream ) );
-	size_t	tb = s->tmp_bytes;
-	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp, &tb, s->stream ) );
+		s->d_lo, s->d_len, s->d_src, bad, s->stream.get() ) );
+	size_t	tb = s->d_tmp.bytes();
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp.as<void>(), &tb, s->stream.get() ) );
 	return 0;
 }
 
@@ -394,23 +357,23 @@ int hit_structures_count( rma_scanner_t *sc, const rma_db *db, const int32_t *d_
 {
 	rma::HitPost	&p = *sc->post;
 	rma::HitWindowScratch	*s = p.win;
-	hipStream_t	st = s->stream;
+	hipStream_t	st = s->stream.get();
 	const int	stride = rma_hit_stride( &sc->prog );
 	// d_bad[ 0 ]: the least index of a bad record, counted over the call; d_bad[ 2 ]: where the spans of a later chunk,
 	// which count from the chunk's first record, put theirs (the same records, already judged).  A call of one chunk
 	// has no pass over all records: the chunk's own spans judge them.
 	const bool	chunks = n_hits > HW_CHUNK;
-	if( check_records( s, db, sc->prog, d_hits, n_hits, stream, chunks, p.d_hs_carry, sizeof( int64_t ), err, errlen ) )
+	if( check_records( s, db, sc->prog, d_hits, n_hits, stream, chunks, p.hs_carry(), sizeof( int64_t ), err, errlen ) )
 		return 1;
-	HIPCHK( rma::hit_helix_check( d_hits, n_hits, stride, p.d_hs_table, s->d_bad, st ) );
+	HIPCHK( rma::hit_helix_check( d_hits, n_hits, stride, p.hs_table(), s->d_bad, st ) );
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
 		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
 		if( hit_structures_spans( sc, db, d_hits + c0 * stride, cn, chunks ? s->d_bad + 2 : s->d_bad, err, errlen ) )
 			return 1;
-		HIPCHK( rma::hit_carry_add( p.d_hs_carry, s->d_off + cn, st ) );
+		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
 	}
 	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.d_hs_carry, sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
 	HIPCHK( hipStreamSynchronize( st ) );
 	if( s->h_bad[ 0 ] != ~0ull ){
 		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
@@ -470,9 +433,9 @@ extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const 
 	}
 	rma::HitPost	&p = *sc->post;
 	rma::HitWindowScratch	*s = p.win;
-	hipStream_t	st = s->stream;
+	hipStream_t	st = s->stream.get();
 	const int	stride = rma_hit_stride( &sc->prog );
-	HIPCHK( hipMemsetAsync( p.d_hs_carry, 0, sizeof( int64_t ), st ) );
+	HIPCHK( hipMemsetAsync( p.hs_carry(), 0, sizeof( int64_t ), st ) );
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
 		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
 		const int32_t	*ch = d_hits + c0 * stride;
@@ -480,9 +443,9 @@ extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const 
 		if( n_hits > HW_CHUNK && hit_structures_spans( sc, db, ch, cn, s->d_bad + 2, err, errlen ) )
 			return 1;
 		const rma::HitStructOut	out{ d_off + c0, d_lo + c0, d_base, d_elem, d_mate };
-		HIPCHK( rma::hit_struct_fill( db->text, ch, cn, stride, rma::hitwin_shape( sc->prog ), p.d_hs_table, s->d_lo, s->d_src, s->d_off,
-			p.d_hs_carry, tab, codes, out, c0 + cn == n_hits, st ) );
-		HIPCHK( rma::hit_carry_add( p.d_hs_carry, s->d_off + cn, st ) );
+		HIPCHK( rma::hit_struct_fill( db->text, ch, cn, stride, rma::hitwin_shape( sc->prog ), p.hs_table(), s->d_lo, s->d_src, s->d_off,
+			p.hs_carry(), tab, codes, out, c0 + cn == n_hits, st ) );
+		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
 	}
 	return rma::stream_after( caller, st, err, errlen );
 }
@@ -500,7 +463,7 @@ int hit_alignment_widths( rma_scanner_t *sc, const rma_db *db, const int32_t *d_
 	char *err, size_t errlen )
 {
 	rma::HitWindowScratch	*s = sc->post->win;
-	hipStream_t	st = s->stream;
+	hipStream_t	st = s->stream.get();
 	const int	stride = rma_hit_stride( &sc->prog );
 	const rma::HitWinShape	shape = rma::hitwin_shape( sc->prog );
 	int32_t	*d_w = reinterpret_cast<int32_t *>( s->d_len ), *h_w = reinterpret_cast<int32_t *>( s->h_off );
@@ -577,7 +540,7 @@ extern "C" int rma_hit_alignment( rma_scanner_t *sc, const rma_db_t *db, const i
 		( d_pos != nullptr && rma::check_device_bytes( d_pos, sc->device, 0, n_hits * W * 4, "the positions", err, errlen ) ) ) )
 		return 1;
 	rma::HitWindowScratch	*s = sc->post->win;
-	hipStream_t	st = s->stream, caller = static_cast<hipStream_t>( stream );
+	hipStream_t	st = s->stream.get(), caller = static_cast<hipStream_t>( stream );
 	// the letters, as rma_hit_structures takes them: on their way ahead of the check, whose synchronisation leaves the
 	// page-locked copy free for the next call
 	const uint8_t	*tab = nullptr;
@@ -627,38 +590,41 @@ extern "C" int rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int3
 		return 1;
 	rma::HitPost	&p = post_of( sc );
 	hipStream_t	st = static_cast<hipStream_t>( stream );
-	if( p.d_pr_table == nullptr ){
-		const size_t	at = align256( sizeof( rma::PruneTable ) );
-		void	*m = nullptr;
-		HIPCHK( hipMalloc( &m, at + 256 ) );
-		p.d_pr_table = static_cast<rma::PruneTable *>( m );
-		HIPCHK( hipMemcpy( p.d_pr_table, &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
-		HIPCHK( hipEventCreateWithFlags( &p.pr_done, hipEventDisableTiming ) );
-		HIPCHK( hipEventRecord( p.pr_done, st ) );
+	if( !p.pr_table ){
+		rma::DevMem	table;
+		rma::PinMem	words;
+		rma::Event	done;
+		HIPCHK( table.exact( align256( sizeof( rma::PruneTable ) ) + 256 ) );
+		HIPCHK( hipMemcpy( table.as<void>(), &tab, sizeof( tab ), hipMemcpyHostToDevice ) );
+		HIPCHK( words.exact( 256 ) );
+		HIPCHK( done.create( hipEventDisableTiming ) );
+		HIPCHK( hipEventRecord( done.get(), st ) );
+		p.pr_table = std::move( table );
+		p.h_pr = std::move( words );
+		p.pr_done = std::move( done );
 	}
 	// behind the kernels of the call before this one (they read the scratch) and the database's tables
-	HIPCHK( hipStreamWaitEvent( st, p.pr_done, 0 ) );
-	HIPCHK( hipStreamWaitEvent( st, db->ready, 0 ) );
+	HIPCHK( hipStreamWaitEvent( st, p.pr_done.get(), 0 ) );
+	HIPCHK( hipStreamWaitEvent( st, db->ready.get(), 0 ) );
 	const size_t	n = size_t( n_hits ), parts = size_t( rma::prune_parts( n_hits ) );
 	rma::PruneDev	pd;
-	HIPCHK( dev_room( &p.d_pr, &p.pr_bytes, rma::prune_carve( pd, nullptr, n, parts, size_t( row ) ) ) );
-	HIPCHK( host_room( &p.h_pr, &p.h_pr_bytes, 256 ) );
-	rma::prune_carve( pd, p.d_pr, n, parts, size_t( row ) );
-	char	*dt = reinterpret_cast<char *>( p.d_pr_table ) + align256( sizeof( rma::PruneTable ) );
-	pd.tab = p.d_pr_table;
+	HIPCHK( p.d_pr.room( rma::prune_carve( pd, nullptr, n, parts, size_t( row ) ) ) );
+	rma::prune_carve( pd, p.d_pr.as<void>(), n, parts, size_t( row ) );
+	char	*dt = p.pr_table.as<char>() + align256( sizeof( rma::PruneTable ) );
+	pd.tab = p.pr_table.as<rma::PruneTable>();
 	pd.groups = nullptr;
 	pd.bad = reinterpret_cast<unsigned long long *>( dt );
 	pd.n_blocks = reinterpret_cast<long long *>( dt + 8 );
 	if( group_of_entry != nullptr && db->n_seq > 0 ){
 		// (pageable memory: the copy has left the caller's array when the call returns)
-		HIPCHK( dev_room( &p.d_pr_groups, &p.pr_groups_bytes, size_t( db->n_seq ) * 4 ) );
-		HIPCHK( hipMemcpyAsync( p.d_pr_groups, group_of_entry, size_t( db->n_seq ) * 4, hipMemcpyHostToDevice, st ) );
-		pd.groups = static_cast<const int32_t *>( p.d_pr_groups );
+		HIPCHK( p.d_pr_groups.room( size_t( db->n_seq ) * 4 ) );
+		HIPCHK( hipMemcpyAsync( p.d_pr_groups.as<void>(), group_of_entry, size_t( db->n_seq ) * 4, hipMemcpyHostToDevice, st ) );
+		pd.groups = p.d_pr_groups.as<int32_t>();
 	}
 	HIPCHK( hipMemsetAsync( pd.bad, 0xff, sizeof( unsigned long long ), st ) );
 	HIPCHK( hipMemsetAsync( pd.n_blocks, 0, sizeof( long long ), st ) );
 	HIPCHK( rma::prune_blocks( d_hits, n_hits, stride, rma::hitwin_shape( sc->prog ), row, db->d_slen, db->n_seq, pd, st ) );
-	unsigned long long	*h = static_cast<unsigned long long *>( p.h_pr );
+	unsigned long long	*h = p.h_pr.as<unsigned long long>();
 	HIPCHK( hipMemcpyAsync( h, pd.bad, 16, hipMemcpyDeviceToHost, st ) );
 	HIPCHK( hipStreamSynchronize( st ) );
 	if( h[ 0 ] != ~0ull ){
@@ -672,7 +638,7 @@ extern "C" int rma_prune_hits( rma_scanner_t *sc, const rma_db_t *db, const int3
 		return 1;
 	}
 	HIPCHK( rma::prune_rezip( n_hits, row, pd, n_blocks, d_keep, st ) );
-	HIPCHK( hipEventRecord( p.pr_done, st ) );
+	HIPCHK( hipEventRecord( p.pr_done.get(), st ) );
 	return 0;
 }
 
@@ -707,23 +673,10 @@ extern "C" int rma_scanner_load_energy_tables( rma_scanner_t *sc, const char *di
 	}
 	HIPCHK( hipSetDevice( sc->device ) );
 	// (behind the energy kernels of rma_structure_energies calls that read the tables now)
-	if( sc->post != nullptr && sc->post->se_done != nullptr )
-		HIPCHK( hipEventSynchronize( sc->post->se_done ) );
-	if( efn ){
-		std::vector<int16_t>	t16;
-		std::vector<int32_t>	tlkey;
-		rma::efn_tables16( efn.get(), t16, tlkey );
-		if( sc->d_t16 == nullptr )
-			HIPCHK( hipMalloc( &sc->d_t16, t16.size() * sizeof( int16_t ) ) );
-		HIPCHK( hipMemcpy( sc->d_t16, t16.data(), t16.size() * sizeof( int16_t ), hipMemcpyHostToDevice ) );
-		if( sc->d_tlkey == nullptr )
-			HIPCHK( hipMalloc( &sc->d_tlkey, tlkey.size() * sizeof( int32_t ) ) );
-		HIPCHK( hipMemcpy( sc->d_tlkey, tlkey.data(), tlkey.size() * sizeof( int32_t ), hipMemcpyHostToDevice ) );
-		if( sc->d_loginc == nullptr )
-			HIPCHK( hipMalloc( &sc->d_loginc, RMA_EFN_LOGINC * sizeof( int32_t ) ) );
-		HIPCHK( hipMemcpy( sc->d_loginc, efn->loginc, RMA_EFN_LOGINC * sizeof( int32_t ), hipMemcpyHostToDevice ) );
-		sc->have_efn = true;
-	}
+	if( sc->post != nullptr && sc->post->se_done.get() != nullptr )
+		HIPCHK( hipEventSynchronize( sc->post->se_done.get() ) );
+	if( efn && rma::efn_tables_to_device( sc, efn.get(), err, errlen ) )
+		return 1;
 	if( efn2 && rma_scanner_set_efn2data( sc, efn2.get(), err, errlen ) )
 		return 1;
 	return 0;
@@ -814,7 +767,7 @@ extern "C" int rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off, 
 	}
 	if( n == 0 )
 		return 0;
-	if( ( d_efn != nullptr && !sc->have_efn ) || ( d_efn2 != nullptr && sc->d_efn2 == nullptr ) ){
+	if( ( d_efn != nullptr && !sc->have_efn ) || ( d_efn2 != nullptr && !sc->d_efn2 ) ){
 		snprintf( err, errlen, "%s: the scanner has no %s tables: its descriptor has no such call, and rma_scanner_load_energy_tables() was not called",
 			who, d_efn != nullptr && !sc->have_efn ? "efn()" : "efn2()" );
 		return 1;
@@ -828,17 +781,23 @@ extern "C" int rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off, 
 		return 1;
 	rma::HitPost	&p = post_of( sc );
 	hipStream_t	st = static_cast<hipStream_t>( stream );
-	if( p.d_se == nullptr ){
-		HIPCHK( hipMalloc( &p.d_se, SE_CODES_AT + 256 ) );
-		HIPCHK( hipHostMalloc( &p.h_se, SE_CODES_AT + 256, hipHostMallocDefault ) );
-		HIPCHK( hipEventCreateWithFlags( &p.se_done, hipEventDisableTiming ) );
-		HIPCHK( hipEventRecord( p.se_done, st ) );
+	if( !p.d_se ){
+		rma::DevMem	dev;
+		rma::PinMem	pin;
+		rma::Event	done;
+		HIPCHK( dev.exact( SE_CODES_AT + 256 ) );
+		HIPCHK( pin.exact( SE_CODES_AT + 256 ) );
+		HIPCHK( done.create( hipEventDisableTiming ) );
+		HIPCHK( hipEventRecord( done.get(), st ) );
+		p.d_se = std::move( dev );
+		p.h_se = std::move( pin );
+		p.se_done = std::move( done );
 	}
 	// behind the kernels of the call before this one: they read the scratch
-	HIPCHK( hipStreamWaitEvent( st, p.se_done, 0 ) );
-	HIPCHK( dev_room( &p.d_se_info, &p.se_info_bytes, size_t( n ) * 4 ) );
-	unsigned long long	*d_bad = static_cast<unsigned long long *>( p.d_se ), *h_bad = static_cast<unsigned long long *>( p.h_se );
-	uint8_t	*d_code = static_cast<uint8_t *>( p.d_se ) + SE_CODES_AT, *h_code = static_cast<uint8_t *>( p.h_se ) + SE_CODES_AT;
+	HIPCHK( hipStreamWaitEvent( st, p.se_done.get(), 0 ) );
+	HIPCHK( p.d_se_info.room( size_t( n ) * 4 ) );
+	unsigned long long	*d_bad = p.d_se.as<unsigned long long>(), *h_bad = p.h_se.as<unsigned long long>();
+	uint8_t	*d_code = p.d_se.as<uint8_t>() + SE_CODES_AT, *h_code = p.h_se.as<uint8_t>() + SE_CODES_AT;
 	// (the page-locked copy is free: every call before this one has waited behind its upload)
 	for( int b = 0; b < 256; b++ )
 		h_code[ b ] = uint8_t( rmse_letter_code( letters != nullptr ? letters[ b ] : rma::hitwin_reader_letter( static_cast<unsigned char>( b ) ) ) );
@@ -846,7 +805,7 @@ extern "C" int rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off, 
 	HIPCHK( hipMemsetAsync( d_bad, 0xff, sizeof( unsigned long long ), st ) );
 	HIPCHK( hipMemsetAsync( d_bad + 1, 0, sizeof( unsigned long long ), st ) );
 	const rma::StructBatch	batch{ d_off, d_base, d_pair, pair_stride, n, total };
-	int32_t	*d_info = static_cast<int32_t *>( p.d_se_info );
+	int32_t	*d_info = p.d_se_info.as<int32_t>();
 	const int	cus = sc->grid_blocks / 8, wgs = sc->opt.struct_wgs;
 	HIPCHK( rma::struct_check( batch, d_info, d_bad, wgs, cus, st ) );
 	HIPCHK( hipMemcpyAsync( h_bad, d_bad, 2 * sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
@@ -854,12 +813,13 @@ extern "C" int rma_structure_energies( rma_scanner_t *sc, const int64_t *d_off, 
 	if( h_bad[ 0 ] != ~0ull )
 		return bad_structure( batch, int64_t( h_bad[ 0 ] ), st, err, errlen );
 	if( d_efn != nullptr || d_efn2 != nullptr ){
-		const rma::StructTables	t{ d_efn != nullptr ? sc->d_t16 : nullptr, sc->d_tlkey, sc->d_loginc, d_efn2 != nullptr ? sc->d_efn2 : nullptr, d_code };
+		const rma::StructTables	t{ d_efn != nullptr ? sc->d_t16.as<int16_t>() : nullptr, sc->d_tlkey.as<int32_t>(), sc->d_loginc.as<int32_t>(),
+			d_efn2 != nullptr ? sc->efn2() : nullptr, d_code };
 		HIPCHK( rma::struct_energies( batch, d_info, t, d_efn, d_efn2, 0, wgs, cus, st ) );
 		if( h_bad[ 1 ] != 0 )
 			HIPCHK( rma::struct_energies( batch, d_info, t, d_efn, d_efn2, 1, wgs, cus, st ) );
 	}
-	HIPCHK( hipEventRecord( p.se_done, st ) );
+	HIPCHK( hipEventRecord( p.se_done.get(), st ) );
 	return 0;
 }
 
@@ -911,17 +871,18 @@ extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const r
 	}
 	rma::HitPost	&p = *sc->post;
 	rma::HitWindowScratch	*s = p.win;
-	hipStream_t	st = s->stream, caller = static_cast<hipStream_t>( stream );
+	hipStream_t	st = s->stream.get(), caller = static_cast<hipStream_t>( stream );
 	const size_t	n = size_t( n_hits ), flags = ( n + 7 ) & ~size_t( 7 ), want = SC_RESULTS_AT + 2 * flags + 8 * n;
-	if( want > p.sc_bytes )		// (the copies of the call before this one may still read the block that goes)
+	if( want > p.d_sc.bytes() )		// (the copies of the call before this one may still read the block that goes)
 		HIPCHK( hipStreamSynchronize( st ) );
-	HIPCHK( dev_room( &p.d_sc, &p.sc_bytes, want ) );
-	if( p.h_sc == nullptr )
-		HIPCHK( hipHostMalloc( &p.h_sc, SC_RESULTS_AT, hipHostMallocDefault ) );
+	HIPCHK( p.d_sc.room( want ) );
+	if( !p.h_sc )
+		HIPCHK( p.h_sc.exact( SC_RESULTS_AT ) );
 	if( p.sc_serial != sp->img.serial ){
 		HIPCHK( hipStreamSynchronize( st ) );
-		HIPCHK( dev_room( &p.d_sc_image, &p.sc_image_bytes, size_t( m->bytes ) ) );
-		HIPCHK( hipMemcpy( p.d_sc_image, m, size_t( m->bytes ), hipMemcpyHostToDevice ) );
+		p.sc_serial = 0;		// (no image's until this one's bytes are in)
+		HIPCHK( p.d_sc_image.room( size_t( m->bytes ) ) );
+		HIPCHK( hipMemcpy( p.d_sc_image.as<void>(), m, size_t( m->bytes ), hipMemcpyHostToDevice ) );
 		p.sc_serial = sp->img.serial;
 	}
 	const uint8_t	*tab = nullptr;
@@ -929,17 +890,17 @@ extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const r
 	if( letters_on_device( s, db, letters, &tab, &codes, err, errlen ) ||
 		check_records( s, db, sc->prog, d_hits, n_hits, stream, false, nullptr, 0, err, errlen ) )
 		return 1;
-	char	*base = static_cast<char *>( p.d_sc );
-	unsigned long long	*d_words = reinterpret_cast<unsigned long long *>( base ), *h_words = static_cast<unsigned long long *>( p.h_sc );
+	char	*base = p.d_sc.as<char>();
+	unsigned long long	*d_words = reinterpret_cast<unsigned long long *>( base ), *h_words = p.h_sc.as<unsigned long long>();
 	RmsResult	*d_detail = reinterpret_cast<RmsResult *>( base + SC_DETAIL_AT );
-	RmsResult	*h_detail = reinterpret_cast<RmsResult *>( static_cast<char *>( p.h_sc ) + SC_DETAIL_AT );
+	RmsResult	*h_detail = reinterpret_cast<RmsResult *>( p.h_sc.as<char>() + SC_DETAIL_AT );
 	uint8_t	*acc = reinterpret_cast<uint8_t *>( base + SC_RESULTS_AT );
 	int8_t	*kind = reinterpret_cast<int8_t *>( acc + flags );
 	double	*score = reinterpret_cast<double *>( acc + 2 * flags );
 	HIPCHK( hipMemsetAsync( d_words, 0xff, 2 * sizeof( unsigned long long ), st ) );
 	const int	stride = rma_hit_stride( &sc->prog );
 	auto batch = [&]( int64_t c0, int64_t cn, RmsResult *detail ){
-		return rma::ScoreBatch{ p.d_sc_image, m->bytes, m->stack, m->n_vars, d_hits + c0 * stride, ( long long )cn, ( long long )c0, stride,
+		return rma::ScoreBatch{ p.d_sc_image.as<RmsImage>(), m->bytes, m->stack, m->n_vars, d_hits + c0 * stride, ( long long )cn, ( long long )c0, stride,
 			rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq, db->text, tab, codes, sc->opt.score_budget,
 			acc + c0, score + c0, kind + c0, d_words, d_words + 1, detail };
 	};

@@ -10,21 +10,21 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
+#include "rm_hip_own.h"
 
 namespace rma {
 
 struct DevHitSort {
-	unsigned long long	*keys[ 2 ] = { nullptr, nullptr };
-	unsigned	*vals[ 2 ] = { nullptr, nullptr };
-	void	*tmp = nullptr;
-	size_t	tmp_bytes = 0;
-	int32_t	*d_out = nullptr;
-	int	*d_flag = nullptr;
-	int64_t	cap = 0;
+	DevMem	keys[ 2 ], vals[ 2 ];	// 64-bit keys and 32-bit slots, before and after the sort
+	DevMem	tmp;			// the library's work area
+	DevMem	out, flag;		// the ordered records, one int
+	int64_t	cap = 0;		// records there is room for: all six buffers or none (0)
 	int	stride = 0;
 	int	w_ord = 20;	// bits for the order word (pieces of items count in their own ranges, rm_scan_kernel.h PIECE_ORDER_BITS); widened after a scan whose order words did not fit
 
-	// room for cap records of stride words
+	int32_t	*d_out() const { return out.as<int32_t>(); }
+	int	*d_flag() const { return flag.as<int>(); }
+	// room for cap records of stride words; on failure the object is as release() leaves it: cap 0, no buffer
 	hipError_t	reserve( int64_t cap, int stride );
 	// Enqueue on s: d_out[ n ][ stride ] = d_hits[ n ][ stride ] in order, order word renumbered;
 	// *d_flag != 0 afterwards if some header word did not fit (then d_out is not to be used).

@@ -82,42 +82,36 @@ hipError_t relabel_entries( int32_t *d_hits, int64_t n, int stride, const int32_
 
 void DevHitSort::release()
 {
-	for( int i = 0; i < 2; i++ ){
-		if( keys[ i ] ) ( void )hipFree( keys[ i ] );
-		if( vals[ i ] ) ( void )hipFree( vals[ i ] );
-		keys[ i ] = nullptr;
-		vals[ i ] = nullptr;
-	}
-	if( tmp ) ( void )hipFree( tmp );
-	if( d_out ) ( void )hipFree( d_out );
-	if( d_flag ) ( void )hipFree( d_flag );
-	tmp = nullptr;
-	d_out = nullptr;
-	d_flag = nullptr;
+	for( DevMem *m : { &keys[ 0 ], &keys[ 1 ], &vals[ 0 ], &vals[ 1 ], &tmp, &out, &flag } )
+		m->reset();
 	cap = 0;
-	tmp_bytes = 0;
 }
 
+// (all or nothing: a caller that goes on without the ordering -- rma_scanner_create -- finds cap 0, not a part of it)
 hipError_t DevHitSort::reserve( int64_t want, int stride_ )
 {
 	if( want <= cap && stride_ == stride )
 		return hipSuccess;
-	const int	keep = w_ord;
 	release();
-	w_ord = keep;
-	hipError_t	e;
-	for( int i = 0; i < 2; i++ ){
-		if( ( e = hipMalloc( &keys[ i ], size_t( want ) * sizeof( unsigned long long ) ) ) != hipSuccess ) return e;
-		if( ( e = hipMalloc( &vals[ i ], size_t( want ) * sizeof( unsigned ) ) ) != hipSuccess ) return e;
-	}
-	if( ( e = hipMalloc( &d_out, size_t( want ) * stride_ * sizeof( int32_t ) ) ) != hipSuccess ) return e;
-	if( ( e = hipMalloc( &d_flag, sizeof( int ) ) ) != hipSuccess ) return e;
+	const size_t	n = size_t( want );
 	size_t	bytes = 0;
-	if( ( e = rocprim::radix_sort_pairs( nullptr, bytes, keys[ 0 ], keys[ 1 ], vals[ 0 ], vals[ 1 ], size_t( want ), 0u, 64u ) ) != hipSuccess ) return e;
-	if( bytes == 0 )
-		bytes = 16;
-	if( ( e = hipMalloc( &tmp, bytes ) ) != hipSuccess ) return e;
-	tmp_bytes = bytes;
+	hipError_t	e = hipSuccess;
+	for( int i = 0; i < 2 && e == hipSuccess; i++ )
+		if( ( e = keys[ i ].exact( n * sizeof( unsigned long long ) ) ) == hipSuccess )
+			e = vals[ i ].exact( n * sizeof( unsigned ) );
+	if( e == hipSuccess )
+		e = out.exact( n * stride_ * sizeof( int32_t ) );
+	if( e == hipSuccess )
+		e = flag.exact( sizeof( int ) );
+	if( e == hipSuccess )
+		e = rocprim::radix_sort_pairs( nullptr, bytes, keys[ 0 ].as<unsigned long long>(), keys[ 1 ].as<unsigned long long>(),
+			vals[ 0 ].as<unsigned>(), vals[ 1 ].as<unsigned>(), n, 0u, 64u );
+	if( e == hipSuccess )
+		e = tmp.exact( bytes != 0 ? bytes : 16 );
+	if( e != hipSuccess ){
+		release();
+		return e;
+	}
 	cap = want;
 	stride = stride_;
 	return hipSuccess;
@@ -137,9 +131,11 @@ hipError_t DevHitSort::run( const int32_t *d_hits, int64_t n, int w_seq, int w_p
 	if( w.ord < 4 )
 		return hipErrorInvalidValue;
 	hipError_t	e;
-	if( ( e = hipMemsetAsync( d_flag, 0, sizeof( int ), s ) ) != hipSuccess ) return e;
+	unsigned long long	*k0 = keys[ 0 ].as<unsigned long long>(), *k1 = keys[ 1 ].as<unsigned long long>();
+	unsigned	*v0 = vals[ 0 ].as<unsigned>(), *v1 = vals[ 1 ].as<unsigned>();
+	if( ( e = hipMemsetAsync( d_flag(), 0, sizeof( int ), s ) ) != hipSuccess ) return e;
 	hipLaunchKernelGGL( hit_keys_kernel, dim3( unsigned( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, s,
-		d_hits, ( long long )n, stride, w, keys[ 0 ], vals[ 0 ], d_flag );
+		d_hits, ( long long )n, stride, w, k0, v0, d_flag() );
 	if( ( e = hipGetLastError() ) != hipSuccess ) return e;
 	// All 64 bits of the key, whatever the fields in use: the library picks its kernels by the bit range,
 	// and a range that changes with the database means kernels that are loaded in the middle of a search
@@ -147,20 +143,16 @@ hipError_t DevHitSort::run( const int32_t *d_hits, int64_t n, int w_seq, int w_p
 	// few thousand keys cost microseconds.
 	const unsigned	bits = 64u;
 	size_t	bytes = 0;
-	if( ( e = rocprim::radix_sort_pairs( nullptr, bytes, keys[ 0 ], keys[ 1 ], vals[ 0 ], vals[ 1 ], size_t( n ), 0u, bits, s ) ) != hipSuccess ) return e;
-	if( bytes > tmp_bytes ){
+	if( ( e = rocprim::radix_sort_pairs( nullptr, bytes, k0, k1, v0, v1, size_t( n ), 0u, bits, s ) ) != hipSuccess ) return e;
+	if( bytes > tmp.bytes() ){
 		// (the library picks its algorithm by size: what a small sort needs is not bounded by the largest one's)
 		if( ( e = hipStreamSynchronize( s ) ) != hipSuccess ) return e;
-		( void )hipFree( tmp );
-		tmp = nullptr;
-		tmp_bytes = 0;
-		if( ( e = hipMalloc( &tmp, bytes ) ) != hipSuccess ) return e;
-		tmp_bytes = bytes;
+		if( ( e = tmp.exact( bytes ) ) != hipSuccess ) return e;
 	}
-	bytes = tmp_bytes;
-	if( ( e = rocprim::radix_sort_pairs( tmp, bytes, keys[ 0 ], keys[ 1 ], vals[ 0 ], vals[ 1 ], size_t( n ), 0u, bits, s ) ) != hipSuccess ) return e;
+	bytes = tmp.bytes();
+	if( ( e = rocprim::radix_sort_pairs( tmp.as<void>(), bytes, k0, k1, v0, v1, size_t( n ), 0u, bits, s ) ) != hipSuccess ) return e;
 	hipLaunchKernelGGL( hit_gather_kernel, dim3( unsigned( ( n + 3 ) / 4 ) ), dim3( 256 ), 0, s,
-		d_hits, vals[ 1 ], keys[ 1 ], w.ord, ( long long )n, stride, d_out );
+		d_hits, v1, k1, w.ord, ( long long )n, stride, d_out() );
 	return hipGetLastError();
 }
 

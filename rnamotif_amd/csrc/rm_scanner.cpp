@@ -6,7 +6,8 @@
 //   DevCtx (one per GPU)  the upload stream and a cache of device blocks: a database that is
 //                         destroyed gives its block back, the next one of about that size takes
 //                         it -- no hipMalloc / hipFree per database (the loop over batches of the
-//                         command line, rnamot.c:158-185, makes one per batch)
+//                         command line, rnamot.c:158-185, makes one per batch); it lives as long
+//                         as the process
 //   rma_db                the packed bases of some entries in HBM -- codes, ambiguity mask,
 //                         offsets, lengths, start-position ranges: nothing in it depends on a
 //                         descriptor -- plus, per launch shape that has scanned it, the tiling
@@ -15,7 +16,8 @@
 //                         work areas and ordering stage
 // A database is uploaded on the device's upload stream; a scan waits for that on its own stream
 // (an event), so the upload of the next database runs under the scan of this one.
-// The two structs are defined in rm_scanner_impl.h; the calls that consume records already on the
+// The two structs are defined in rm_scanner_impl.h, which also says who frees what and when (the
+// owners are rm_hip_own.h's); the calls that consume records already on the
 // device (windows, structures, alignments, pruning) are rm_hitpost.cpp's.
 #include <algorithm>
 #include <chrono>
@@ -41,7 +43,7 @@ using rma::Block;
 struct rma::DevCtx {
 	int	device = 0;
 	std::mutex	mu;
-	hipStream_t	upload = nullptr;
+	rma::Stream	upload;
 	std::vector<Block>	spare;		// blocks of destroyed databases, waiting for the next one
 	size_t	spare_bytes = 0;
 	// Take a block of at least `bytes`: a spare one that is not more than twice that, else a new one.
@@ -103,24 +105,24 @@ using rma::DevCtx;
 namespace {
 
 std::mutex	g_ctx_mu;
-std::vector<std::unique_ptr<DevCtx>>	g_ctx;
+std::vector<DevCtx *>	g_ctx;		// (never destroyed: no call of the runtime is made while the process exits)
 
 // (the caller has made `device` current)
 DevCtx *dev_ctx( int device, char *err, size_t errlen )
 {
 	std::lock_guard<std::mutex>	lk( g_ctx_mu );
-	for( auto &c : g_ctx )
+	for( DevCtx *c : g_ctx )
 		if( c->device == device )
-			return c.get();
+			return c;
 	std::unique_ptr<DevCtx>	c( new DevCtx );
 	c->device = device;
-	hipError_t	e = hipStreamCreateWithFlags( &c->upload, hipStreamNonBlocking );
+	hipError_t	e = c->upload.create( hipStreamNonBlocking );
 	if( e != hipSuccess ){
 		snprintf( err, errlen, "hipStreamCreate (upload stream): %s", hipGetErrorString( e ) );
 		return nullptr;
 	}
-	g_ctx.push_back( std::move( c ) );
-	return g_ctx.back().get();
+	g_ctx.push_back( c.release() );
+	return g_ctx.back();
 }
 
 }	// namespace
@@ -131,8 +133,7 @@ struct rma::Layout : rma::LayoutKey, rma::Tiling {
 	int64_t	*d_tile_start = nullptr;
 	int32_t	*d_tile_seq = nullptr;
 	int32_t	*d_tile_meta = nullptr;
-	hipEvent_t	ready = nullptr;	// the copies are complete: every scan waits for it on its stream
-	~Layout(){ if( ready != nullptr ) ( void )hipEventDestroy( ready ); }
+	rma::Event	ready;		// the copies are complete: every scan waits for it on its stream
 };
 using rma::Layout;
 
@@ -150,6 +151,10 @@ bool rma::is_device_db( const rma_db *db )
 extern "C" void rma_db_destroy( rma_db_t *db );
 extern "C" void rma_scanner_destroy( rma_scanner_t *sc );
 extern "C" int rma_scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, char *err, size_t errlen );
+
+// a scanner / a database under construction: destroyed on every way out but release()
+using ScannerPtr = std::unique_ptr<rma_scanner, void ( * )( rma_scanner * )>;
+using DbPtr = std::unique_ptr<rma_db, void ( * )( rma_db * )>;
 
 extern "C" int rma_device_count( void )
 {
@@ -185,9 +190,8 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 	rma_scanner_t **out, char *err, size_t errlen )
 {
 	*out = nullptr;
-	rma_scanner	*sc = new rma_scanner;
-	// every early return below releases the scanner and what it holds by then
-	struct ScGuard { rma_scanner *p; ~ScGuard(){ if( p ) rma_scanner_destroy( p ); } }	guard{ sc };
+	ScannerPtr	guard( new rma_scanner, rma_scanner_destroy );
+	rma_scanner	*sc = guard.get();
 	memcpy( &sc->prog, prog, sizeof( rma_program_t ) );	// (every byte, padding too: rma_score_hits compares the bytes with an image's copy)
 	sc->opt.latch();
 	// (host work first: a descriptor outside the device limits is refused with its reason whether
@@ -218,50 +222,58 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 	sc->ctx = dev_ctx( device, err, errlen );
 	if( sc->ctx == nullptr )
 		return 1;
-	HIPCHK( hipStreamCreateWithFlags( &sc->stream, hipStreamNonBlocking ) );
+	HIPCHK( sc->stream.create( hipStreamNonBlocking ) );
 	for( int i = 0; i < 5; i++ )
-		HIPCHK( hipEventCreate( &sc->ev[ i ] ) );
+		HIPCHK( sc->ev[ i ].create( hipEventDefault ) );
 	{
 		// the device gets the compact image; sc->dprog stays the full struct for the host
 		std::vector<char>	img( sizeof( rmd_program_t ) );
 		sc->prog_bytes = int( rmd_make_image( &sc->dprog, img.data() ) );
-		HIPCHK( hipMalloc( &sc->d_prog, size_t( sc->prog_bytes ) ) );
-		HIPCHK( hipMemcpy( sc->d_prog, img.data(), size_t( sc->prog_bytes ), hipMemcpyHostToDevice ) );
+		HIPCHK( sc->d_prog.exact( size_t( sc->prog_bytes ) ) );
+		HIPCHK( hipMemcpy( sc->d_prog.as<void>(), img.data(), size_t( sc->prog_bytes ), hipMemcpyHostToDevice ) );
 	}
-	HIPCHK( hipMalloc( &sc->d_counters, RMK_N_COUNTERS * sizeof( unsigned long long ) ) );
-	if( efn != nullptr ){
-		std::vector<int16_t>	t16;
-		std::vector<int32_t>	tlkey;
-		rma::efn_tables16( efn, t16, tlkey );
-		HIPCHK( hipMalloc( &sc->d_t16, t16.size() * sizeof( int16_t ) ) );
-		HIPCHK( hipMemcpy( sc->d_t16, t16.data(), t16.size() * sizeof( int16_t ), hipMemcpyHostToDevice ) );
-		HIPCHK( hipMalloc( &sc->d_tlkey, tlkey.size() * sizeof( int32_t ) ) );
-		HIPCHK( hipMemcpy( sc->d_tlkey, tlkey.data(), tlkey.size() * sizeof( int32_t ), hipMemcpyHostToDevice ) );
-		HIPCHK( hipMalloc( &sc->d_loginc, RMA_EFN_LOGINC * sizeof( int32_t ) ) );
-		HIPCHK( hipMemcpy( sc->d_loginc, efn->loginc, RMA_EFN_LOGINC * sizeof( int32_t ), hipMemcpyHostToDevice ) );
-		sc->have_efn = true;
-	}
+	HIPCHK( sc->d_counters.exact( RMK_N_COUNTERS * sizeof( unsigned long long ) ) );
+	if( efn != nullptr && rma::efn_tables_to_device( sc, efn, err, errlen ) )
+		return 1;
 	hipDeviceProp_t	prop;
 	HIPCHK( hipGetDeviceProperties( &prop, device ) );
 	sc->grid_blocks = prop.multiProcessorCount * 8;
 	// (the general instances run workgroups of one wave, four times as many, on tiles a quarter the size)
 	sc->spill_blocks = sc->grid_blocks * rma::wgs_per_wave( sc->dprog );
-	sc->spill_cap = sc->opt.spill >= 0 ? sc->opt.spill : SPILL_ITEMS / rma::wgs_per_wave( sc->dprog );	// (tests: 0 = overflow searched in place)
-	HIPCHK( hipMalloc( &sc->d_spill, std::max<size_t>( size_t( sc->spill_blocks ) * sc->spill_cap, 1 ) * sizeof( unsigned ) ) );
-	sc->plan = rma::plan_program( *prog, sc->dprog, sc->prog_bytes, sc->spill_cap, sc->opt );
+	const int	spill = sc->opt.spill >= 0 ? sc->opt.spill : SPILL_ITEMS / rma::wgs_per_wave( sc->dprog );	// (tests: 0 = overflow searched in place)
+	HIPCHK( sc->d_spill.exact( std::max<size_t>( size_t( sc->spill_blocks ) * spill, 1 ) * sizeof( unsigned ) ) );
+	sc->plan = rma::plan_program( *prog, sc->dprog, sc->prog_bytes, sc->spill_cap(), sc->opt );
 	// room for the candidates of a few hundred Mbase at the densities of the reference's descriptors
 	// (63 per Mbase for trna.descr); a scan that finds more is repeated into a buffer of the right
 	// size (count-then-emit, rma_scan_end)
-	sc->hit_cap = 1 << 17;
-	HIPCHK( hipMalloc( &sc->d_hits, size_t( sc->hit_cap ) * sc->dprog.hit_stride * sizeof( int32_t ) ) );
-	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_ctr ), RMK_C_COPIED * sizeof( unsigned long long ), hipHostMallocDefault ) );
+	HIPCHK( sc->d_hits.exact( ( size_t( 1 ) << 17 ) * sc->dprog.hit_stride * sizeof( int32_t ) ) );
+	HIPCHK( sc->h_ctr.exact( RMK_C_COPIED * sizeof( unsigned long long ) ) );
 	// page-locked room for the records of a usual batch (16 K of them) now, not in the first scan
-	sc->h_raw_cap = size_t( 16384 ) * sc->dprog.hit_stride;
-	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_raw ), sc->h_raw_cap * sizeof( int32_t ), hipHostMallocDefault ) );
-	if( sc->dsort.reserve( sc->hit_cap, sc->dprog.hit_stride ) != hipSuccess )
+	HIPCHK( sc->h_raw.exact( size_t( 16384 ) * sc->dprog.hit_stride * sizeof( int32_t ) ) );
+	if( sc->dsort.reserve( sc->hit_cap(), sc->dprog.hit_stride ) != hipSuccess )
 		( void )hipGetLastError();	// (no room for the ordering's buffers: rma_scan_end orders on the host)
-	guard.p = nullptr;
-	*out = sc;
+	*out = guard.release();
+	return 0;
+}
+
+// efn()'s tables as the kernels read them.  Tables loaded again replace the ones that are there, in place; have_efn
+// says that all three are complete.
+int rma::efn_tables_to_device( rma_scanner *sc, const rma_efndata_t *efn, char *err, size_t errlen )
+{
+	std::vector<int16_t>	t16;
+	std::vector<int32_t>	tlkey;
+	rma::efn_tables16( efn, t16, tlkey );
+	const struct { rma::DevMem *d; const void *h; size_t bytes; }	tables[ 3 ] = {
+		{ &sc->d_t16, t16.data(), t16.size() * sizeof( int16_t ) },
+		{ &sc->d_tlkey, tlkey.data(), tlkey.size() * sizeof( int32_t ) },
+		{ &sc->d_loginc, efn->loginc, RMA_EFN_LOGINC * sizeof( int32_t ) } };
+	sc->have_efn = false;
+	for( const auto &t : tables ){
+		if( t.d->bytes() < t.bytes )
+			HIPCHK( t.d->exact( t.bytes ) );
+		HIPCHK( hipMemcpy( t.d->as<void>(), t.h, t.bytes, hipMemcpyHostToDevice ) );
+	}
+	sc->have_efn = true;
 	return 0;
 }
 
@@ -286,9 +298,13 @@ extern "C" int rma_scanner_set_option( rma_scanner_t *sc, const char *name, int 
 extern "C" int rma_scanner_set_efn2data( rma_scanner_t *sc, const rma_efn2data_t *efn2, char *err, size_t errlen )
 {
 	HIPCHK( hipSetDevice( sc->device ) );
-	if( sc->d_efn2 == nullptr )
-		HIPCHK( hipMalloc( &sc->d_efn2, sizeof( rma_efn2data_t ) ) );
-	HIPCHK( hipMemcpy( sc->d_efn2, efn2, sizeof( rma_efn2data_t ), hipMemcpyHostToDevice ) );
+	rma::DevMem	fresh;		// (the scanner has tables once they are complete)
+	rma::DevMem	&d = sc->d_efn2 ? sc->d_efn2 : fresh;
+	if( !d )
+		HIPCHK( d.exact( sizeof( rma_efn2data_t ) ) );
+	HIPCHK( hipMemcpy( d.as<void>(), efn2, sizeof( rma_efn2data_t ), hipMemcpyHostToDevice ) );
+	if( fresh )
+		sc->d_efn2 = std::move( fresh );
 	return 0;
 }
 
@@ -296,39 +312,17 @@ extern "C" void rma_scanner_destroy( rma_scanner_t *sc )
 {
 	if( sc == nullptr )
 		return;
-	if( sc->d_prog == nullptr && sc->stream == nullptr ){	// (refused before anything was set up on a device)
-		delete sc;
-		return;
+	if( sc->stream.get() != nullptr ){	// (else: refused before anything was set up on a device)
+		( void )hipSetDevice( sc->device );
+		if( sc->fly.db != nullptr ){		// (a scan begun and never ended)
+			const int32_t	*h = nullptr;
+			int64_t	n = 0;
+			char	e[ 256 ];
+			( void )rma_scan_end( sc, &h, &n, e, sizeof( e ) );
+		}
+		( void )hipStreamSynchronize( sc->stream.get() );
+		rma::hitpost_free( sc->post );		// (waits for its scratch stream first)
 	}
-	( void )hipSetDevice( sc->device );
-	if( sc->fly.db != nullptr ){		// (a scan begun and never ended)
-		const int32_t	*h = nullptr;
-		int64_t	n = 0;
-		char	e[ 256 ];
-		( void )rma_scan_end( sc, &h, &n, e, sizeof( e ) );
-	}
-	if( sc->stream )
-		( void )hipStreamSynchronize( sc->stream );
-	( void )hipFree( sc->d_prog );
-	( void )hipFree( sc->d_efn2 );
-	if( sc->h_raw != nullptr )
-		( void )hipHostFree( sc->h_raw );
-	if( sc->h_ctr != nullptr )
-		( void )hipHostFree( sc->h_ctr );
-	sc->dsort.release();
-	( void )hipFree( sc->d_t16 );
-	( void )hipFree( sc->d_tlkey );
-	( void )hipFree( sc->d_loginc );
-	( void )hipFree( sc->d_hits );
-	( void )hipFree( sc->d_counters );
-	( void )hipFree( sc->d_spill );
-	( void )hipFree( sc->d_pool );
-	rma::hitpost_free( sc->post );
-	for( int i = 0; i < 5; i++ )
-		if( sc->ev[ i ] )
-			( void )hipEventDestroy( sc->ev[ i ] );
-	if( sc->stream )
-		( void )hipStreamDestroy( sc->stream );
 	delete sc;
 }
 
@@ -352,12 +346,12 @@ static int db_alloc( int device, const int64_t *base_off, const int32_t *slen, i
 	DevCtx	*ctx = dev_ctx( device, err, errlen );
 	if( ctx == nullptr )
 		return 1;
-	rma_db	*db = new rma_db;
+	// every early return below frees what has been allocated so far
+	DbPtr	guard( new rma_db, rma_db_destroy );
+	rma_db	*db = guard.get();
 	db->device = device;
 	db->ctx = ctx;
 	db->n_seq = n;
-	// every early return below frees what has been allocated so far
-	struct DbGuard { rma_db *p; ~DbGuard(){ if( p ) rma_db_destroy( p ); } }	guard{ db };
 	db->h_slen.assign( slen, slen + n );
 	db->h_base_off.assign( base_off, base_off + n );
 	if( pos_lo != nullptr ){
@@ -395,8 +389,8 @@ static int db_alloc( int device, const int64_t *base_off, const int32_t *slen, i
 	const size_t	total = carve( nullptr ) + extra;
 	HIPCHK( ctx->take( total, &db->blk ) );
 	carve( db->blk.p );
-	HIPCHK( hipEventCreateWithFlags( &db->ready, hipEventDisableTiming ) );
-	hipStream_t	up = ctx->upload;
+	HIPCHK( db->ready.create( hipEventDisableTiming ) );
+	hipStream_t	up = ctx->upload.get();
 	if( n > 0 ){
 		// (the small tables come from the host copies the database keeps: they outlive the call)
 		HIPCHK( hipMemcpyAsync( db->d_base_off, db->h_base_off.data(), size_t( n ) * 8, hipMemcpyHostToDevice, up ) );
@@ -406,8 +400,7 @@ static int db_alloc( int device, const int64_t *base_off, const int32_t *slen, i
 			HIPCHK( hipMemcpyAsync( db->d_pos_hi, db->h_pos_hi.data(), size_t( n ) * 4, hipMemcpyHostToDevice, up ) );
 		}
 	}
-	guard.p = nullptr;
-	*out = db;
+	*out = guard.release();
 	return 0;
 }
 
@@ -415,13 +408,12 @@ static int db_alloc( int device, const int64_t *base_off, const int32_t *slen, i
 // On failure db is destroyed.
 static int db_ready( rma_db_t **out, bool wait, char *err, size_t errlen )
 {
-	struct DbGuard { rma_db *p; ~DbGuard(){ if( p ) rma_db_destroy( p ); } }	guard{ *out };
+	DbPtr	guard( *out, rma_db_destroy );
 	*out = nullptr;
-	HIPCHK( hipEventRecord( guard.p->ready, guard.p->ctx->upload ) );
+	HIPCHK( hipEventRecord( guard->ready.get(), guard->ctx->upload.get() ) );
 	if( wait )
-		HIPCHK( hipEventSynchronize( guard.p->ready ) );
-	*out = guard.p;
-	guard.p = nullptr;
+		HIPCHK( hipEventSynchronize( guard->ready.get() ) );
+	*out = guard.release();
 	return 0;
 }
 
@@ -440,10 +432,10 @@ static int db_upload( int device, const std::vector<Piece> &pieces, const int64_
 		n_mask += p.mask_words;
 	if( db_alloc( device, base_off, slen, n, pos_lo, pos_hi, n_mask, 0, out, nullptr, err, errlen ) )
 		return 1;
-	rma_db	*db = *out;
-	struct DbGuard { rma_db *p; ~DbGuard(){ if( p ) rma_db_destroy( p ); } }	guard{ db };
+	DbPtr	guard( *out, rma_db_destroy );
+	rma_db	*db = guard.get();
 	*out = nullptr;
-	hipStream_t	up = db->ctx->upload;
+	hipStream_t	up = db->ctx->upload.get();
 	size_t	at = 0;		// mask words uploaded so far
 	for( const Piece &p : pieces ){
 		if( p.mask_words == 0 )
@@ -452,8 +444,7 @@ static int db_upload( int device, const std::vector<Piece> &pieces, const int64_
 		HIPCHK( hipMemcpyAsync( db->d_amask + at, p.amask, p.mask_words * 4, hipMemcpyHostToDevice, up ) );
 		at += p.mask_words;
 	}
-	guard.p = nullptr;
-	*out = db;
+	*out = guard.release();
 	return db_ready( out, wait, err, errlen );
 }
 
@@ -465,7 +456,7 @@ static const Layout *layout_for( rma_scanner_t *sc, const rma_db_t *cdb, char *e
 // a database made for a scanner gets that scanner's tiling with it, behind its words on the upload stream
 static int tile_at_creation( rma_scanner_t *sc, rma_db_t **out, char *err, size_t errlen )
 {
-	if( sc == nullptr || layout_for( sc, *out, err, errlen, ( *out )->ctx->upload ) != nullptr )
+	if( sc == nullptr || layout_for( sc, *out, err, errlen, ( *out )->ctx->upload.get() ) != nullptr )
 		return 0;
 	rma_db_destroy( *out );
 	*out = nullptr;
@@ -610,12 +601,14 @@ int rma::check_device_bytes( const void *p, int device, int64_t lo, int64_t hi, 
 // the caller's stream has reached this point before anything later on `on` runs
 int rma::stream_after( hipStream_t on, hipStream_t caller, char *err, size_t errlen )
 {
-	hipEvent_t	ev = nullptr;
-	HIPCHK( hipEventCreateWithFlags( &ev, hipEventDisableTiming ) );
-	hipError_t	e = hipEventRecord( ev, caller );
-	if( e == hipSuccess )
-		e = hipStreamWaitEvent( on, ev, 0 );
-	( void )hipEventDestroy( ev );		// (the wait holds what it needs)
+	hipError_t	e;
+	{
+		rma::Event	ev;		// (destroyed once the wait is queued: the wait holds what it needs)
+		HIPCHK( ev.create( hipEventDisableTiming ) );
+		e = hipEventRecord( ev.get(), caller );
+		if( e == hipSuccess )
+			e = hipStreamWaitEvent( on, ev.get(), 0 );
+	}
 	if( e != hipSuccess ){
 		snprintf( err, errlen, "ordering behind the caller's stream: %s", hipGetErrorString( e ) );
 		return 1;
@@ -702,12 +695,12 @@ static int db_from_device_text( rma_scanner_t *sc, const void *text, int64_t tex
 	char	*extra = nullptr;
 	if( db_alloc( device, base_off.data(), slen, n, pos_lo, pos_hi, n_mask, align256( size_t( std::max( n, 1 ) ) * 8 ) + 256, out, &extra, err, errlen ) )
 		return 1;
-	rma_db	*db = *out;
-	struct DbGuard { rma_db *p; ~DbGuard(){ if( p ) rma_db_destroy( p ); } }	guard{ db };
+	DbPtr	guard( *out, rma_db_destroy );
+	rma_db	*db = guard.get();
 	*out = nullptr;
 	int64_t	*d_start = reinterpret_cast<int64_t *>( extra );
 	uint8_t	*d_table = reinterpret_cast<uint8_t *>( extra + align256( size_t( std::max( n, 1 ) ) * 8 ) );
-	hipStream_t	up = db->ctx->upload;
+	hipStream_t	up = db->ctx->upload.get();
 	// (host copies the database keeps until it is destroyed: the copies read them after this returns)
 	db->h_text_start.assign( start, start + n );
 	db->h_table = tab;
@@ -729,8 +722,7 @@ static int db_from_device_text( rma_scanner_t *sc, const void *text, int64_t tex
 		HIPCHK( hipMemcpyAsync( d_table, table, 256, hipMemcpyDeviceToDevice, up ) );
 	HIPCHK( rma::pack_text( static_cast<const uint8_t *>( text ), d_start, db->d_base_off, db->d_slen, n, int64_t( n_mask ), d_table,
 		db->d_codes, db->d_amask, up ) );
-	guard.p = nullptr;
-	*out = db;
+	*out = guard.release();
 	if( db_ready( out, false, err, errlen ) )
 		return 1;
 	if( tile_at_creation( sc, out, err, errlen ) )
@@ -762,7 +754,7 @@ extern "C" int rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, 
 	DevCtx	*ctx = dev_ctx( device, err, errlen );
 	if( ctx == nullptr )
 		return 1;
-	hipStream_t	up = ctx->upload;
+	hipStream_t	up = ctx->upload.get();
 	const std::vector<uint8_t>	tab( rma::letter_codes(), rma::letter_codes() + 256 );
 	// device blocks of this call: back to the cache on every way out, once the upload stream is done with them; the
 	// clean text goes to the database instead
@@ -773,7 +765,7 @@ extern "C" int rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, 
 		~Blocks()
 		{
 			if( !idle )
-				( void )hipStreamSynchronize( ctx->upload );
+				( void )hipStreamSynchronize( ctx->upload.get() );
 			ctx->give( work ); ctx->give( entries ); ctx->give( headers ); ctx->give( clean );
 		}
 	}	b{ ctx, {}, {}, {}, {} };
@@ -913,7 +905,7 @@ extern "C" int rma_db_read_packed( const rma_db_t *db, uint32_t *codes, uint32_t
 	char *err, size_t errlen )
 {
 	HIPCHK( hipSetDevice( db->device ) );
-	HIPCHK( hipEventSynchronize( db->ready ) );
+	HIPCHK( hipEventSynchronize( db->ready.get() ) );
 	const size_t	n_mask = size_t( db->padded_bases / 32 ), n = size_t( db->n_seq );
 	if( codes != nullptr && n_mask > 0 )
 		HIPCHK( hipMemcpy( codes, db->d_codes, n_mask * 8, hipMemcpyDeviceToHost ) );
@@ -931,7 +923,7 @@ extern "C" void rma_letter_codes( uint8_t codes[ 256 ] ) { memcpy( codes, rma::l
 extern "C" int rma_db_wait( rma_db_t *db, char *err, size_t errlen )
 {
 	HIPCHK( hipSetDevice( db->device ) );
-	HIPCHK( hipEventSynchronize( db->ready ) );
+	HIPCHK( hipEventSynchronize( db->ready.get() ) );
 	return 0;
 }
 
@@ -951,16 +943,14 @@ extern "C" void rma_db_destroy( rma_db_t *db )
 		busy = db->busy;
 	}
 	for( rma_scanner *sc : busy )
-		( void )hipStreamSynchronize( sc->stream );
-	if( db->ready != nullptr ){
-		( void )hipEventSynchronize( db->ready );	// (an upload still on its way into the block)
-		( void )hipEventDestroy( db->ready );
-	}
+		( void )hipStreamSynchronize( sc->stream.get() );
+	if( db->ready.get() != nullptr )
+		( void )hipEventSynchronize( db->ready.get() );	// (an upload still on its way into the block)
 	// (a tiling's two copies may still be on their way -- made by rma_db_attach() on a scanner's stream, or behind the
 	// words on the upload stream after db->ready was recorded: they read the layout's host vectors and write its block)
 	for( auto &l : db->layouts )
-		if( l->ready != nullptr )
-			( void )hipEventSynchronize( l->ready );
+		if( l->ready.get() != nullptr )
+			( void )hipEventSynchronize( l->ready.get() );
 	if( db->ctx != nullptr ){
 		db->ctx->give( db->blk );
 		db->ctx->give( db->text_blk );
@@ -1005,7 +995,7 @@ extern "C" int rma_pack_pin( rma_pack_t *pack, char *err, size_t errlen )
 static const Layout *layout_for( rma_scanner_t *sc, const rma_db_t *cdb, char *err, size_t errlen, hipStream_t on )
 {
 	if( on == nullptr )
-		on = sc->stream;
+		on = sc->stream.get();
 	rma_db	*db = const_cast<rma_db *>( cdb );
 	const rma::DbShape	shape{ db->n_seq, db->sum_slen, db->padded_bases, !db->h_pos_lo.empty(), db->ascending };
 	const rma::LayoutKey	key = rma::choose_layout( sc->plan, sc->opt, shape, sc->grid_blocks / 8 );
@@ -1035,9 +1025,9 @@ static const Layout *layout_for( rma_scanner_t *sc, const rma_db_t *cdb, char *e
 		e = hipMemcpyAsync( l->d_tile_meta, tile_meta.data(), tile_meta.size() * 4, hipMemcpyHostToDevice, on );
 	}
 	if( e == hipSuccess )
-		e = hipEventCreateWithFlags( &l->ready, hipEventDisableTiming );
+		e = l->ready.create( hipEventDisableTiming );
 	if( e == hipSuccess )
-		e = hipEventRecord( l->ready, on );
+		e = hipEventRecord( l->ready.get(), on );
 	if( e != hipSuccess ){
 		db->ctx->give( l->blk );
 		snprintf( err, errlen, "tiling of the database: %s", hipGetErrorString( e ) );
@@ -1078,24 +1068,19 @@ static DbView view_of( const rma_db *db, const Layout *l )
 }
 
 // ---------------------------------------------------------------- scans
-// Work areas that grow when a scan asks for more; what was there is freed first.
+// Work areas that grow when a scan asks for more; what was there is freed first, and a failure leaves none.
 // The spill area: room for `need` items a workgroup.
 static int grow_spill( rma_scanner_t *sc, unsigned long long need, char *err, size_t errlen )
 {
-	( void )hipFree( sc->d_spill );
-	sc->d_spill = nullptr;
-	sc->spill_cap = int( need ) + 1024;
-	HIPCHK( hipMalloc( &sc->d_spill, size_t( sc->spill_blocks ) * sc->spill_cap * sizeof( unsigned ) ) );
+	HIPCHK( sc->d_spill.exact( size_t( sc->spill_blocks ) * ( size_t( need ) + 1024 ) * sizeof( unsigned ) ) );
 	return 0;
 }
 
 // The pooled instance's d_pool: the drain kernel's list of `list` items, then `cap` items of every workgroup's pool.
 static int grow_pool( rma_scanner_t *sc, int list, int cap, char *err, size_t errlen )
 {
-	( void )hipFree( sc->d_pool );
-	sc->d_pool = nullptr;
 	sc->pool_cap = sc->glist_cap = 0;
-	HIPCHK( hipMalloc( &sc->d_pool, ( size_t( list ) + size_t( sc->grid_blocks ) * cap ) * RMK_POOL_WORDS * sizeof( unsigned ) ) );
+	HIPCHK( sc->d_pool.exact( ( size_t( list ) + size_t( sc->grid_blocks ) * cap ) * RMK_POOL_WORDS * sizeof( unsigned ) ) );
 	sc->pool_cap = cap;
 	sc->glist_cap = list;
 	return 0;
@@ -1104,44 +1089,38 @@ static int grow_pool( rma_scanner_t *sc, int list, int cap, char *err, size_t er
 // The pinned staging buffer of the records (the copy back is a single DMA): twice `words` when they do not fit.
 static int grow_h_raw( rma_scanner_t *sc, size_t words, char *err, size_t errlen )
 {
-	if( words <= sc->h_raw_cap )
-		return 0;
-	if( sc->h_raw != nullptr )
-		( void )hipHostFree( sc->h_raw );
-	sc->h_raw = nullptr;
-	sc->h_raw_cap = 0;
-	HIPCHK( hipHostMalloc( reinterpret_cast<void **>( &sc->h_raw ), words * 2 * sizeof( int32_t ), hipHostMallocDefault ) );
-	sc->h_raw_cap = words * 2;
+	if( words > sc->h_raw_cap() )
+		HIPCHK( sc->h_raw.exact( words * 2 * sizeof( int32_t ) ) );
 	return 0;
 }
 
 static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
 {
 	const rma_scanner::InFlight	&f = sc->fly;
-	HIPCHK( hipMemsetAsync( sc->d_counters, 0, RMK_N_COUNTERS * sizeof( unsigned long long ), sc->stream ) );
+	HIPCHK( hipMemsetAsync( sc->counters(), 0, RMK_N_COUNTERS * sizeof( unsigned long long ), sc->stream.get() ) );
 	rmk_search_args	a;
-	a.d_prog = sc->d_prog;
+	a.d_prog = sc->d_prog.as<rmd_program_t>();
 	a.prog_bytes = sc->prog_bytes;
 	a.qcap = f.lay->qcap;
 	a.db = view_of( f.db, f.lay );
 	const bool	listed = f.plan.listed, drain = listed && sc->glist_cap > 0;
-	a.hb = HitBuf{ sc->d_hits, sc->d_counters + RMK_C_COUNT, sc->d_counters + RMK_C_TICKET, sc->hit_cap, sc->d_spill, sc->spill_cap, sc->d_pool, sc->pool_cap,
+	a.hb = HitBuf{ sc->hits(), sc->counters() + RMK_C_COUNT, sc->counters() + RMK_C_TICKET, sc->hit_cap(), sc->d_spill.as<unsigned>(), sc->spill_cap(), sc->d_pool.as<unsigned>(), sc->pool_cap,
 		sc->opt.pool_min, sc->opt.pool_refill, listed ? sc->glist_cap : 0 };
 	a.tile_bytes = f.plan.tile_bytes;
 	a.dbg = sc->opt.dbg | ( sc->whole_items ? RMK_DBG_WHOLE_ITEMS : 0 );
-	HIPCHK( hipEventRecord( sc->ev[ 0 ], sc->stream ) );
-	HIPCHK( rmk_launch_search( f.plan.inst, f.plan.grid, f.plan.lds, sc->stream, a ) );
+	HIPCHK( hipEventRecord( sc->ev[ 0 ].get(), sc->stream.get() ) );
+	HIPCHK( rmk_launch_search( f.plan.inst, f.plan.grid, f.plan.lds, sc->stream.get(), a ) );
 	sc->drained = drain;
 	sc->searched = true;
 	sc->efn_ran = false;
 	if( drain ){	// the items the search kernel left in the list: walked by a kernel of their own
-		HIPCHK( hipEventRecord( sc->ev[ 4 ], sc->stream ) );
+		HIPCHK( hipEventRecord( sc->ev[ 4 ].get(), sc->stream.get() ) );
 		a.tile_bytes = f.plan.drain_nib;
-		HIPCHK( rmk_launch_lean_drain( f.plan.drain_grid, f.plan.drain_lds, sc->stream, a ) );
+		HIPCHK( rmk_launch_lean_drain( f.plan.drain_grid, f.plan.drain_lds, sc->stream.get(), a ) );
 	}
-	HIPCHK( hipEventRecord( sc->ev[ 1 ], sc->stream ) );
+	HIPCHK( hipEventRecord( sc->ev[ 1 ].get(), sc->stream.get() ) );
 	// RMK_C_COUNT, RMK_C_QUEUE_NEED / RMK_C_PIECE_OVERFLOW, RMK_C_LIST_RESERVED, RMK_C_FLUSH_QUEUE_NEED: one copy, one wait
-	HIPCHK( hipMemcpyAsync( sc->h_ctr, sc->d_counters, RMK_C_COPIED * sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream ) );
+	HIPCHK( hipMemcpyAsync( sc->ctr(), sc->counters(), RMK_C_COPIED * sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream.get() ) );
 	return 0;
 }
 
@@ -1150,7 +1129,7 @@ static void debug_report( rma_scanner_t *sc )
 {
 	const rma_scanner::InFlight	&f = sc->fly;
 	unsigned long long	ctr[ RMK_N_COUNTERS ] = { 0 };
-	( void )hipMemcpy( ctr, sc->d_counters, sizeof( ctr ), hipMemcpyDeviceToHost );
+	( void )hipMemcpy( ctr, sc->counters(), sizeof( ctr ), hipMemcpyDeviceToHost );
 	rma::debug_report( ctr, rma::ScanShape{ sc->opt.dbg, f.lay->tile_t, f.plan.grouped ? f.lay->group : 1, f.lay->qcap, f.plan.grid, f.plan.lds,
 		( long long )f.lay->n_tiles, f.plan.lean, sc->drained }, sc->dprog );
 }
@@ -1168,7 +1147,7 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 		snprintf( err, errlen, "the database lives on device %d, the scanner on device %d", db->device, sc->device );
 		return 1;
 	}
-	if( sc->need_efn2 && sc->d_efn2 == nullptr ){
+	if( sc->need_efn2 && !sc->d_efn2 ){
 		snprintf( err, errlen, "the program has efn2() call sites but rma_scanner_set_efn2data() was not called" );
 		return 1;
 	}
@@ -1207,16 +1186,16 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 			int( std::min<long long>( std::max<long long>( db->sum_slen / 32, 1 << 18 ), 1 << 24 ) );
 		if( lay->flush )		// (what an earlier scan reserved beyond the list's end: search_finish)
 			want = std::max( want, sc->glist_need );
-		const int	cap = sc->opt.pool_min + lay->qcap + sc->spill_cap;
+		const int	cap = sc->opt.pool_min + lay->qcap + sc->spill_cap();
 		if( cap > sc->pool_cap || want > sc->glist_cap || ( want == 0 && sc->glist_cap != 0 ) || ( sc->opt.glist > 0 && want != sc->glist_cap && !lay->flush ) ){
-			HIPCHK( hipStreamSynchronize( sc->stream ) );
+			HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
 			if( grow_pool( sc, want, std::max( cap, sc->pool_cap ), err, errlen ) )
 				return 1;
 		}
 	}
 	// the database's upload and the tiling's, on the device's upload stream, come first
-	HIPCHK( hipStreamWaitEvent( sc->stream, db->ready, 0 ) );
-	HIPCHK( hipStreamWaitEvent( sc->stream, lay->ready, 0 ) );
+	HIPCHK( hipStreamWaitEvent( sc->stream.get(), db->ready.get(), 0 ) );
+	HIPCHK( hipStreamWaitEvent( sc->stream.get(), lay->ready.get(), 0 ) );
 	if( launch_search( sc, err, errlen ) )
 		return 1;
 	unfly.armed = false;
@@ -1234,14 +1213,14 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 	const rmd_program_t	&dp = sc->dprog;
 	unsigned long long	count = 0;
 	for( int attempt = 0; ; attempt++ ){
-		HIPCHK( hipStreamSynchronize( sc->stream ) );
-		count = sc->h_ctr[ RMK_C_COUNT ];
+		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		count = sc->ctr()[ RMK_C_COUNT ];
 		if( sc->opt.dbg )
 			debug_report( sc );
 		bool	again = false;
 		if( !f.plan.lean ){
 			// the general instance does not search queue overflow in place: a larger spill area, and again
-			const unsigned long long	need = sc->h_ctr[ RMK_C_QUEUE_NEED ];
+			const unsigned long long	need = sc->ctr()[ RMK_C_QUEUE_NEED ];
 			if( need > 0 ){
 				if( attempt == 3 ){
 					snprintf( err, errlen, "work queue overflow after regrow (%llu items in a tile)", need );
@@ -1255,7 +1234,7 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 		if( f.plan.walks_nothing ){
 			// the instance that walks nothing reports what it had no room for -- a tile's items beyond queue and spill area, the
 			// list's items beyond its end -- and the scan is repeated with room for them
-			const unsigned long long	q_need = sc->h_ctr[ RMK_C_FLUSH_QUEUE_NEED ], l_need = sc->h_ctr[ RMK_C_LIST_RESERVED ];
+			const unsigned long long	q_need = sc->ctr()[ RMK_C_FLUSH_QUEUE_NEED ], l_need = sc->ctr()[ RMK_C_LIST_RESERVED ];
 			if( ( q_need > 0 || l_need > ( unsigned long long )sc->glist_cap ) && attempt == 3 ){
 				snprintf( err, errlen, "work queue or item list overflow after regrow (%llu items in a tile, %llu in the list)", q_need, l_need );
 				return 1;
@@ -1276,22 +1255,19 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 				again = true;
 			}
 		}
-		if( f.plan.lean && sc->h_ctr[ RMK_C_PIECE_OVERFLOW ] != 0 && !sc->whole_items ){
+		if( f.plan.lean && sc->ctr()[ RMK_C_PIECE_OVERFLOW ] != 0 && !sc->whole_items ){
 			// a piece of an item found more candidates than the order words of the pieces leave room for
 			// (PIECE_ORDER_BITS): once more, and from now on, with whole items
 			sc->whole_items = true;
 			again = true;
 		}
-		if( !again && int64_t( count ) > sc->hit_cap ){
+		if( !again && int64_t( count ) > sc->hit_cap() ){
 			if( attempt == 3 ){
 				snprintf( err, errlen, "hit buffer overflow after regrow (%llu candidates)", count );
 				return 1;
 			}
 			// count-then-emit: the first pass told us how many records there are
-			( void )hipFree( sc->d_hits );
-			sc->d_hits = nullptr;
-			sc->hit_cap = int64_t( count ) + 1024;
-			HIPCHK( hipMalloc( &sc->d_hits, size_t( sc->hit_cap ) * dp.hit_stride * sizeof( int32_t ) ) );
+			HIPCHK( sc->d_hits.exact( ( size_t( count ) + 1024 ) * dp.hit_stride * sizeof( int32_t ) ) );
 			again = true;
 		}
 		if( !again )
@@ -1300,7 +1276,7 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 			return 1;
 	}
 	if( search_ms )
-		HIPCHK( hipEventElapsedTime( search_ms, sc->ev[ 0 ], sc->ev[ 1 ] ) );
+		HIPCHK( hipEventElapsedTime( search_ms, sc->ev[ 0 ].get(), sc->ev[ 1 ].get() ) );
 	*n_hits = int64_t( count );
 	return 0;
 }
@@ -1308,19 +1284,19 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 static int launch_efn( rma_scanner_t *sc, int64_t count, char *err, size_t errlen )
 {
 	const rmd_program_t	&dp = sc->dprog;
-	if( !( ( sc->have_efn || sc->d_efn2 != nullptr ) && dp.n_efn > 0 && count > 0 ) )
+	if( !( ( sc->have_efn || sc->d_efn2 ) && dp.n_efn > 0 && count > 0 ) )
 		return 0;
 	// one workgroup per CU at most (its LDS), each striding over the candidates
 	const int64_t	blocks = std::min<int64_t>( ( count + EFN_BLOCK - 1 ) / EFN_BLOCK, sc->grid_blocks / 8 );
-	rmk_efn_args	a{ sc->d_prog, view_of( sc->fly.db, sc->fly.lay ), sc->d_hits, ( long long )count,
-		sc->have_efn ? sc->d_t16 : nullptr, sc->d_tlkey, sc->d_loginc, sc->d_efn2 };
+	rmk_efn_args	a{ sc->d_prog.as<rmd_program_t>(), view_of( sc->fly.db, sc->fly.lay ), sc->hits(), ( long long )count,
+		sc->have_efn ? sc->d_t16.as<int16_t>() : nullptr, sc->d_tlkey.as<int32_t>(), sc->d_loginc.as<int32_t>(), sc->efn2() };
 	sc->efn_ran = true;
-	HIPCHK( hipEventRecord( sc->ev[ 2 ], sc->stream ) );
+	HIPCHK( hipEventRecord( sc->ev[ 2 ].get(), sc->stream.get() ) );
 	if( sc->fly.plan.efn_light )
-		HIPCHK( rmk_launch_efn_light( int( std::min<int64_t>( ( count + 63 ) / 64, sc->grid_blocks * 2 ) ), sc->stream, a ) );
+		HIPCHK( rmk_launch_efn_light( int( std::min<int64_t>( ( count + 63 ) / 64, sc->grid_blocks * 2 ) ), sc->stream.get(), a ) );
 	else
-	HIPCHK( sc->dprog.efn_big ? rmk_launch_efn_big( int( blocks ), sc->stream, a ) : rmk_launch_efn( int( blocks ), sc->stream, a ) );
-	HIPCHK( hipEventRecord( sc->ev[ 3 ], sc->stream ) );
+	HIPCHK( sc->dprog.efn_big ? rmk_launch_efn_big( int( blocks ), sc->stream.get(), a ) : rmk_launch_efn( int( blocks ), sc->stream.get(), a ) );
+	HIPCHK( hipEventRecord( sc->ev[ 3 ].get(), sc->stream.get() ) );
 	return 0;
 }
 
@@ -1352,12 +1328,12 @@ extern "C" int rma_scan_device( rma_scanner_t *sc, const rma_db_t *db, int64_t *
 	if( search_finish( sc, &n, search_ms, err, errlen ) )
 		return 1;
 	*n_hits = n;
-	const bool	has_efn = ( sc->have_efn || sc->d_efn2 != nullptr ) && sc->dprog.n_efn > 0 && n > 0;
+	const bool	has_efn = ( sc->have_efn || sc->d_efn2 ) && sc->dprog.n_efn > 0 && n > 0;
 	if( launch_efn( sc, n, err, errlen ) )
 		return 1;
-	HIPCHK( hipStreamSynchronize( sc->stream ) );
+	HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
 	if( efn_ms && has_efn )
-		HIPCHK( hipEventElapsedTime( efn_ms, sc->ev[ 2 ], sc->ev[ 3 ] ) );
+		HIPCHK( hipEventElapsedTime( efn_ms, sc->ev[ 2 ].get(), sc->ev[ 3 ].get() ) );
 	return 0;
 }
 
@@ -1367,16 +1343,16 @@ extern "C" int rma_scanner_last_kernel_ms( rma_scanner_t *sc, float ms[ 3 ], cha
 {
 	HIPCHK( hipSetDevice( sc->device ) );
 	ms[ 0 ] = ms[ 1 ] = ms[ 2 ] = 0;
-	HIPCHK( hipStreamSynchronize( sc->stream ) );
+	HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
 	if( !sc->searched )
 		return 0;		// (nothing was launched yet)
 	if( sc->drained ){
-		HIPCHK( hipEventElapsedTime( &ms[ 0 ], sc->ev[ 0 ], sc->ev[ 4 ] ) );
-		HIPCHK( hipEventElapsedTime( &ms[ 1 ], sc->ev[ 4 ], sc->ev[ 1 ] ) );
+		HIPCHK( hipEventElapsedTime( &ms[ 0 ], sc->ev[ 0 ].get(), sc->ev[ 4 ].get() ) );
+		HIPCHK( hipEventElapsedTime( &ms[ 1 ], sc->ev[ 4 ].get(), sc->ev[ 1 ].get() ) );
 	}else
-		HIPCHK( hipEventElapsedTime( &ms[ 0 ], sc->ev[ 0 ], sc->ev[ 1 ] ) );
+		HIPCHK( hipEventElapsedTime( &ms[ 0 ], sc->ev[ 0 ].get(), sc->ev[ 1 ].get() ) );
 	if( sc->efn_ran )
-		HIPCHK( hipEventElapsedTime( &ms[ 2 ], sc->ev[ 2 ], sc->ev[ 3 ] ) );
+		HIPCHK( hipEventElapsedTime( &ms[ 2 ], sc->ev[ 2 ].get(), sc->ev[ 3 ].get() ) );
 	return 0;
 }
 
@@ -1414,7 +1390,7 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 	if( launch_efn( sc, n, err, errlen ) )
 		return 1;
 	if( timing ){
-		HIPCHK( hipStreamSynchronize( sc->stream ) );
+		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
 		lap( "energies" );
 	}
 	const rma_db	*db = sc->fly.db;
@@ -1427,19 +1403,19 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 	// Header words that do not fit the 64-bit key (or host_sort): the host's sort_hits().
 	bool	on_device = false;
 	if( !sc->opt.host_sort && n >= 2 ){
-		if( sc->dsort.reserve( sc->hit_cap, stride ) == hipSuccess &&
-			sc->dsort.run( sc->d_hits, n, rma::bits_of( unsigned( db->n_seq > 0 ? db->n_seq - 1 : 0 ) ), rma::bits_of( unsigned( db->max_slen ) ),
-				rma::bits_of( unsigned( sc->dprog.w_winsize ) ), sc->stream ) == hipSuccess ){
+		if( sc->dsort.reserve( sc->hit_cap(), stride ) == hipSuccess &&
+			sc->dsort.run( sc->hits(), n, rma::bits_of( unsigned( db->n_seq > 0 ? db->n_seq - 1 : 0 ) ), rma::bits_of( unsigned( db->max_slen ) ),
+				rma::bits_of( unsigned( sc->dprog.w_winsize ) ), sc->stream.get() ) == hipSuccess ){
 			int	flag = 1;
 			if( timing ){
-				HIPCHK( hipStreamSynchronize( sc->stream ) );
+				HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
 				lap( "sorted" );
 			}
 			if( copy_back )
-				HIPCHK( hipMemcpyAsync( sc->h_raw, sc->dsort.d_out, words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream ) );
-			HIPCHK( hipMemcpyAsync( sc->h_ctr, sc->dsort.d_flag, sizeof( int ), hipMemcpyDeviceToHost, sc->stream ) );
-			HIPCHK( hipStreamSynchronize( sc->stream ) );
-			memcpy( &flag, sc->h_ctr, sizeof( flag ) );
+				HIPCHK( hipMemcpyAsync( sc->raw(), sc->dsort.d_out(), words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream.get() ) );
+			HIPCHK( hipMemcpyAsync( sc->ctr(), sc->dsort.d_flag(), sizeof( int ), hipMemcpyDeviceToHost, sc->stream.get() ) );
+			HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+			memcpy( &flag, sc->ctr(), sizeof( flag ) );
 			on_device = flag == 0;
 			if( !on_device && sc->dsort.w_ord < 31 )
 				sc->dsort.w_ord = 31;	// (order words above 255: room for them from now on, if the other fields leave it)
@@ -1448,40 +1424,40 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 	}
 	if( on_device ){
 		lap( "ordered" );
-		sc->d_last = sc->dsort.d_out;
+		sc->d_last = sc->dsort.d_out();
 		sc->n_last = n;
 		sc->last_state = 1;
 		if( hits )
-			*hits = copy_back ? sc->h_raw : nullptr;
+			*hits = copy_back ? sc->raw() : nullptr;
 		return 0;
 	}
 	if( n == 1 && !sc->opt.host_sort ){
 		// (a single record is in order; its order word -- the kernels leave the number of the walk's choices
 		// there, or a count within a piece of an item -- is 0 as the sorts would make it)
-		HIPCHK( hipMemsetAsync( sc->d_hits + 4, 0, sizeof( int32_t ), sc->stream ) );
+		HIPCHK( hipMemsetAsync( sc->hits() + 4, 0, sizeof( int32_t ), sc->stream.get() ) );
 		if( copy_back )
-			HIPCHK( hipMemcpyAsync( sc->h_raw, sc->d_hits, words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream ) );
-		HIPCHK( hipStreamSynchronize( sc->stream ) );
-		sc->d_last = sc->d_hits;
+			HIPCHK( hipMemcpyAsync( sc->raw(), sc->hits(), words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream.get() ) );
+		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		sc->d_last = sc->hits();
 		sc->n_last = 1;
 		sc->last_state = 1;
 		if( hits )
-			*hits = copy_back ? sc->h_raw : nullptr;
+			*hits = copy_back ? sc->raw() : nullptr;
 		return 0;
 	}
 	if( grow_h_raw( sc, words, err, errlen ) )		// (not asked to copy back, but the host has to order)
 		return 1;
-	HIPCHK( hipMemcpyAsync( sc->h_raw, sc->d_hits, words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream ) );
-	HIPCHK( hipStreamSynchronize( sc->stream ) );
+	HIPCHK( hipMemcpyAsync( sc->raw(), sc->hits(), words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream.get() ) );
+	HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
 	lap( "copy back" );
 	sc->h_sorted.resize( words );
-	rma::sort_hits( sc->h_raw, n, stride, sc->h_sorted.data(), sc->keys, sc->keys_tmp );
+	rma::sort_hits( sc->raw(), n, stride, sc->h_sorted.data(), sc->keys, sc->keys_tmp );
 	lap( "ordering" );
 	if( !copy_back ){
 		// the ordered records back where a device-side consumer finds them
-		HIPCHK( hipMemcpyAsync( sc->d_hits, sc->h_sorted.data(), words * sizeof( int32_t ), hipMemcpyHostToDevice, sc->stream ) );
-		HIPCHK( hipStreamSynchronize( sc->stream ) );
-		sc->d_last = sc->d_hits;
+		HIPCHK( hipMemcpyAsync( sc->hits(), sc->h_sorted.data(), words * sizeof( int32_t ), hipMemcpyHostToDevice, sc->stream.get() ) );
+		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		sc->d_last = sc->hits();
 		sc->n_last = n;
 		sc->last_state = 1;
 	}
@@ -1538,10 +1514,10 @@ extern "C" int rma_scan_records_to_device( rma_scanner_t *sc, int32_t *dst, int6
 	if( rma::check_device_bytes( dst, sc->device, 0, words * 4, "the destination", err, errlen ) )
 		return 1;
 	hipStream_t	caller = static_cast<hipStream_t>( stream );
-	if( rma::stream_after( sc->stream, caller, err, errlen ) )
+	if( rma::stream_after( sc->stream.get(), caller, err, errlen ) )
 		return 1;
-	HIPCHK( hipMemcpyAsync( dst, sc->d_last, size_t( words ) * 4, hipMemcpyDeviceToDevice, sc->stream ) );
-	return rma::stream_after( caller, sc->stream, err, errlen );
+	HIPCHK( hipMemcpyAsync( dst, sc->d_last, size_t( words ) * 4, hipMemcpyDeviceToDevice, sc->stream.get() ) );
+	return rma::stream_after( caller, sc->stream.get(), err, errlen );
 }
 
 // One scan of eight start positions, so that what the runtime sets up on first use (code objects of
@@ -1573,20 +1549,21 @@ extern "C" int rma_scanner_warmup( rma_scanner_t *sc, char *err, size_t errlen )
 		// records -- its code object, and the scratch memory its interval stack makes the runtime set
 		// aside at a kernel's first launch (9 ms in the first batch, measured)
 		( void )rmk_preload_efn();
-		rmk_efn_args	a{ sc->d_prog, DbView{}, sc->d_hits, 0ll, sc->have_efn ? sc->d_t16 : nullptr, sc->d_tlkey, sc->d_loginc, sc->d_efn2 };
-		( void )rmk_launch_efn( 1, sc->stream, a );
-		( void )hipStreamSynchronize( sc->stream );
+		rmk_efn_args	a{ sc->d_prog.as<rmd_program_t>(), DbView{}, sc->hits(), 0ll, sc->have_efn ? sc->d_t16.as<int16_t>() : nullptr, sc->d_tlkey.as<int32_t>(),
+			sc->d_loginc.as<int32_t>(), sc->efn2() };
+		( void )rmk_launch_efn( 1, sc->stream.get(), a );
+		( void )hipStreamSynchronize( sc->stream.get() );
 		( void )hipGetLastError();
 	}
 	if( rc == 0 && sc->dsort.cap >= 4096 ){
 		// ... and one pass of the ordering over a cleared hit buffer
-		( void )hipMemsetAsync( sc->d_hits, 0, size_t( 4096 ) * sc->dprog.hit_stride * sizeof( int32_t ), sc->stream );
-		( void )sc->dsort.run( sc->d_hits, 4096, 10, 20, 8, sc->stream );
+		( void )hipMemsetAsync( sc->hits(), 0, size_t( 4096 ) * sc->dprog.hit_stride * sizeof( int32_t ), sc->stream.get() );
+		( void )sc->dsort.run( sc->hits(), 4096, 10, 20, 8, sc->stream.get() );
 		// ... and the way back of the records, as a scan ends: the first copy of this size from the device
 		// sets up the engine that makes it
-		if( sc->h_raw_cap >= size_t( 4096 ) * sc->dprog.hit_stride )
-			( void )hipMemcpyAsync( sc->h_raw, sc->dsort.d_out, size_t( 4096 ) * sc->dprog.hit_stride * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream );
-		( void )hipStreamSynchronize( sc->stream );
+		if( sc->h_raw_cap() >= size_t( 4096 ) * sc->dprog.hit_stride )
+			( void )hipMemcpyAsync( sc->raw(), sc->dsort.d_out(), size_t( 4096 ) * sc->dprog.hit_stride * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream.get() );
+		( void )hipStreamSynchronize( sc->stream.get() );
 		( void )hipGetLastError();
 	}
 	sc->opt = keep;

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include <vector>
+#include "rm_hip_own.h"
 #include "rm_launch_plan.h"
 #include "rm_hitsort.h"
 #include "rm_hitsort_dev.h"
@@ -41,7 +42,7 @@ struct Block {			// device memory of a device's block cache (DevCtx)
 struct DevCtx;			// rm_scanner.cpp: the upload stream and the block cache of one GPU
 struct Layout;			// rm_scanner.cpp: the tiling of a database for one launch shape
 struct HitPost;			// rm_hitpost.cpp: what its calls keep on the device between them, made on first use
-void	hitpost_free( HitPost *p );	// (null: nothing)
+void	hitpost_free( HitPost *p );	// (null: nothing; the scanner's device is current)
 
 // rm_scanner.cpp.  p is device memory of `device` and bytes [lo, hi) from it lie inside its allocation; the caller's
 // stream has reached this point before anything later on `on` runs; db is a database rma_db_create_device() or
@@ -49,9 +50,18 @@ void	hitpost_free( HitPost *p );	// (null: nothing)
 int	check_device_bytes( const void *p, int device, int64_t lo, int64_t hi, const char *what, char *err, size_t errlen );
 int	stream_after( hipStream_t on, hipStream_t caller, char *err, size_t errlen );
 bool	is_device_db( const rma_db *db );
+// efn()'s tables on the scanner's device (current), in the buffers that are there when they are large enough
+int	efn_tables_to_device( rma_scanner *sc, const rma_efndata_t *efn, char *err, size_t errlen );
 
 }	// namespace rma
 
+// Who frees what, and when.  Device memory, page-locked memory, streams and events are members of the types of
+// rm_hip_own.h and go with their holder, in reverse order of declaration; no holder keeps a list of them.  What the
+// owners cannot know is the holder's to do first: a destroy function (rma_scanner_destroy, rma_db_destroy,
+// rma::hitpost_free, rma::hitwin_scratch_free, rma_comm_destroy) makes the holder's device current, ends what is in
+// flight and waits for every stream and event whose work may touch the holder's memory -- and only then deletes.
+// A set-up of several pieces (a first use, a regrow) is built in locals and moved into the holder when it is complete:
+// a failure leaves the holder as it was, and a capacity is never kept apart from the pointer it describes.
 struct rma_scanner {
 	rma_program_t	prog;
 	rmd_program_t	dprog;
@@ -59,35 +69,41 @@ struct rma_scanner {
 	rma::ProgramPlan	plan;		// tile sizes of the descriptor (rma_scanner_create)
 	int	device = 0;
 	rma::DevCtx	*ctx = nullptr;
-	hipStream_t	stream = nullptr;
-	hipEvent_t	ev[ 5 ] = { nullptr, nullptr, nullptr, nullptr, nullptr };	// search kernel's start / end, efn kernel's, [4]: the search kernel's end when a drain kernel follows
+	rma::Stream	stream;
+	rma::Event	ev[ 5 ];		// search kernel's start / end, efn kernel's, [4]: the search kernel's end when a drain kernel follows
 	bool	drained = false;		// the last launch had a drain kernel
 	bool	searched = false, efn_ran = false;	// a search kernel was launched at all; the last scan had an efn kernel
-	rma_efn2data_t	*d_efn2 = nullptr;	// efn2() tables, global memory
+	rma::DevMem	d_efn2;			// efn2() tables (rma_efn2data_t), global memory
 	bool	need_efn2 = false;
-	rmd_program_t	*d_prog = nullptr;	// compact image, prog_bytes long
+	rma::DevMem	d_prog;			// compact image (rmd_program_t), prog_bytes long
 	int	prog_bytes = 0;
-	int16_t	*d_t16 = nullptr;
-	int32_t	*d_tlkey = nullptr, *d_loginc = nullptr;
+	rma::DevMem	d_t16, d_tlkey, d_loginc;	// efn() tables: int16_t, int32_t, int32_t
 	bool	have_efn = false;
-	int32_t	*d_hits = nullptr;
-	int64_t	hit_cap = 0;
-	unsigned long long	*d_counters = nullptr;	// [RMK_N_COUNTERS], rm_diag.h: RMK_C_*
-	unsigned	*d_spill = nullptr;		// [grid_blocks][spill_cap] queue overflow of every workgroup
-	int	spill_cap = 0;
+	rma::DevMem	d_hits;			// [hit_cap()][hit_stride]
+	rma::DevMem	d_counters;		// unsigned long long [RMK_N_COUNTERS], rm_diag.h: RMK_C_*
+	rma::DevMem	d_spill;		// unsigned [spill_blocks][spill_cap()] queue overflow of every workgroup
 	bool	whole_items = false;		// ... which takes the items whole, not in pieces (see search_finish)
 	int	glist_cap = 0;			// pooled instance: items of the list the drain kernel walks (the head of d_pool)
 	int	glist_need = 0;			// ... and what a scan of the instance that walks nothing asked for (search_finish)
-	unsigned	*d_pool = nullptr;		// [grid_blocks][pool_cap][3] pooled instance: items waiting for pass B
+	rma::DevMem	d_pool;			// unsigned [glist_cap + grid_blocks * pool_cap][3] pooled instance: items waiting for pass B
 	int	pool_cap = 0;
-	int32_t	*h_raw = nullptr;		// pinned
-	size_t	h_raw_cap = 0;
+	rma::PinMem	h_raw;			// int32_t [h_raw_cap()]
 	std::vector<int32_t>	h_sorted;
 	std::vector<rma::HitKey>	keys, keys_tmp;
 	rma::DevHitSort	dsort;		// ordering on the device (rm_hitsort_dev.h)
-	unsigned long long	*h_ctr = nullptr;	// pinned: the first RMK_C_COPIED counters as a launch leaves them
+	rma::PinMem	h_ctr;			// unsigned long long: the first RMK_C_COPIED counters as a launch leaves them
 	int	grid_blocks = 0;		// most workgroups of a launch of a lean instance (eight of four waves per CU)
 	int	spill_blocks = 0;		// workgroups d_spill has areas for
+	// the capacities of d_hits (records), d_spill (items a workgroup) and h_raw (words) are what the buffers hold
+	int64_t	hit_cap() const { return int64_t( d_hits.bytes() / ( size_t( dprog.hit_stride ) * sizeof( int32_t ) ) ); }
+	int	spill_cap() const { return spill_blocks > 0 ? int( d_spill.bytes() / ( size_t( spill_blocks ) * sizeof( unsigned ) ) ) : 0; }
+	size_t	h_raw_cap() const { return h_raw.bytes() / sizeof( int32_t ); }
+	// ... and the buffers by the type of what they hold
+	int32_t	*hits() const { return d_hits.as<int32_t>(); }
+	int32_t	*raw() const { return h_raw.as<int32_t>(); }
+	unsigned long long	*counters() const { return d_counters.as<unsigned long long>(); }
+	unsigned long long	*ctr() const { return h_ctr.as<unsigned long long>(); }
+	const rma_efn2data_t	*efn2() const { return d_efn2.as<rma_efn2data_t>(); }	// (null: none were given)
 	// the scan between rma_scan_begin() and rma_scan_end()
 	struct InFlight {
 		const rma_db	*db = nullptr;
@@ -127,7 +143,7 @@ struct rma_db {
 	int64_t	total_bases = 0, sum_slen = 0;
 	int64_t	padded_bases = 0;	// bases the packed arrays hold, padding between the entries included
 	bool	ascending = true;	// the entries lie in the packed arrays in their order, none overlapping
-	hipEvent_t	ready = nullptr;	// the upload is complete (recorded on the upload stream)
+	rma::Event	ready;			// the upload is complete (recorded on the upload stream)
 	std::mutex	mu;			// layouts, busy
 	std::vector<std::unique_ptr<rma::Layout>>	layouts;	// (made and destroyed in rm_scanner.cpp alone)
 	std::vector<rma_scanner *>	busy;		// scanners with a scan of this database in flight
