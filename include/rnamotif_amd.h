@@ -472,6 +472,49 @@ int	rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db
 		const uint8_t *letters /* 256 or NULL */, uint8_t *d_accept /* n */, double *d_score /* n or NULL */,
 		int8_t *d_kind /* n or NULL: 0 none, 1 int, 2 float */, void *stream, char *err, size_t errlen );
 
+/* ---- loose seq= expressions on the device: which records are rnamotif's candidates (csrc/rm_seqcheck.h has the rule,
+ * one function shared by the host and the kernel, and the image it runs with its limits).  The records of a descriptor
+ * with rma_program_loose() > 0 are a superset of the reference's candidates: the scan tests a necessary condition for a
+ * seq= with a \( \) group and a back reference, with \< or \>, or -- iupac = 0 -- with a letter that is not acgt.
+ * rma_seqcheck_hits() applies the expressions themselves to the element text of each record, as rma_replay_*() does on
+ * the host before it counts a candidate (step(), or mm_step() where the element has a mismatch limit).
+ * rma_seqcheck_open() flattens the loose expressions of d into an image; a descriptor that is not loose opens with zero
+ * expressions, so that one pipeline serves every descriptor.  Refused with words: more than 20 loose elements, more
+ * than 255 ops in one expression, an image that leaves no room in 64 KB of LDS for the stack of one wave. */
+typedef struct rma_seqcheck	rma_seqcheck_t;
+int	rma_seqcheck_open( const rma_descr_t *d, rma_seqcheck_t **out, char *err, size_t errlen );
+void	rma_seqcheck_close( rma_seqcheck_t *sq );
+/* What an image and its kernel take (profiles/seq_check.py): info[ 0 ] expressions, [ 1 ] ops of all of them, [ 2 ] frames
+ * of the matcher's stack (the most repeating ops of one expression), [ 3 ] bytes of the image, [ 4 ] waves of a
+ * workgroup, [ 5 ] bytes of dynamic LDS of a workgroup; from the runtime, -1 each where no device answers: [ 6 ] bytes of
+ * private memory a lane of rma_seqcheck_kernel has, [ 7 ] its registers. */
+void	rma_seqcheck_info( const rma_seqcheck_t *sq, int32_t info[ 8 ] );
+/* rma_seqcheck_hits(): d_keep[ h ] = 1 where record h passes every loose expression -- it is a candidate of the
+ * reference's -- and 0 where it is dropped at the first that fails, in the order of the elements.  d_fixed (or NULL):
+ * the records again, n_hits * stride words, with word RMA_HIT_HDR + 4 * e + 3 of a kept record replaced by mm_step()'s
+ * mismatch count for every loose element e with a mismatch limit, as the replay fixes it before the score section
+ * reads it; a dropped record's row is the input row.  d_hits[ d_keep ] of the fixed rows are what rma_score_hits of a
+ * program opened by rma_score_open_checked() takes.  d_fixed may not overlap d_hits.
+ * Arguments as rma_score_hits takes them: any rows of a scan's records in any order; db made by
+ * rma_db_create_device*() (its text is read in place, through `letters` -- 256 bytes, none 0, or NULL); the pointers
+ * checked against their allocations on the scanner's device; the program of sq must be the scanner's, byte for byte.
+ * Every record is checked on the device by rma_replay_device()'s rule before anything it points to is read; a bad
+ * record fails the call, naming its index.  budget: the ops one record may visit, 0 for 2^20 -- backtracking over an
+ * expression like .*\(..\).*\1 grows fast with the element's length, and no expression may hold the device; a record
+ * that needs more fails the call: err names the lowest such record, its element and the budget.  An element's text ends
+ * where the element ends: nothing behind it is read.
+ * After a failed call the outputs hold what they held before: results go to scratch of the scanner's and are copied
+ * once the check has passed.  The work runs on a stream of the scanner's own, behind what is queued on `stream` (the
+ * caller's hipStream_t, NULL = the default stream) and ahead of what is queued there next; the call waits once.
+ * n_hits == 0 does nothing. */
+int	rma_seqcheck_hits( rma_scanner_t *sc, const rma_seqcheck_t *sq, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *letters /* 256 or NULL */, int32_t budget /* 0: 2^20 */,
+		uint8_t *d_keep /* n_hits */, int32_t *d_fixed /* n_hits * stride, or NULL */, void *stream, char *err, size_t errlen );
+/* rma_score_open() without its refusal of a loose descriptor; every other refusal and every limit stays.  The caller
+ * promises that the records it will pass to rma_score_hits() passed rma_seqcheck_hits() (d_keep 1) and are its fixed
+ * rows: on any other record of a loose descriptor MAIN judges what the reference never scored. */
+int	rma_score_open_checked( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen );
+
 #ifdef __cplusplus
 }
 #endif

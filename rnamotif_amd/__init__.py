@@ -159,6 +159,13 @@ def lib() -> C.CDLL:
     L.rma_score_info.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rma_score_info.restype = None
     L.rma_score_hits.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_score_open_checked.argtypes = [vp, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.rma_seqcheck_open.argtypes = [vp, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.rma_seqcheck_close.argtypes = [vp]
+    L.rma_seqcheck_close.restype = None
+    L.rma_seqcheck_info.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rma_seqcheck_info.restype = None
+    L.rma_seqcheck_hits.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, C.c_int32, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_program_loose.argtypes = [vp]
     L.rma_program_loose.restype = C.c_int
     _lib = L
@@ -465,20 +472,24 @@ class ScoreProgram:
     (rma_score_open; Scanner.score() takes it).  Raises RnamotifError with the reason where the program cannot be
     judged record by record on the device: HOLD / RELEASE or a variable carried from one hit to the next, sprintf(),
     bits(), mismatches( string, pattern ), =~ / !~, a read of NAME, a loose descriptor, an image beyond the limits of
-    csrc/rm_score_image.h.  The descriptor itself is not touched: the image is made from a private copy."""
+    csrc/rm_score_image.h.  The descriptor itself is not touched: the image is made from a private copy.
+    checked=True (rma_score_open_checked) opens a loose descriptor too: the caller promises to score only
+    r.hits[r.keep] of r = Scanner.seq_check(db, hits), the records that are rnamotif's candidates, as fixed rows."""
 
-    def __init__(self, descr: Descriptor):
+    def __init__(self, descr: Descriptor, checked: bool = False):
         h = C.c_void_p()
         err = C.create_string_buffer(_ERRLEN)
-        _check(lib().rma_score_open(descr._h, C.byref(h), err, _ERRLEN), err)
+        L = lib()
+        _check((L.rma_score_open_checked if checked else L.rma_score_open)(descr._h, C.byref(h), err, _ERRLEN), err)
         self._h = h
         self.descr = descr
+        self.checked = bool(checked)
 
     @staticmethod
-    def reason(descr: Descriptor) -> Optional[str]:
-        """Why ScoreProgram(descr) would refuse, or None where it opens."""
+    def reason(descr: Descriptor, checked: bool = False) -> Optional[str]:
+        """Why ScoreProgram(descr, checked) would refuse, or None where it opens."""
         try:
-            ScoreProgram(descr).close()
+            ScoreProgram(descr, checked).close()
         except RnamotifError as e:
             return str(e)
         return None
@@ -500,6 +511,50 @@ class ScoreProgram:
             self.close()
         except Exception:
             pass
+
+
+class SeqCheck:
+    """The seq= expressions of a descriptor that its scan tests loosely (descr.loose > 0: back references, \\< \\>,
+    letters that are not acgt with iupac = 0) as an image the GPU applies to records, one record per lane
+    (rma_seqcheck_open; Scanner.seq_check() takes it).  A descriptor that is not loose opens with no expressions.
+    Raises RnamotifError with the reason beyond the limits of csrc/rm_seqcheck.h."""
+
+    def __init__(self, descr: Descriptor):
+        h = C.c_void_p()
+        err = C.create_string_buffer(_ERRLEN)
+        _check(lib().rma_seqcheck_open(descr._h, C.byref(h), err, _ERRLEN), err)
+        self._h = h
+        self.descr = descr
+
+    @property
+    def info(self) -> dict:
+        """The image's and its kernel's sizes (rma_seqcheck_info); the last two are -1 where no GPU answers."""
+        a = (C.c_int32 * 8)()
+        lib().rma_seqcheck_info(self._h, a)
+        return dict(zip(("expressions", "ops", "frames", "image_bytes", "waves_per_workgroup", "workgroup_lds_bytes",
+                         "private_bytes", "registers"), (int(x) for x in a)))
+
+    def close(self) -> None:
+        if self._h:
+            lib().rma_seqcheck_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SeqChecked:
+    """Scanner.seq_check()'s result, tensors on the scanner's device, ready on torch's current stream.
+
+    keep  torch.bool [n]          the record passes every loose seq= expression: it is a candidate of rnamotif's
+    hits  int32 [n, hit_stride]   the records with the mismatch counts the expressions fix (None with fixed=False);
+                                  hits[keep] are the rows the score section, prune(), align() ... go on with"""
+
+    def __init__(self, keep, hits):
+        self.keep, self.hits = keep, hits
 
 
 class HitScores:
@@ -694,7 +749,7 @@ class Scanner:
     def scan_tensor(self, db: Database):
         """scan(db) with the records left on the GPU: an int32 tensor [n, hit_stride] on the scanner's device, the
         same records in the same order, ready on torch's current stream.  Candidates before the score section, a
-        superset of rnamotif's when descr.loose > 0, until Replay.device() replays them."""
+        superset of rnamotif's when descr.loose > 0, until Replay.device() replays them or seq_check() says which to keep."""
         import torch
         self.scan_begin(db)
         n = self.scan_end_on_device()
@@ -843,6 +898,39 @@ class Scanner:
             hits.record_stream(stream)
         return HitScores(*out)
 
+    def seq_check(self, db: Database, hits, check: Optional[SeqCheck] = None, letters: Optional[bytes] = None, budget: int = 0,
+                  fixed: bool = True) -> SeqChecked:
+        """The loose seq= expressions of the descriptor applied to the element text of each of these records, on the
+        GPU (rma_seqcheck_hits; the rule is csrc/rm_seqcheck.h's, what the replay does on the host): a SeqChecked, so
+        that r.hits[r.keep] -- rnamotif's candidates -- go on to score() with ScoreProgram(descr, checked=True),
+        prune(), hit_structures(), align() without a trip to the host.  For a descriptor that is not loose every
+        record is kept.  hits: int32 CUDA tensor [n, hit_stride] on the scanner's device, any rows of a scan's records
+        in any order; db: the database_from_tensor() / database_from_fasta_tensor() database they are of; check:
+        SeqCheck(descr) of this scanner's descriptor (default: one made on first use and kept by the scanner);
+        letters as Replay.device() takes them; budget: the ops one record may visit, 0 for 2^20; fixed=False: no rows,
+        only keep.  The call waits once.  A malformed record, and a record that needs more than the budget, raise
+        RnamotifError naming the lowest such record; nothing is written then."""
+        import torch
+        hits, n, dev, stream, letters = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner",
+                                                    "its records are checked by Replay.batch() or pack()", letters)
+        if check is None:
+            check = getattr(self, "_seq_check", None)
+            if check is None or not check._h:
+                check = self._seq_check = SeqCheck(self.descr)
+        if not isinstance(check, SeqCheck) or not check._h:
+            raise ValueError("check: an open SeqCheck is needed")
+        if int(budget) < 0:
+            raise ValueError(f"budget is {budget}")
+        keep = torch.empty(n, dtype=torch.bool, device=dev)
+        rows = torch.empty((n, self.descr.hit_stride), dtype=torch.int32, device=dev) if fixed else None
+        if n:
+            err = C.create_string_buffer(_ERRLEN)
+            _check(lib().rma_seqcheck_hits(self._h, check._h, db._h, hits.data_ptr(), n, letters, int(budget), keep.data_ptr(),
+                                           rows.data_ptr() if fixed else None, stream.cuda_stream, err, _ERRLEN), err)
+            # (the records are read by a kernel queued behind this stream: torch keeps their memory until it has run)
+            hits.record_stream(stream)
+        return SeqChecked(keep, rows)
+
     def load_energy_tables(self, dir: str = EFNDATA_DIR, efn: bool = True, efn2: bool = True) -> None:
         """The tables of efn() and / or efn2() from a directory onto the scanner's GPU (rma_scanner_load_energy_tables),
         for structure_energies() of a scanner whose descriptor has no such call in its score section.  No scan changes."""
@@ -972,6 +1060,9 @@ class Scanner:
         return ms[0], ms[1], ms[2]
 
     def close(self) -> None:
+        if getattr(self, "_seq_check", None) is not None:
+            self._seq_check.close()
+            self._seq_check = None
         if self._h:
             lib().rma_scanner_destroy(self._h)
             self._h = None

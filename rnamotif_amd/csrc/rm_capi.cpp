@@ -9,6 +9,7 @@
 #include "rm_hitsort.h"
 #include "rm_hitwin.h"
 #include "rm_score_image.h"
+#include "rm_seqcheck.h"
 #include <cctype>
 #include <cstddef>
 #include <cstring>
@@ -114,15 +115,15 @@ extern "C" int rma_program_loose( const rma_program_t *p )
 	return n;
 }
 
-extern "C" int rma_score_open( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen )
+static int score_open( const rma_descr_t *d, rma_score_t **out, bool checked, char *err, size_t errlen )
 {
 	if( out != nullptr )
 		*out = nullptr;
 	if( d == nullptr || out == nullptr )
-		return set_err( err, errlen, "rma_score_open: no descriptor" );
+		return set_err( err, errlen, checked ? "rma_score_open_checked: no descriptor" : "rma_score_open: no descriptor" );
 	try{
 		std::unique_ptr<rma_score>	sp( new rma_score );
-		const std::string	why = rma::score_image_make( *d->pr.descr, *d->pr.prog, &sp->img );
+		const std::string	why = rma::score_image_make( *d->pr.descr, *d->pr.prog, &sp->img, checked );
 		if( !why.empty() )
 			return set_err( err, errlen, why.c_str() );
 		*out = sp.release();
@@ -134,7 +135,37 @@ extern "C" int rma_score_open( const rma_descr_t *d, rma_score_t **out, char *er
 	}
 }
 
+extern "C" int rma_score_open( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen )
+{
+	return score_open( d, out, false, err, errlen );
+}
+
+extern "C" int rma_score_open_checked( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen )
+{
+	return score_open( d, out, true, err, errlen );
+}
+
 extern "C" void rma_score_close( rma_score_t *sp ) { delete sp; }
+
+extern "C" int rma_seqcheck_open( const rma_descr_t *d, rma_seqcheck_t **out, char *err, size_t errlen )
+{
+	if( out != nullptr )
+		*out = nullptr;
+	if( d == nullptr || out == nullptr )
+		return set_err( err, errlen, "rma_seqcheck_open: no descriptor" );
+	try{
+		std::unique_ptr<rma_seqcheck>	sq( new rma_seqcheck );
+		const std::string	why = rma::seqcheck_image_make( *d->pr.descr, *d->pr.prog, &sq->img );
+		if( !why.empty() )
+			return set_err( err, errlen, why.c_str() );
+		*out = sq.release();
+		return 0;
+	}catch( std::exception &e ){
+		return set_err( err, errlen, e.what() );
+	}
+}
+
+extern "C" void rma_seqcheck_close( rma_seqcheck_t *sq ) { delete sq; }
 
 extern "C" int rma_replay_open( rma_descr_t *d, const char *path, rma_replay_t **out, char *err, size_t errlen )
 {

@@ -5,7 +5,9 @@
 // structures in device memory -- and rma_scanner_load_energy_tables, which gives a scanner the tables for it.
 // Of a scan they need nothing: a scanner's program and device, a database's tables and text (rm_scanner_impl.h), and
 // scratch of their own.  Last rma_score_hits (rm_score_dev.hip): the score section's MAIN over records, the rule of
-// rm_score_core.h on an image of rm_score_image.h.  What they all do first is written once:
+// rm_score_core.h on an image of rm_score_image.h -- and, for the records of a loose descriptor ahead of it,
+// rma_seqcheck_hits (rm_seqcheck_dev.hip): the seq= expressions themselves, the rule of rm_seqcheck.h.  What they all do
+// first is written once:
 //   record_call_args    the database, the records and the device refused or accepted
 //   letters_on_device   the table the window bytes go through
 //   check_records       behind the caller's stream, the bad-record word reset, every record judged by the span kernel
@@ -25,6 +27,8 @@
 #include "rm_structenergy_dev.h"
 #include "rm_score_core.h"
 #include "rm_score_dev.h"
+#include "rm_seqcheck.h"
+#include "rm_seqcheck_dev.h"
 
 namespace {
 // records of a call go through the kernels HW_CHUNK at a time; windows come to the host (rma_hit_windows) in pieces
@@ -79,6 +83,11 @@ struct rma::HitPost {
 	DevMem	d_sc, d_sc_image;
 	PinMem	h_sc;
 	uint64_t	sc_serial = 0;
+	// rma_seqcheck_hits: two result words, a stopped record's result and a call's keep flags and fixed rows; two
+	// page-locked words and a result; the image that is on the device now (its serial; 0: none) and its bytes
+	DevMem	d_sq, d_sq_image;
+	PinMem	h_sq;
+	uint64_t	sq_serial = 0;
 };
 
 // (the scanner's device is current; the scratch stream is synchronised before anything goes)
@@ -950,4 +959,142 @@ extern "C" void rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] )
 	info[ 7 ] = priv;
 	info[ 8 ] = lds;
 	info[ 9 ] = regs;
+}
+
+// ---------------------------------------------------------------- loose seq= expressions over records on the device
+// rma_seqcheck_hits(): rma_seqcheck_kernel (rm_seqcheck_dev.hip) in chunks of HW_CHUNK records on the stream of the
+// scanner's span scratch, behind the caller's stream, as rma_score_hits runs its kernel: the kernel checks each record
+// by the span rule before it applies the expressions to it; results go to scratch of the scanner's; one wait learns the
+// least index of a bad and of a stopped record; then the results are copied to the caller's tensors, ahead of what the
+// caller queues next.  For a stopped record the kernel runs once more, on that record alone, to learn its element.
+namespace {
+constexpr size_t	SQ_DETAIL_AT = 64, SQ_RESULTS_AT = 256;
+}
+
+extern "C" int rma_seqcheck_hits( rma_scanner_t *sc, const rma_seqcheck_t *sq, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, int32_t budget, uint8_t *d_keep, int32_t *d_fixed, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_seqcheck_hits";
+	if( sc == nullptr || sq == nullptr || db == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : sq == nullptr ? "seq= check" : "database" );
+		return 1;
+	}
+	// (both are memcpy copies of a descriptor's program: padding bytes included, equal where the descriptor's are)
+	if( memcmp( sq->img.prog.get(), &sc->prog, sizeof( rma_program_t ) ) != 0 ){
+		snprintf( err, errlen, "%s: the seq= check was opened for another descriptor than the scanner's (their programs differ): nothing written", who );
+		return 1;
+	}
+	if( budget < 0 ){
+		snprintf( err, errlen, "%s: a budget of %d steps: bad arguments", who, budget );
+		return 1;
+	}
+	if( budget == 0 )
+		budget = RMQ_DEFAULT_BUDGET;
+	if( hit_structures_args( sc, db, d_hits, n_hits, who, err, errlen ) )
+		return 1;
+	if( n_hits == 0 )
+		return 0;
+	if( d_keep == nullptr ){
+		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )n_hits );
+		return 1;
+	}
+	const int	stride = rma_hit_stride( &sc->prog );
+	const int64_t	row_bytes = n_hits * stride * 4;
+	if( rma::check_device_bytes( d_keep, sc->device, 0, n_hits, "the keep flags", err, errlen ) ||
+		( d_fixed != nullptr && rma::check_device_bytes( d_fixed, sc->device, 0, row_bytes, "the fixed rows", err, errlen ) ) )
+		return 1;
+	if( d_fixed != nullptr ){
+		const char	*a = reinterpret_cast<const char *>( d_hits ), *f = reinterpret_cast<const char *>( d_fixed );
+		if( a < f + row_bytes && f < a + row_bytes ){
+			snprintf( err, errlen, "%s: the fixed rows overlap the records: nothing written", who );
+			return 1;
+		}
+	}
+	if( letters != nullptr )
+		for( int b = 0; b < 256; b++ )
+			if( letters[ b ] == 0 ){
+				snprintf( err, errlen, "%s: the letters give byte %d the letter 0, which ends the text of an element: nothing written", who, b );
+				return 1;
+			}
+	const RmqImage	*m = sq->img.image();
+	if( rma::seqcheck_waves( m->bytes, m->frames ) < 1 || m->stride != stride ){
+		snprintf( err, errlen, "%s: the image leaves no room for a wave", who );
+		return 1;
+	}
+	rma::HitPost	&p = *sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream.get(), caller = static_cast<hipStream_t>( stream );
+	const size_t	n = size_t( n_hits ), flags = ( n + 7 ) & ~size_t( 7 ), want = SQ_RESULTS_AT + flags + ( d_fixed != nullptr ? size_t( row_bytes ) : 0 );
+	if( want > p.d_sq.bytes() )		// (the copies of the call before this one may still read the block that goes)
+		HIPCHK( hipStreamSynchronize( st ) );
+	HIPCHK( p.d_sq.room( want ) );
+	if( !p.h_sq )
+		HIPCHK( p.h_sq.exact( SQ_RESULTS_AT ) );
+	if( p.sq_serial != sq->img.serial ){
+		HIPCHK( hipStreamSynchronize( st ) );
+		p.sq_serial = 0;		// (no image's until this one's bytes are in)
+		HIPCHK( p.d_sq_image.room( size_t( m->bytes ) ) );
+		HIPCHK( hipMemcpy( p.d_sq_image.as<void>(), m, size_t( m->bytes ), hipMemcpyHostToDevice ) );
+		p.sq_serial = sq->img.serial;
+	}
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	if( letters_on_device( s, db, letters, &tab, &codes, err, errlen ) ||
+		check_records( s, db, sc->prog, d_hits, n_hits, stream, false, nullptr, 0, err, errlen ) )
+		return 1;
+	char	*base = p.d_sq.as<char>();
+	unsigned long long	*d_words = reinterpret_cast<unsigned long long *>( base ), *h_words = p.h_sq.as<unsigned long long>();
+	RmqResult	*d_detail = reinterpret_cast<RmqResult *>( base + SQ_DETAIL_AT );
+	RmqResult	*h_detail = reinterpret_cast<RmqResult *>( p.h_sq.as<char>() + SQ_DETAIL_AT );
+	uint8_t	*keep = reinterpret_cast<uint8_t *>( base + SQ_RESULTS_AT );
+	int32_t	*fixed = d_fixed != nullptr ? reinterpret_cast<int32_t *>( base + SQ_RESULTS_AT + flags ) : nullptr;
+	HIPCHK( hipMemsetAsync( d_words, 0xff, 2 * sizeof( unsigned long long ), st ) );
+	auto batch = [&]( int64_t c0, int64_t cn, RmqResult *detail ){
+		return rma::SeqBatch{ p.d_sq_image.as<void>(), m->bytes, m->frames, d_hits + c0 * stride, ( long long )cn, ( long long )c0, stride,
+			rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq, db->text, tab, codes, budget,
+			keep + c0, detail == nullptr && fixed != nullptr ? fixed + c0 * stride : nullptr, d_words, d_words + 1, detail };
+	};
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
+		HIPCHK( rma::seqcheck_records( batch( c0, std::min( HW_CHUNK, n_hits - c0 ), nullptr ), st ) );
+	HIPCHK( hipMemcpyAsync( h_words, d_words, 2 * sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( h_words[ 0 ] != ~0ull )
+		return bad_record( s, db, sc->prog, d_hits, int64_t( h_words[ 0 ] ), nullptr, "written", err, errlen );
+	if( h_words[ 1 ] != ~0ull ){
+		const int64_t	h = int64_t( h_words[ 1 ] );
+		memset( h_detail, 0, sizeof( RmqResult ) );
+		HIPCHK( hipMemsetAsync( d_detail, 0, sizeof( RmqResult ), st ) );
+		HIPCHK( rma::seqcheck_records( batch( h, 1, d_detail ), st ) );
+		HIPCHK( hipMemcpyAsync( h_detail, d_detail, sizeof( RmqResult ), hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipStreamSynchronize( st ) );
+		snprintf( err, errlen, "%s: record %lld: element %d: its seq= takes more than the budget of %d steps: nothing written", who, ( long long )h,
+			h_detail->elem, budget );
+		return 1;
+	}
+	HIPCHK( hipMemcpyAsync( d_keep, keep, n, hipMemcpyDeviceToDevice, st ) );
+	if( d_fixed != nullptr )
+		HIPCHK( hipMemcpyAsync( d_fixed, fixed, size_t( row_bytes ), hipMemcpyDeviceToDevice, st ) );
+	return rma::stream_after( caller, st, err, errlen );
+}
+
+extern "C" void rma_seqcheck_info( const rma_seqcheck_t *sq, int32_t info[ 8 ] )
+{
+	if( sq == nullptr ){
+		for( int i = 0; i < 8; i++ )
+			info[ i ] = -1;
+		return;
+	}
+	const RmqImage	*m = sq->img.image();
+	const int	waves = rma::seqcheck_waves( m->bytes, m->frames );
+	info[ 0 ] = m->n_expr;
+	info[ 1 ] = m->n_ops;
+	info[ 2 ] = m->frames;
+	info[ 3 ] = m->bytes;
+	info[ 4 ] = waves;
+	info[ 5 ] = m->bytes + RMQ_LDS_TABLES + waves * rmq_wave_bytes( m->frames );
+	int	priv = -1, lds = -1, regs = -1;
+	if( rma::seqcheck_kernel_attributes( &priv, &lds, &regs ) != hipSuccess )
+		( void )hipGetLastError();
+	info[ 6 ] = priv;
+	info[ 7 ] = regs;
 }

@@ -41,6 +41,22 @@ struct ScoreBatch {
 	RmsResult	*detail;		// not null: where a stopped record leaves its result (a launch of one record)
 };
 
+#if defined( __HIPCC__ )
+// the letters Replay.device() reads: the table's (of a code: its letter), on strand 1 the complement, read downwards
+// (rma_score_kernel and rma_seqcheck_kernel of rm_seqcheck_dev.hip read bases through it)
+struct ScoreBases {
+	const uint8_t	*text;		// the entry's first byte
+	const uint8_t	*let, *cmp;	// in LDS
+	int	comp, slen;
+	__device__ unsigned char	operator()( int i ) const
+	{
+		if( unsigned( i ) >= unsigned( slen ) )
+			return 'n';
+		return comp ? cmp[ text[ slen - 1 - i ] ] : let[ text[ i ] ];
+	}
+};
+#endif
+
 // waves of a workgroup: as many of 4 as RMS_LDS_BYTES hold next to the image (0: not one)
 int	score_waves( int image_bytes, int stack, int n_vars );
 // Enqueue on s the rule over the batch's records.

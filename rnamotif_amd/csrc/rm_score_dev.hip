@@ -12,19 +12,6 @@ namespace {
 
 constexpr int	SC_MAX_WAVES = 4;
 
-// the letters Replay.device() reads: the table's (of a code: its letter), on strand 1 the complement, read downwards
-struct ScoreBases {
-	const uint8_t	*text;		// the entry's first byte
-	const uint8_t	*let, *cmp;	// in LDS
-	int	comp, slen;
-	__device__ unsigned char	operator()( int i ) const
-	{
-		if( unsigned( i ) >= unsigned( slen ) )
-			return 'n';
-		return comp ? cmp[ text[ slen - 1 - i ] ] : let[ text[ i ] ];
-	}
-};
-
 __global__ void __launch_bounds__( SC_MAX_WAVES * 64 )
 rma_score_kernel( ScoreBatch b )
 {

@@ -87,11 +87,11 @@ struct Builder {
 
 }	// namespace
 
-std::string score_image_make( const Descriptor &d, const rma_program_t &prog, ScoreImage *out )
+std::string score_image_make( const Descriptor &d, const rma_program_t &prog, ScoreImage *out, bool checked )
 {
 	static std::atomic<uint64_t>	serials{ 0 };
 	const char	*who = "the score section cannot run on the device: ";
-	for( int e = 0; e < prog.n_elems; e++ )
+	for( int e = 0; e < prog.n_elems && !checked; e++ )
 		if( prog.elems[ e ].re >= 0 && prog.regexes[ prog.elems[ e ].re ].loose )
 			return std::string( who ) + fmt( "the descriptor is loose (element %d's seq= is tested by a necessary condition only): its records are "
 				"not yet the reference's candidates", e );

@@ -94,8 +94,9 @@ struct ScoreImage {
 };
 
 // The image of d's MAIN program, made from a private copy of d compiled as ParallelReplayer compiles its workers'
-// (BEGIN run on the copy; d itself untouched).  Returns "" or, with no image made, why not.
-std::string	score_image_make( const Descriptor &d, const rma_program_t &prog, ScoreImage *out );
+// (BEGIN run on the copy; d itself untouched).  Returns "" or, with no image made, why not.  checked: a loose descriptor
+// is not refused -- the caller's records have passed rma_seqcheck_hits (rm_seqcheck.h) and are its fixed rows.
+std::string	score_image_make( const Descriptor &d, const rma_program_t &prog, ScoreImage *out, bool checked = false );
 // the host VM's words for a stop
 std::string	score_stop_text( const ScoreImage &img, const RmsResult &r );
 

@@ -1,0 +1,91 @@
+// rm_seqcheck.cpp -- see rm_seqcheck.h: the loose seq= expressions of a compiled descriptor as an image, and what is refused.
+#include "rm_host.h"
+#include "rm_regex.h"
+#include "rm_seqcheck.h"
+#include <atomic>
+#include <cstdio>
+#include <cstring>
+
+namespace rma {
+
+static_assert( int( RMQ_CHR ) == RE_CHR && int( RMQ_DOT ) == RE_DOT && int( RMQ_CCL ) == RE_CCL && int( RMQ_NCCL ) == RE_NCCL && int( RMQ_DOL ) == RE_DOL &&
+	int( RMQ_BRA ) == RE_BRA && int( RMQ_KET ) == RE_KET && int( RMQ_BACK ) == RE_BACK && int( RMQ_BRC ) == RE_BRC && int( RMQ_LET ) == RE_LET,
+	"the rule's op kinds are RE_*" );
+static_assert( int( RMQ_ONE ) == REP_ONE && int( RMQ_STAR ) == REP_STAR && int( RMQ_RANGE ) == REP_RANGE, "the rule's repeats are REP_*" );
+
+std::string seqcheck_image_make( const Descriptor &d, const rma_program_t &prog, SeqImage *out )
+{
+	static std::atomic<uint64_t>	serials{ 0 };
+	const std::string	who = "the seq= expressions cannot be applied on the device: ";
+	char	buf[ 256 ];
+	if( int( d.descr.size() ) != prog.n_elems )
+		return who + "the program is not this descriptor's";
+	RmqImage	hdr;
+	memset( &hdr, 0, sizeof( hdr ) );
+	hdr.magic = RMQ_MAGIC;
+	hdr.stride = rma_hit_stride( &prog );
+	std::vector<RmqOp>	ops;
+	for( int e = 0; e < prog.n_elems; e++ ){
+		const int	ri = prog.elems[ e ].re;
+		if( ri < 0 || !prog.regexes[ ri ].loose )
+			continue;
+		const Strel	&s = d.descr[ size_t( e ) ];
+		if( s.re == nullptr || s.seq == nullptr )
+			return who + "the program is not this descriptor's";
+		if( hdr.n_expr >= RMQ_MAX_EXPR ){
+			snprintf( buf, sizeof( buf ), "more than %d elements have a loose seq=", int( RMQ_MAX_EXPR ) );
+			return who + buf;
+		}
+		if( s.re->ops.size() > size_t( RMQ_MAX_OPS ) ){
+			snprintf( buf, sizeof( buf ), "element %d's seq= has %zu ops, the image holds %d an expression", e, s.re->ops.size(), int( RMQ_MAX_OPS ) );
+			return who + buf;
+		}
+		RmqExpr	&ex = hdr.expr[ hdr.n_expr++ ];
+		ex.elem = e;
+		ex.anchored = *s.seq == '^';
+		ex.mismatch = s.mismatch;
+		ex.first = int32_t( ops.size() );
+		ex.n_ops = int32_t( s.re->ops.size() );
+		int	repeats = 0;
+		for( const ReOp &op : s.re->ops ){
+			RmqOp	o;
+			memset( &o, 0, sizeof( o ) );
+			o.kind = op.kind;
+			o.rep = op.rep;
+			o.c = op.c;
+			o.lo = op.lo;
+			o.hi = op.hi;
+			memcpy( o.set, op.set, sizeof( o.set ) );	// (little endian: bit ch of the 128 is bit ch & 31 of word ch >> 5)
+			if( ( op.kind == RE_BRA || op.kind == RE_KET || op.kind == RE_BACK ) && op.c >= RMQ_NBRA )
+				return who + "a group number beyond 9";
+			if( op.rep != REP_ONE )
+				repeats++;
+			ops.push_back( o );
+		}
+		if( repeats > hdr.frames )
+			hdr.frames = repeats;
+	}
+	hdr.n_ops = int32_t( ops.size() );
+	const size_t	bytes = sizeof( RmqImage ) + ops.size() * sizeof( RmqOp );
+	const int	cap = bytes > size_t( RMQ_LDS_BYTES ) ? -1 : rmq_frames_cap( int( bytes ) );
+	if( cap < 0 ){
+		snprintf( buf, sizeof( buf ), "the image of %d ops (%zu bytes) leaves no room in %d bytes of LDS for a wave", hdr.n_ops, bytes, int( RMQ_LDS_BYTES ) );
+		return who + buf;
+	}
+	if( hdr.frames > cap ){
+		snprintf( buf, sizeof( buf ), "an expression has %d repeating ops, a wave has room for %d frames next to the image", hdr.frames, cap );
+		return who + buf;
+	}
+	hdr.bytes = int32_t( bytes );
+	SeqImage	&img = *out;
+	img.blob.assign( bytes / 8, 0 );
+	memcpy( img.blob.data(), &hdr, sizeof( hdr ) );
+	if( !ops.empty() )
+		memcpy( reinterpret_cast<char *>( img.blob.data() ) + sizeof( hdr ), ops.data(), ops.size() * sizeof( RmqOp ) );
+	img.prog.reset( new rma_program_t );
+	memcpy( img.prog.get(), &prog, sizeof( rma_program_t ) );
+	img.serial = ++serials;
+	return "";
+}
+
+}	// namespace rma
