@@ -636,7 +636,12 @@ int rmd_build( const rma_program_t *p, rmd_program_t *out, char *err, size_t err
 			ch.s_hi = int16_t( e0.maxlen );
 			bool	any_leaf = false;
 			int	level_of[ RMD_MAX_CHAIN ];
-			for( int s = e0.inner_s; s >= 0 && ch.n < RMD_MAX_CHAIN; s = out->elems[ p->searches[ s ] ].next_s ){
+			bool	whole = false;		// the chain holds every group of the interior
+			for( int s = e0.inner_s; ch.n < RMD_MAX_CHAIN; s = out->elems[ p->searches[ s ] ].next_s ){
+				if( s < 0 ){
+					whole = true;
+					break;
+				}
 				const rmd_elem_t	&g = out->elems[ p->searches[ s ] ];
 				if( g.maxglen == RMA_UNBOUNDED || g.maxglen >= 2000 )
 					break;		// (what lies behind a group of any length is not pinned down by the start)
@@ -672,9 +677,15 @@ int rmd_build( const rma_program_t *p, rmd_program_t *out, char *err, size_t err
 					}
 				}
 			}
-			// (drop groups behind the last stem-loop: they say nothing)
-			while( ch.n > 0 && !ch.sib[ ch.n - 1 ].leaf )
+			// (drop groups behind the last stem-loop: they say nothing to the chain; the end window counts their lengths)
+			long	aft_lo = 0, aft_hi = 0;
+			bool	aft_ss = true;		// ... which takes single strands only
+			while( ch.n > 0 && !ch.sib[ ch.n - 1 ].leaf ){
+				aft_lo += ch.sib[ ch.n - 1 ].len_lo;
+				aft_hi += ch.sib[ ch.n - 1 ].len_hi;
+				aft_ss = aft_ss && out->elems[ p->searches[ level_of[ ch.n - 1 ] ] ].type == RMA_T_SS;
 				ch.n--;
+			}
 			// the cores of the first two shapes of stem-loop are kept for the candidate test of pass A'
 			{
 				int	keys[ 2 ] = { -1, -1 };
@@ -742,6 +753,18 @@ int rmd_build( const rma_program_t *p, rmd_program_t *out, char *err, size_t err
 				ch.n = int8_t( nm - first );
 				for( int k = 0; k < ch.n; k++ )
 					ch.sib[ k ] = m[ first + k ];
+				for( int k = ch.n; k < RMD_MAX_CHAIN; k++ )
+					memset( &ch.sib[ k ], 0, sizeof( ch.sib[ k ] ) );
+				// the end window (rmd_chain_t): where the last stem-loop's core lies, seen from the end of the first element's group
+				const rmd_chain_sib_t	tl = ch.sib[ ch.n - 1 ];
+				const long	d_lo = e0.minlen + aft_lo + 2 * tl.hmin + tl.lmin - 1, d_hi = e0.maxlen + aft_hi + 2 * tl.hmin + tl.lmax + tl.tmax - 1;
+				if( whole && aft_ss && ch.n < RMD_MAX_CHAIN && tl.leaf && tl.core_slot >= 0 && d_hi - d_lo < 24 && d_hi < 1000 ){
+					rmd_chain_sib_t	&en = ch.sib[ ch.n ];
+					en.end_on = 1;
+					en.core_slot = tl.core_slot;
+					en.len_lo = int16_t( d_lo );
+					en.len_hi = int16_t( d_hi );
+				}
 			}
 		}
 	}

@@ -170,7 +170,7 @@ struct rmd_chain_sib_t {
 	int16_t	lmin, lmax;		// leaf: loop lengths
 	int16_t	len_lo, len_hi;		// total length of the group
 	int8_t	core_slot;		// leaf: which of the two kept core vectors is its own (-1: none kept)
-	int8_t	pad_;
+	int8_t	end_on;			// only in sib[ n ], one past the chain: 1 when it holds the end window (rmd_chain_t)
 };
 struct rmd_chain_t {
 	int8_t	on, n;
@@ -182,6 +182,13 @@ struct rmd_chain_t {
 	int8_t	hn_on, hn_slot;
 	int16_t	hn_tmax, hn_glo, hn_ghi;
 	int16_t	s_lo, s_hi;		// first group starts s_lo .. s_hi after the start position (the outer helix' lengths)
+	// The end window (the instance that walks nothing, rm_scan_kernel.h): when the interior's last group is a stem-loop of
+	// the chain that keeps its cores, or only single strands lie behind that, an END position e of the first element's group
+	// has the stem-loop's core at e - d for some d in a fixed range -- d = hl + p + 2 * hmin + L + t - 1, hl the outer
+	// helix' length, p the single strands behind the stem-loop, L its loop, hmin + t its helix.  The range is narrow for the descriptors this is for
+	// (trna.descr: one value) and the end positions without a core there are not queued: nine in ten of what the first-pairs
+	// test leaves.  It is kept in the entry one past the chain, which the chain's own loop never reads: sib[ n ] with
+	// end_on = 1, len_lo .. len_hi = the range of d, core_slot = the vector.  n = RMD_MAX_CHAIN: no room, no end window.
 	rmd_chain_sib_t	sib[ RMD_MAX_CHAIN ];
 };
 

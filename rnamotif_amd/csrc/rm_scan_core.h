@@ -894,6 +894,218 @@ RMD_FN bool rmd_tail_ok( const rmd_program_t *P, const rmd_elem_t &stp, const SQ
 	return false;
 }
 
+// ---------------------------------------------------------------- pass A' of the pooled lean instances: the item rule
+// (rm_scan_kernel.h; stated here once, for the kernel and for tests/hostsim/passa_check.cpp)
+//
+// Pair rows of one pair table over a tile: rows5[ b * pb_words ] has a bit per tile position (64
+// pad bits in front) whose base can be the 3' partner of 5' base b.  End positions w0 .. w0+63 of
+// a helix whose 5' strand starts at s5: bit i of the result is set when the first hl0 pairs of
+// (s5, w0+i) hold with at most lim mispairs (and, with ends5, the first pair itself holds) --
+// match_wchlx's rule for reaching length minlen, find_motif.c:1010-1033,1065-1080; positions
+// below lo are cleared.
+RMD_FN_MEMBER unsigned long long rmd_rows_win( const unsigned long long *rows5, int pb_words, const uint8_t *tile, int p_lo,
+	int hl0, int lim, bool ends5, int s5, int w0, int lo )
+{
+	unsigned long long	W;
+	if( lim == 0 ){
+		// no mispair allowed: a plain AND of the shifted rows, done as soon as no end position is left
+		// (a copy of the loop per helix length, unrolled so that the LDS reads of all its steps are issued
+		// together, measured the same: trna.descr 3.26 / 1.94 ms against 3.25 / 1.92)
+		W = ~0ull;
+		for( int h = 0; h < hl0 && W; h++ ){
+			const int	qq = w0 - h - p_lo + 64;	// bit index into the padded vector
+			W &= qq >= 0 ? rmd_bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull;
+		}
+	}else{
+		unsigned long long	c1 = 0, c2 = 0, c3 = 0, c4 = 0, first = 0;	// >= 1/2/3/4 mispairs
+		for( int h = 0; h < hl0; h++ ){
+			const int	qq = w0 - h - p_lo + 64;
+			const unsigned long long	mis = ~( qq >= 0 ? rmd_bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull );
+			if( h == 0 )
+				first = mis;
+			c4 |= c3 & mis;
+			c3 |= c2 & mis;
+			c2 |= c1 & mis;
+			c1 |= mis;
+		}
+		W = ~( lim == 1 ? c2 : lim == 2 ? c3 : c4 );
+		if( ends5 )
+			W &= ~first;
+	}
+	const int	imin = lo - w0;
+	if( imin > 0 )
+		W = imin >= 64 ? 0 : W & ( ~0ull << imin );
+	return W;
+}
+
+// The tail test of rmd_lean_step() from the pre-filter's bit vectors.  pb[c][q] says "the base
+// at q pairs with 5' base c"; when the pair table is symmetric it also says "the base at q,
+// as the 5' partner, pairs with 3' base c".  For a tail helix that allows no mispair and must
+// have both ends paired, "some admissible 5' end s starts it against the 3' end b" is then an
+// AND over its first minlen pairs of windows of those rows -- a few dozen instructions
+// instead of one first-pairs test per admissible s.  false: undecided, *res is not written.
+struct TailAccel {
+	const rmd_program_t	*P;
+	const unsigned long long	*pb;
+	const uint8_t	*tile;
+	int	pb_words, p_lo, vec_bits;
+	int	usable_for;		// element index (level-0 helix) the rows were built for, or -1
+	RMD_FN_MEMBER bool	tail( const rmd_elem_t &stp, int z, int a, int b, bool *res ) const
+	{
+		if( usable_for < 0 || stp.searchno != 0 )
+			return false;
+		const rmd_elem_t	&t = P->elems[ P->searches[ stp.tail_s ] ];
+		int	s_hi = b - t.minglen + 1, s_lo = b - t.maxglen + 1;
+		if( a + stp.tail_pre_min > s_lo )
+			s_lo = a + stp.tail_pre_min;
+		if( stp.tail_pre_max >= 0 && a + stp.tail_pre_max < s_hi )
+			s_hi = a + stp.tail_pre_max;
+		const int	n = s_hi - s_lo + 1;
+		if( n <= 0 ){
+			*res = false;
+			return true;
+		}
+		if( n > 64 )
+			return false;
+		unsigned long long	m = n == 64 ? ~0ull : ( 1ull << n ) - 1;
+		for( int j = 0; j < t.minlen && m; j++ ){
+			const int	c3 = tile[ z + b - j - p_lo ];
+			const int	q = z + s_lo + j - p_lo + 64;		// bit of 5' position s_lo + j
+			if( c3 > 4 || q < 0 || q + 64 > vec_bits )
+				return false;
+			m &= rmd_bits64( pb + c3 * pb_words, q );
+		}
+		*res = m != 0;
+		return true;
+	}
+};
+
+// What pass A' knows of a tile: the pair rows of row set 0 (pb), the look-ahead chain's vectors (tv: the cores at
+// tv + ( 7 + slot ) * pb_words), the byte per base, and which of the tests apply.
+struct rmd_passa_t {
+	const rmd_program_t	*P;
+	const unsigned long long	*pb, *tv;
+	const uint8_t	*tile;
+	int	pb_words, p_lo, vec_bits;
+	bool	tail_from_rows, head_from_rows, head_next, all_ends;	// (all_ends: RMK_DBG_HEAD_ALL_ENDS)
+};
+
+// An item is a start position szero and the end of the first element's group, span bases on.  One length hl of the first
+// element: 0 -- the interior is too short for it, and for every longer one; 1 -- too long: the next length; 2 -- the tests.
+RMD_FN int rmd_passa_len( const rmd_elem_t &e0, int span, int hl )
+{
+	const int	ilen = span - 2 * hl;
+	return ilen < e0.minilen ? 0 : ilen > e0.maxilen ? 1 : 2;
+}
+
+// The first helix of the interior, 5' strand at one of a few offsets from the interior's start: can any 3' end start it
+// (rmd_rows_win: its first minlen pairs)?  *ends_left: those ends, bit j = the j-th from the lowest, when they fit a word.
+RMD_FN bool rmd_passa_head( const rmd_passa_t &A, const rmd_elem_t &e0, int szero, int span, int hl, unsigned *ends_left )
+{
+	const rmd_program_t	*const P = A.P;
+	const rmd_elem_t	&H = P->elems[ P->searches[ e0.head_s ] ];
+	const int	lim = ( H.ends & RMA_5PAIRED ) ? H.mplim : ( H.mplim > 1 ? H.mplim : 1 );
+	const int	b = szero + span - 1 - hl;		// last position of the interior
+	bool	ok = false;
+	for( int pre = e0.head_pre_min; pre <= e0.head_pre_max && !ok; pre++ ){
+		const int	s5 = szero + hl + pre;
+		const int	top = rmd_imin( s5 + H.maxglen - 1, b ), bot = s5 + H.minglen - 1;
+		if( top < bot )
+			continue;
+		const int	w0 = top - 63, q_hi = w0 - A.p_lo + 64;
+		// (undecided -- a range wider than a word, bits the vectors do not hold: kept)
+		if( top - bot >= 64 || q_hi - H.minlen < 0 || q_hi + 96 > A.vec_bits )
+			ok = true;
+		else{
+			unsigned long long	Wd = rmd_rows_win( A.pb, A.pb_words, A.tile, A.p_lo, H.minlen, lim, ( H.ends & RMA_5PAIRED ) != 0, s5, w0, bot );
+			if( !A.all_ends ){
+				// ... of which the walk takes only those that leave the groups behind the helix their room and let
+				// them reach the interior's end (rmd_lean_open, rmd_lean_step: rem_min, rem_max): bit i = end w0 + i
+				const int	e_hi = rmd_imin( top, b - H.rem_min ) - w0, e_lo = ( H.rem_max >= 0 ? rmd_imax( bot, b - H.rem_max ) : bot ) - w0;
+				if( e_hi < 63 )
+					Wd &= e_hi < 0 ? 0ull : ( 2ull << e_hi ) - 1;
+				if( e_lo > 0 )
+					Wd &= e_lo > 63 ? 0ull : ~0ull << e_lo;
+			}
+			if( Wd && A.head_next ){
+				// ... and one of those ends must have the next stem-loop's core at the right distance
+				// behind it (bit i of Wd: end w0 + i)
+				const rmd_chain_t	&C = P->chain;
+				const int	x = w0 - A.p_lo + 64, g_lo = C.hn_glo + 1, g_hi = C.hn_ghi + 1 + C.hn_tmax;
+				// (a distance that leaves the vector: undecided)
+				const bool	all = g_hi < g_lo || ( x + g_lo >= 0 && x + g_hi + 96 <= A.vec_bits );
+				if( all )
+					Wd &= rmd_or_window( A.tv + ( 7 + C.hn_slot ) * A.pb_words, x, g_lo, g_hi, A.vec_bits );
+				// (bit j of the mask: end bot + j)
+				if( all && top - bot < 32 )
+					*ends_left = unsigned( Wd >> ( bot - w0 ) );
+			}
+			ok = Wd != 0;
+		}
+	}
+	return ok;
+}
+
+// One test of one length: 0 -- the pinned tail helix of the interior (undecided: passed), 1 -- its first helix.
+RMD_FN bool rmd_passa_test( const rmd_passa_t &A, const rmd_elem_t &e0, int szero, int span, int hl, int test, unsigned *ends_left )
+{
+	*ends_left = ~0u;
+	if( test == 0 ){
+		const TailAccel	ac{ A.P, A.pb, A.tile, A.pb_words, A.p_lo, A.vec_bits, 0 };
+		bool	t = true;
+		return !( A.tail_from_rows && ac.tail( e0, szero, hl, span - 1 - hl, &t ) ) || t;
+	}
+	return !A.head_from_rows || rmd_passa_head( A, e0, szero, span, hl, ends_left );
+}
+
+// The lengths' results, taken in order, make the item's: keep, and per length (the first two) the 3' ends left to the
+// interior's first helix.  Start: keep false, the masks 0 with want_masks and ~0 without.  state: rmd_passa_len(); ok: both
+// tests passed; ends_left: the head test's.  false: no further length counts (those that follow only cost time).
+RMD_FN bool rmd_passa_fold( const rmd_elem_t &e0, bool want_masks, int hl, int state, bool ok, unsigned ends_left, bool *keep, unsigned *hm0, unsigned *hm1 )
+{
+	if( hl > e0.maxlen || ( *keep && !want_masks ) || state == 0 )
+		return false;
+	if( state == 1 )
+		return true;
+	if( ok && hl - e0.minlen < 2 )
+		*( hl == e0.minlen ? hm0 : hm1 ) = want_masks ? ends_left : ~0u;
+	if( ok && hl - e0.minlen >= 2 ){
+		*hm0 = *hm1 = ~0u;		// (a third length: no room for its mask; no restriction)
+		*keep = true;
+	}
+	*keep = *keep || ok;
+	// (a length that failed its tests keeps the mask 0: the walk finds nothing there either way)
+	return true;
+}
+
+// An item on a quad of lanes, as the kernel that walks nothing runs it: lane sub takes length h0 + ( sub >> 1 ) and test
+// sub & 1 of a round, the four results are folded in order, rounds of two lengths until the fold says stop.  On the host
+// the lanes are a loop.
+RMD_FN void rmd_passa_quads( const rmd_passa_t &A, const rmd_elem_t &e0, int szero, int span, bool want_masks, bool *keep, unsigned *hm0, unsigned *hm1 )
+{
+	*keep = false;
+	*hm0 = *hm1 = want_masks ? 0u : ~0u;
+	bool	go = true;
+	for( int h0 = e0.minlen; h0 <= e0.maxlen && go; h0 += 2 ){
+		int	state[ 4 ];
+		bool	ok[ 4 ];
+		unsigned	el[ 4 ];
+		for( int sub = 0; sub < 4; sub++ ){
+			const int	hl = h0 + ( sub >> 1 );
+			state[ sub ] = 0;
+			ok[ sub ] = false;
+			el[ sub ] = ~0u;
+			if( hl <= e0.maxlen ){
+				state[ sub ] = rmd_passa_len( e0, span, hl );
+				if( state[ sub ] == 2 )
+					ok[ sub ] = rmd_passa_test( A, e0, szero, span, hl, sub & 1, &el[ sub ] );
+			}
+		}
+		go = rmd_passa_fold( e0, want_masks, h0, state[ 0 ], ok[ 0 ] && ok[ 1 ], el[ 1 ], keep, hm0, hm1 );
+		go = go && rmd_passa_fold( e0, want_masks, h0 + 1, state[ 2 ], ok[ 2 ] && ok[ 3 ], el[ 3 ], keep, hm0, hm1 );
+	}
+}
+
 RMD_FN rmd_lrec_t rmd_lean_open( const rmd_program_t *P, int level, int zero, int osd )	// rmd_enter()
 {
 	const rmd_elem_t	&stp = P->elems[ P->searches[ level ] ];

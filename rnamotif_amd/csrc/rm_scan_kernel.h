@@ -429,88 +429,7 @@ struct LdsSplit {
 	}
 };
 
-// The tail test of rmd_lean_step() from the pre-filter's bit vectors.  pb[c][q] says "the base
-// at q pairs with 5' base c"; when the pair table is symmetric it also says "the base at q,
-// as the 5' partner, pairs with 3' base c".  For a tail helix that allows no mispair and must
-// have both ends paired, "some admissible 5' end s starts it against the 3' end b" is then an
-// AND over its first minlen pairs of windows of those rows -- a few dozen instructions
-// instead of one first-pairs test per admissible s.
-struct TailAccel {
-	const rmd_program_t	*P;
-	const unsigned long long	*pb;
-	const uint8_t	*tile;
-	int	pb_words, p_lo, vec_bits;
-	int	usable_for;		// element index (level-0 helix) the rows were built for, or -1
-	__device__ inline bool	tail( const rmd_elem_t &stp, int z, int a, int b, bool *res ) const
-	{
-		if( usable_for < 0 || stp.searchno != 0 )
-			return false;
-		const rmd_elem_t	&t = P->elems[ P->searches[ stp.tail_s ] ];
-		int	s_hi = b - t.minglen + 1, s_lo = b - t.maxglen + 1;
-		if( a + stp.tail_pre_min > s_lo )
-			s_lo = a + stp.tail_pre_min;
-		if( stp.tail_pre_max >= 0 && a + stp.tail_pre_max < s_hi )
-			s_hi = a + stp.tail_pre_max;
-		const int	n = s_hi - s_lo + 1;
-		if( n <= 0 ){
-			*res = false;
-			return true;
-		}
-		if( n > 64 )
-			return false;
-		unsigned long long	m = n == 64 ? ~0ull : ( 1ull << n ) - 1;
-		for( int j = 0; j < t.minlen && m; j++ ){
-			const int	c3 = tile[ z + b - j - p_lo ];
-			const int	q = z + s_lo + j - p_lo + 64;		// bit of 5' position s_lo + j
-			if( c3 > 4 || q < 0 || q + 64 > vec_bits )
-				return false;
-			m &= rmd_bits64( pb + c3 * pb_words, q );
-		}
-		*res = m != 0;
-		return true;
-	}
-};
-
-// Pair rows of one pair table over a tile: rows5[ b * pb_words ] has a bit per tile position (64
-// pad bits in front) whose base can be the 3' partner of 5' base b.  End positions w0 .. w0+63 of
-// a helix whose 5' strand starts at s5: bit i of the result is set when the first hl0 pairs of
-// (s5, w0+i) hold with at most lim mispairs (and, with ends5, the first pair itself holds) --
-// match_wchlx's rule for reaching length minlen, find_motif.c:1010-1033,1065-1080; positions
-// below lo are cleared.
-__device__ inline unsigned long long rows_win( const unsigned long long *rows5, int pb_words, const uint8_t *tile, int p_lo,
-	int hl0, int lim, bool ends5, int s5, int w0, int lo )
-{
-	unsigned long long	W;
-	if( lim == 0 ){
-		// no mispair allowed: a plain AND of the shifted rows, done as soon as no end position is left
-		// (a copy of the loop per helix length, unrolled so that the LDS reads of all its steps are issued
-		// together, measured the same: trna.descr 3.26 / 1.94 ms against 3.25 / 1.92)
-		W = ~0ull;
-		for( int h = 0; h < hl0 && W; h++ ){
-			const int	qq = w0 - h - p_lo + 64;	// bit index into the padded vector
-			W &= qq >= 0 ? rmd_bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull;
-		}
-	}else{
-		unsigned long long	c1 = 0, c2 = 0, c3 = 0, c4 = 0, first = 0;	// >= 1/2/3/4 mispairs
-		for( int h = 0; h < hl0; h++ ){
-			const int	qq = w0 - h - p_lo + 64;
-			const unsigned long long	mis = ~( qq >= 0 ? rmd_bits64( rows5 + tile[ s5 + h - p_lo ] * pb_words, qq ) : 0ull );
-			if( h == 0 )
-				first = mis;
-			c4 |= c3 & mis;
-			c3 |= c2 & mis;
-			c2 |= c1 & mis;
-			c1 |= mis;
-		}
-		W = ~( lim == 1 ? c2 : lim == 2 ? c3 : c4 );
-		if( ends5 )
-			W &= ~first;
-	}
-	const int	imin = lo - w0;
-	if( imin > 0 )
-		W = imin >= 64 ? 0 : W & ( ~0ull << imin );
-	return W;
-}
+// (TailAccel, the tail test of rmd_lean_step() from the pre-filter's bit vectors, and rmd_rows_win(), the pair rows' windows: rm_scan_core.h)
 
 // rmd_gen_skip_ends()'s accelerator: the 3' ends that can start helix stp, from the pair rows of
 // its pair table (rmd_elem_t::rows names the row set; -1: none, the core tests end by end)
@@ -528,7 +447,7 @@ struct RowEnds {
 		if( q_hi + 96 > vec_bits || s5 < p_lo )		// (rmd_bits64 reads three dwords from its first bit)
 			return false;
 		const int	lim = ( stp.ends & RMA_5PAIRED ) ? stp.mplim : ( stp.mplim > 1 ? stp.mplim : 1 );
-		*mask = rows_win( rows + 5 * stp.rows * pb_words, pb_words, tile, p_lo, stp.minlen, lim,
+		*mask = rmd_rows_win( rows + 5 * stp.rows * pb_words, pb_words, tile, p_lo, stp.minlen, lim,
 			( stp.ends & RMA_5PAIRED ) != 0, s5, w0, lo );
 		return true;
 	}
@@ -1569,6 +1488,8 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 		// first two shapes of stem-loop (kept for pass A'), tv[ 9 ]: those of any other; xv[ 0 ]: the start
 		// positions that remain.
 		const bool	chain = chain_vecs && bitpar && !( dbg & RMK_DBG_NO_CHAIN );
+		// (the instance that walks nothing: the chain's end window as a vector over END positions, rmd_chain_t; none: nullptr)
+		const unsigned long long	*ev = nullptr;
 		if( chain ){
 			const rmd_chain_t	&C = P->chain;
 			const int	vec_bits = vec_words * 64;
@@ -1634,9 +1555,30 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				cur ^= 1;
 			}
 			const unsigned long long	*const g1 = tv + ( 5 + ( cur ^ 1 ) ) * pb_words;
+			// The end window: bit x of E says that the last stem-loop's core lies len_lo .. len_hi bases before x.  A group of
+			// the first element that ends at x without it has no interior; the pre-filter ANDs E onto its end positions
+			// (body()) and nine in ten of them are never queued.  E takes the group vector that is free now: no room of its
+			// own, no pass, no barrier.
+			unsigned long long	*e_dst = nullptr;
+			const unsigned long long	*e_core = nullptr;
+			int	e_hi = 0, e_n = 0;
+			if constexpr( !WALK ){
+				const rmd_chain_sib_t	&en = C.sib[ C.n < RMD_MAX_CHAIN ? C.n : 0 ];
+				if( C.n < RMD_MAX_CHAIN && en.end_on ){
+					e_dst = tv + ( 5 + cur ) * pb_words;
+					e_core = tv + ( 7 + en.core_slot ) * pb_words;
+					e_hi = en.len_hi;
+					e_n = en.len_hi - en.len_lo;
+					ev = e_dst;
+				}
+			}
 			for( int wi = tid; wi < vec_words; wi += BLOCK ){
 				const int	x = wi * 64;
 				xv[ wi ] = rmd_or_window( g1, x, C.s_lo, C.s_hi, vec_bits ) & lit_starts( x );
+				if constexpr( !WALK ){
+					if( e_dst != nullptr )
+						e_dst[ wi ] = rmd_or_window( e_core, x - e_hi, 0, e_n, vec_bits );
+				}
 			}
 			__syncthreads();
 		}
@@ -1654,7 +1596,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 			// end position top-r0-63+i passes; positions below lo are cleared
 			const bool	ends5 = ( e0.ends & RMA_5PAIRED ) != 0;
 			auto	win = [ & ]( int szero, int top, int r0, int lo ) -> unsigned long long {
-				return rows_win( pb, pb_words, tile, p_lo, hl0, lim, ends5, szero, top - r0 - 63, lo );
+				return rmd_rows_win( pb, pb_words, tile, p_lo, hl0, lim, ends5, szero, top - r0 - 63, lo );
 			};
 			int	n_wait = 0;		// pseudoknot pre-filter: start positions of this wave that wait in cbuf
 			// one start position per lane: the end positions that pass the first-pairs test are queued
@@ -1673,6 +1615,11 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 					unsigned long long	W = 0;
 					if( valid && r0 <= hi - lo ){
 						W = win( szero, hi, r0, lo );
+						if constexpr( !WALK ){
+							// ... and end positions without the last stem-loop's core at its distance before them (bit i: end hi - r0 - 63 + i)
+							if( ev != nullptr && W )
+								W &= rmd_peek( ev, ( hi - p_lo ) - r0 + 1, vec_words * 64 );
+						}
 						if( q1f && W ){
 							// ... and end positions before which no third strand can stand (bit i: end hi - r0 - 63 + i)
 							const int	bq = hi - r0 - 63 - p_lo + 64;
@@ -2069,10 +2016,58 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 				TailAccel	ac{ P, pb, tile, pb_words, p_lo, vec_words * 64, 0 };
 				// (the chain's cores are where it left them unless the pre-filter had to search in place)
 				const bool	head_next = chain_vecs && bitpar && P->chain.hn_on && !( dbg & ( RMK_DBG_NO_CHAIN | RMK_DBG_NO_HEAD_NEXT ) ) && !last && s_inplace == 0;
-				for( int c = 0; c < nq; c += BLOCK ){
-					const int	i = c + tid;
+				// The instance that walks nothing: an item on a quad of lanes (rmd_passa_quads) -- lane sub takes outer length
+				// h0 + ( sub >> 1 ) and test sub & 1, tail or head, the four results go round the quad by DPP and are folded in the
+				// lengths' order.  All four waves share a tile's handful of items, and a lane's chain of dependent LDS reads is one
+				// test long, not ( tail + head ) x lengths.  Lane sub == 0 owns the item from there on.
+				constexpr int	PER_ITEM = WALK ? 1 : 4;
+				for( int c = 0; c < nq * PER_ITEM; c += BLOCK ){
+					// (the instance that walks nothing: what a lane derives from its number is derived here, round by round, not
+					// once ahead of the tile loop and kept in registers through the pre-filter, where the kernel has none to spare)
+					int	ltid = tid;
+					if constexpr( !WALK )
+						asm volatile( "" : "+v"( ltid ) );
+					const int	i = ( c + ltid ) / PER_ITEM;
 					unsigned	item = 0, hm[ 2 ] = { ~0u, ~0u };	// (the 3' ends left to the first helix of the interior, per outer length)
 					bool	keep = false;
+					if constexpr( !WALK ){
+						if( i < nq )
+							item = i < qcap ? queue[ i ] : __hip_atomic_load( spill + ( i - qcap ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+						// (go: the item takes the tests and its lengths are not through)
+						bool	go = i < nq && ( tail_from_rows || head_from_rows ) && ( item & 0xffffu ) != 0xffffu;
+						keep = i < nq && !go;
+						int	span = 0;
+						if( go ){
+							int	hi, lo;
+							rmd_level0_range( P, z0 + int( item >> 16 ), slen, &hi, &lo );
+							span = hi - int( item & 0xffffu ) - ( z0 + int( item >> 16 ) ) + 1;
+						}
+						const bool	want_masks = head_next && e0.head_pre_min == e0.head_pre_max;
+						if( go && want_masks )
+							hm[ 0 ] = hm[ 1 ] = 0;
+						const rmd_passa_t	A{ P, pb, tv, tile, pb_words, p_lo, vec_words * 64, tail_from_rows, head_from_rows, head_next, ( dbg & RMK_DBG_HEAD_ALL_ENDS ) != 0 };
+						for( int h0 = e0.minlen; h0 <= e0.maxlen && __ballot( go ); h0 += 2 ){
+							const int	hl = h0 + ( ( ltid >> 1 ) & 1 );
+							int	res = 0;		// rmd_passa_len(), bit 2: the test passed
+							unsigned	el = ~0u;
+							if( go && hl <= e0.maxlen ){
+								res = rmd_passa_len( e0, span, hl );
+								if( res == 2 && rmd_passa_test( A, e0, z0 + int( item >> 16 ), span, hl, ltid & 1, &el ) )
+									res |= 4;
+							}
+							// (every lane of the quad gets the four results and folds them: the quad stays in step)
+#define QUAD_LANE( v_, k_ )	__builtin_amdgcn_mov_dpp( int( v_ ), ( k_ ) * 0x55, 0xf, 0xf, true )
+							res = ( res & __builtin_amdgcn_mov_dpp( res, 0xb1, 0xf, 0xf, true ) & 4 ) | ( res & 3 );		// (with the neighbour's: the length's state, and both tests passed)
+							const int	r0 = QUAD_LANE( res, 0 ), r2 = QUAD_LANE( res, 2 );
+							const unsigned	el1 = unsigned( QUAD_LANE( el, 1 ) ), el3 = unsigned( QUAD_LANE( el, 3 ) );
+#undef QUAD_LANE
+							if( go ){
+								go = rmd_passa_fold( e0, want_masks, h0, r0 & 3, ( r0 & 4 ) != 0, el1, &keep, &hm[ 0 ], &hm[ 1 ] );
+								go = go && rmd_passa_fold( e0, want_masks, h0 + 1, r2 & 3, ( r2 & 4 ) != 0, el3, &keep, &hm[ 0 ], &hm[ 1 ] );
+							}
+						}
+						keep = keep && ( ltid & 3 ) == 0;
+					}else
 					if( i < nq ){
 						item = i < qcap ? queue[ i ] : __hip_atomic_load( spill + ( i - qcap ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
 						const int	r = int( item & 0xffffu );
@@ -2099,7 +2094,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 									ok = t;
 								if( ok && head_from_rows ){
 									// the first helix of the interior, 5' strand at one of a few offsets from the
-									// interior's start: can any 3' end start it? (rows_win: its first minlen pairs)
+									// interior's start: can any 3' end start it? (rmd_rows_win: its first minlen pairs)
 									const rmd_elem_t	&H = P->elems[ P->searches[ e0.head_s ] ];
 									const int	lim = ( H.ends & RMA_5PAIRED ) ? H.mplim : ( H.mplim > 1 ? H.mplim : 1 );
 									const int	b = szero + span - 1 - hl;		// last position of the interior
@@ -2114,7 +2109,7 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 										if( top - bot >= 64 || q_hi - H.minlen < 0 || q_hi + 96 > vec_words * 64 )
 											ok = true;
 										else{
-											unsigned long long	Wd = rows_win( pb, pb_words, tile, p_lo, H.minlen, lim, ( H.ends & RMA_5PAIRED ) != 0, s5, w0, bot );
+											unsigned long long	Wd = rmd_rows_win( pb, pb_words, tile, p_lo, H.minlen, lim, ( H.ends & RMA_5PAIRED ) != 0, s5, w0, bot );
 											if( !( dbg & RMK_DBG_HEAD_ALL_ENDS ) ){
 												// ... of which the walk takes only those that leave the groups behind the helix their room and let
 												// them reach the interior's end (rmd_lean_open, rmd_lean_step: rem_min, rem_max): bit i = end w0 + i
