@@ -1701,6 +1701,43 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 						if( n_pos - rel_lo < 16 )
 							m &= ( 1u << ( n_pos - rel_lo ) ) - 1u;
 					}
+					if constexpr( !WALK ){
+						// (The instances that walk nothing.)  Handing the bits on in rounds -- one bit a lane, a ballot and a
+						// prefix count a round -- takes as many rounds as the fullest lane has bits, four or five for one
+						// survivor a lane.  Here a lane counts its bits, one prefix sum over the wave gives it its place
+						// among the wave's, and it stores its own positions there, no ballot in the loop; what cbuf
+						// cannot hold yet waits in the lane until 64 have been taken.  The positions reach cbuf in another
+						// order; the candidates' order words do not depend on it (rmd_elem_t::ord_stride).
+						if( lit )
+							for( unsigned t = m; t; t &= t - 1 ){
+								bool	ok;
+								LIT_OK( z0 + rel_lo + __ffs( int( t ) ) - 1, ok );
+								if( !ok )
+									m &= ~( t & ( 0u - t ) );
+							}
+						const int	cnt = __popc( m );
+						int	incl = cnt;
+						for( int o = 1; o < 64; o <<= 1 ){
+							const int	v = __shfl_up( incl, o );
+							if( lane_id >= o )
+								incl += v;
+						}
+						const int	tot = __shfl( incl, 63 );
+						int	at = incl - cnt;		// the place of this lane's next position among the wave's
+						for( int base = 0; base < tot; ){
+							const int	lim = base + ( 128 - n_wait );		// (n_wait < 64: room for 65 and more)
+							while( m && at < lim ){
+								cbuf[ n_wait + at - base ] = uint16_t( rel_lo + __ffs( int( m ) ) - 1 );
+								m &= m - 1;
+								at++;
+							}
+							const int	add = rmd_imin( tot, lim ) - base;
+							n_wait += add;
+							base += add;
+							while( n_wait >= 64 )
+								take();
+						}
+					}else
 					while( __ballot( m != 0 ) ){
 						bool	ok = m != 0;
 						const int	rel = rel_lo + ( ok ? __ffs( int( m ) ) - 1 : 0 );
