@@ -70,7 +70,7 @@ int	rma_scanner_create( const rma_program_t *prog, const rma_efndata_t *efn, int
 int	rma_scanner_set_efn2data( rma_scanner_t *sc, const rma_efn2data_t *efn2, char *err, size_t errlen );
 /* Launch-shape and diagnostic switches (DESIGN.md has the table).  The RNAMOTIF_* environment is read
  * once, by rma_scanner_create(); the switches that may change between scans change through this call
- * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "struct_wgs", "score_budget", "flush", "efn_light", "host_sort", "timing", "short".
+ * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "struct_wgs", "score_budget", "score_heap", "flush", "efn_light", "host_sort", "timing", "short".
  * None of them changes the records a scan returns. */
 int	rma_scanner_set_option( rma_scanner_t *sc, const char *name, int value, char *err, size_t errlen );
 /* One scan of eight start positions, thrown away: what the runtime sets up on first use (code objects,
@@ -514,6 +514,33 @@ int	rma_seqcheck_hits( rma_scanner_t *sc, const rma_seqcheck_t *sq, const rma_db
  * promises that the records it will pass to rma_score_hits() passed rma_seqcheck_hits() (d_keep 1) and are its fixed
  * rows: on any other record of a loose descriptor MAIN judges what the reference never scored. */
 int	rma_score_open_checked( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen );
+
+/* ---- the score section on the device with text: sprintf(), bits(), string + and a string in SCORE.
+ * rma_score_open_flags(): flags 0 is rma_score_open(), RMA_SCORE_CHECKED rma_score_open_checked().  With RMA_SCORE_TEXT
+ * the refusals of sprintf() and bits() fall -- every other refusal and limit stays -- and a record has a heap of option
+ * "score_heap" bytes (rma_scanner_set_option; 256 unless set) in which string + and sprintf() make their strings:
+ * a string that does not fit stops the record.  sprintf() writes %d %i %u %o %x %X of an int, %s of a string, %f of a
+ * float, %n and %% with the flags - + blank 0 #, a width and a precision, the bytes of the host's snprintf (%f: every
+ * finite double below 2^63 in magnitude, a precision up to 18).  What the host VM only notes as an error -- a wrong
+ * argument type, no such argument, an unsupported conversion -- stops the record, as do '*', '$' and length modifiers,
+ * %e %E %g %G (refused when the program is opened where the format is a constant), a larger precision and a double %f
+ * cannot write.  bits() reads the host's own logarithms from a table made when the program is opened, for windows of up
+ * to L bases -- the sum of the elements' greatest lengths, at most 1024; a longer window stops the record. */
+#define RMA_SCORE_CHECKED 1u   /* as rma_score_open_checked() */
+#define RMA_SCORE_TEXT    2u   /* sprintf(), bits(), string +, a string in SCORE */
+int	rma_score_open_flags( const rma_descr_t *d, unsigned flags, rma_score_t **out, char *err, size_t errlen );
+/* rma_score_hits() with the score column as bytes.  Row h of d_text (text_stride bytes a row) is the field
+ * HitPrinter::print writes behind the one blank after the name: %8d of an int SCORE, %8.3lf of a float or of none, %8s
+ * of a string; d_text_len[ h ] is its length (at least 8; 0 for a rejected record), bytes behind it are not written.
+ * d_kind[ h ] is 3 for a string SCORE, whose d_score[ h ] is 0.0.  A field longer than text_stride stops the record, as
+ * does a float SCORE %8.3lf cannot write alike on host and device (not finite, 2^63 or more).  The program may be
+ * opened with or without RMA_SCORE_TEXT, as rma_score_hits() takes both (and stops on a string SCORE).
+ * Everything else as rma_score_hits(): the checks, chunks of 2^17 records, results in scratch of the scanner's until
+ * the check has passed, a failed call writes nothing, one wait, the order on the caller's stream. */
+int	rma_score_hits_text( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *letters, uint8_t *d_accept, double *d_score /* or NULL */, int8_t *d_kind /* or NULL */,
+		uint8_t *d_text /* n_hits * text_stride */, int32_t text_stride, int32_t *d_text_len /* n_hits */,
+		void *stream, char *err, size_t errlen );
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,8 @@ def lib() -> C.CDLL:
     L.rma_score_info.restype = None
     L.rma_score_hits.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_score_open_checked.argtypes = [vp, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.rma_score_open_flags.argtypes = [vp, C.c_uint, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.rma_score_hits_text.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, vp, vp, vp, vp, C.c_int32, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_seqcheck_open.argtypes = [vp, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
     L.rma_seqcheck_close.argtypes = [vp]
     L.rma_seqcheck_close.restype = None
@@ -474,22 +476,30 @@ class ScoreProgram:
     bits(), mismatches( string, pattern ), =~ / !~, a read of NAME, a loose descriptor, an image beyond the limits of
     csrc/rm_score_image.h.  The descriptor itself is not touched: the image is made from a private copy.
     checked=True (rma_score_open_checked) opens a loose descriptor too: the caller promises to score only
-    r.hits[r.keep] of r = Scanner.seq_check(db, hits), the records that are rnamotif's candidates, as fixed rows."""
+    r.hits[r.keep] of r = Scanner.seq_check(db, hits), the records that are rnamotif's candidates, as fixed rows.
+    text=True (rma_score_open_flags with RMA_SCORE_TEXT) opens a program with sprintf(), bits(), string + and a string
+    in SCORE: the rule then makes strings in a heap of option "score_heap" bytes a record, writes printf's %d %s %f
+    with the host's bytes and reads bits()'s logarithms from a table made here; %e %E %g %G in a constant format is
+    refused.  Scanner.score(..., text=True) delivers the score column of such a program."""
 
-    def __init__(self, descr: Descriptor, checked: bool = False):
+    def __init__(self, descr: Descriptor, checked: bool = False, text: bool = False):
         h = C.c_void_p()
         err = C.create_string_buffer(_ERRLEN)
         L = lib()
-        _check((L.rma_score_open_checked if checked else L.rma_score_open)(descr._h, C.byref(h), err, _ERRLEN), err)
+        if text:
+            _check(L.rma_score_open_flags(descr._h, (1 if checked else 0) | 2, C.byref(h), err, _ERRLEN), err)
+        else:
+            _check((L.rma_score_open_checked if checked else L.rma_score_open)(descr._h, C.byref(h), err, _ERRLEN), err)
         self._h = h
         self.descr = descr
         self.checked = bool(checked)
+        self.text = bool(text)
 
     @staticmethod
-    def reason(descr: Descriptor, checked: bool = False) -> Optional[str]:
-        """Why ScoreProgram(descr, checked) would refuse, or None where it opens."""
+    def reason(descr: Descriptor, checked: bool = False, text: bool = False) -> Optional[str]:
+        """Why ScoreProgram(descr, checked, text) would refuse, or None where it opens."""
         try:
-            ScoreProgram(descr, checked).close()
+            ScoreProgram(descr, checked, text).close()
         except RnamotifError as e:
             return str(e)
         return None
@@ -562,14 +572,21 @@ class HitScores:
 
     accept  torch.bool [n]   the record is a hit: MAIN accepts it
     score   float64 [n]      its SCORE, an int as its exact double; 0.0 for a rejected record
-    kind    int8 [n]         0: no SCORE, 1: an int, 2: a float; 0 for a rejected record"""
+    kind    int8 [n]         0: no SCORE, 1: an int, 2: a float, 3: a string (score 0.0); 0 for a rejected record
+    with Scanner.score(..., text=True):
+    text_bytes  uint8 [n, W]  the score column HitPrinter::print writes behind the blank after the name: %8d of an int
+                              SCORE, %8.3lf of a float or of none, %8s of a string; bytes behind text_len are not written
+    text_len    int32 [n]     its length, 0 for a rejected record"""
 
-    def __init__(self, accept, score, kind):
+    def __init__(self, accept, score, kind, text_bytes=None, text_len=None):
         self.accept, self.score, self.kind = accept, score, kind
+        self.text_bytes, self.text_len = text_bytes, text_len
 
     def text(self, h: int) -> bytes:
-        """The nine bytes HitPrinter::print puts behind the name for record h: " %8d" of an int SCORE, " %8.3lf" of a
-        float, " %8.3lf" of 0.0 where there is none."""
+        """What HitPrinter::print puts behind the name for record h, the blank and the score column: " %8d" of an int
+        SCORE, " %8.3lf" of a float, " %8.3lf" of 0.0 where there is none and, with text_bytes, " %8s" of a string."""
+        if self.text_bytes is not None:
+            return b" " + bytes(self.text_bytes[h, :int(self.text_len[h])].cpu().numpy().tobytes())
         k = int(self.kind[h])
         v = float(self.score[h])
         if k == 1:
@@ -868,7 +885,8 @@ class Scanner:
             hits.record_stream(stream)
         return keep
 
-    def score(self, db: Database, hits, program: ScoreProgram, letters: Optional[bytes] = None, out=None) -> HitScores:
+    def score(self, db: Database, hits, program: ScoreProgram, letters: Optional[bytes] = None, out=None, text: bool = False,
+              text_width: int = 64) -> HitScores:
         """The score section's MAIN on each of these records, on the GPU (rma_score_hits; the rule is
         csrc/rm_score_core.h's, what ScoreVM::run does on the host): a HitScores -- which records are hits, and the
         SCORE of each -- so that hits[scores.accept] goes on to prune(), hit_structures(), align() without a trip to
@@ -878,19 +896,38 @@ class Scanner:
         kind) tensors to write instead of new ones.  The call waits once.  A malformed record, and a record on which
         MAIN stops -- type mismatch, undefined variable, bad pos or len, integer division by zero, string + string,
         more than option "score_budget" (2^20) instructions ... -- raise RnamotifError naming the lowest such record;
-        nothing is written then."""
+        nothing is written then.  text=True (rma_score_hits_text): the result also has text_bytes [n, text_width] and
+        text_len [n], the score column of every record as HitPrinter::print writes it, so that a program whose SCORE is
+        a string (kind 3; ScoreProgram(descr, text=True)) is served too; a column longer than text_width stops its
+        record.  out may then hold five tensors."""
         import torch
         hits, n, dev, stream, letters = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner",
                                                     "its records are scored by Replay.batch() or pack()", letters)
         if not isinstance(program, ScoreProgram) or not program._h:
             raise ValueError("program: an open ScoreProgram is needed")
+        if text and (not isinstance(text_width, int) or text_width < 1):
+            raise ValueError(f"text_width: a positive int is needed, not {text_width!r}")
         if out is None:
             out = (torch.empty(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.float64, device=dev),
                    torch.zeros(n, dtype=torch.int8, device=dev))
+            if text:
+                out += (torch.zeros((n, text_width), dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+        if len(out) != (5 if text else 3):
+            raise ValueError("out: (accept, score, kind%s) are needed" % (", text_bytes, text_len" if text else ""))
         for t, dt, what in zip(out, (torch.bool, torch.float64, torch.int8), ("accept", "score", "kind")):
             if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (n,) or t.device != dev or not t.is_contiguous():
                 raise ValueError(f"out: {what} must be a contiguous {dt} tensor [{n}] on {dev}")
-        if n:
+        if text:
+            for t, dt, shape, what in ((out[3], torch.uint8, (n, text_width), "text_bytes"), (out[4], torch.int32, (n,), "text_len")):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"out: {what} must be a contiguous {dt} tensor {list(shape)} on {dev}")
+        if n and text:
+            err = C.create_string_buffer(_ERRLEN)
+            _check(lib().rma_score_hits_text(self._h, program._h, db._h, hits.data_ptr(), n, letters, out[0].data_ptr(),
+                                             out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), text_width, out[4].data_ptr(),
+                                             stream.cuda_stream, err, _ERRLEN), err)
+            hits.record_stream(stream)
+        elif n:
             err = C.create_string_buffer(_ERRLEN)
             _check(lib().rma_score_hits(self._h, program._h, db._h, hits.data_ptr(), n, letters, out[0].data_ptr(),
                                         out[1].data_ptr(), out[2].data_ptr(), stream.cuda_stream, err, _ERRLEN), err)

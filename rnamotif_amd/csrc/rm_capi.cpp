@@ -115,15 +115,15 @@ extern "C" int rma_program_loose( const rma_program_t *p )
 	return n;
 }
 
-static int score_open( const rma_descr_t *d, rma_score_t **out, bool checked, char *err, size_t errlen )
+static int score_open( const rma_descr_t *d, rma_score_t **out, unsigned flags, const char *no_descr, char *err, size_t errlen )
 {
 	if( out != nullptr )
 		*out = nullptr;
 	if( d == nullptr || out == nullptr )
-		return set_err( err, errlen, checked ? "rma_score_open_checked: no descriptor" : "rma_score_open: no descriptor" );
+		return set_err( err, errlen, no_descr );
 	try{
 		std::unique_ptr<rma_score>	sp( new rma_score );
-		const std::string	why = rma::score_image_make( *d->pr.descr, *d->pr.prog, &sp->img, checked );
+		const std::string	why = rma::score_image_make_flags( *d->pr.descr, *d->pr.prog, &sp->img, flags );
 		if( !why.empty() )
 			return set_err( err, errlen, why.c_str() );
 		*out = sp.release();
@@ -137,12 +137,22 @@ static int score_open( const rma_descr_t *d, rma_score_t **out, bool checked, ch
 
 extern "C" int rma_score_open( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen )
 {
-	return score_open( d, out, false, err, errlen );
+	return score_open( d, out, 0u, "rma_score_open: no descriptor", err, errlen );
 }
 
 extern "C" int rma_score_open_checked( const rma_descr_t *d, rma_score_t **out, char *err, size_t errlen )
 {
-	return score_open( d, out, true, err, errlen );
+	return score_open( d, out, RMA_SCORE_CHECKED, "rma_score_open_checked: no descriptor", err, errlen );
+}
+
+extern "C" int rma_score_open_flags( const rma_descr_t *d, unsigned flags, rma_score_t **out, char *err, size_t errlen )
+{
+	if( flags & ~( RMA_SCORE_CHECKED | RMA_SCORE_TEXT ) ){
+		if( out != nullptr )
+			*out = nullptr;
+		return set_err( err, errlen, "rma_score_open_flags: flags other than RMA_SCORE_CHECKED and RMA_SCORE_TEXT" );
+	}
+	return score_open( d, out, flags, "rma_score_open_flags: no descriptor", err, errlen );
 }
 
 extern "C" void rma_score_close( rma_score_t *sp ) { delete sp; }

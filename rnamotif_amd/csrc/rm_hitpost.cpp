@@ -80,7 +80,8 @@ struct rma::HitPost {
 	DevMem	d_se_info;
 	// rma_score_hits: two result words, a stopped record's result and a call's accept flags, kinds and scores; two
 	// page-locked words and a result; the image that is on the device now (its serial; 0: none) and its bytes
-	DevMem	d_sc, d_sc_image;
+	// (behind the image's bytes the table of bits() of an image with text; d_sc_heap: the records' heaps of one chunk)
+	DevMem	d_sc, d_sc_image, d_sc_heap;
 	PinMem	h_sc;
 	uint64_t	sc_serial = 0;
 	// rma_seqcheck_hits: two result words, a stopped record's result and a call's keep flags and fixed rows; two
@@ -842,10 +843,13 @@ namespace {
 constexpr size_t	SC_DETAIL_AT = 64, SC_RESULTS_AT = 256;
 }
 
-extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
-	const uint8_t *letters, uint8_t *d_accept, double *d_score, int8_t *d_kind, void *stream, char *err, size_t errlen )
+// rma_score_hits_text() is the same call with three more outputs: the score column of every record as bytes, in scratch
+// like the rest, copied out row by row up to each row's length.  An image with RMS_IMG_TEXT brings its table of bits()
+// behind its bytes and takes a chunk's heaps from the scanner; it and every text call run rma_score_text_kernel.
+static int score_hits( const char *who, bool text_call, rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, uint8_t *d_accept, double *d_score, int8_t *d_kind, uint8_t *d_text, int32_t text_stride, int32_t *d_text_len,
+	void *stream, char *err, size_t errlen )
 {
-	const char	*who = "rma_score_hits";
 	if( sc == nullptr || sp == nullptr || db == nullptr ){
 		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : sp == nullptr ? "score program" : "database" );
 		return 1;
@@ -859,10 +863,17 @@ extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const r
 		return 1;
 	if( n_hits == 0 )
 		return 0;
-	if( d_accept == nullptr ){
+	if( d_accept == nullptr || ( text_call && ( d_text == nullptr || d_text_len == nullptr ) ) ){
 		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )n_hits );
 		return 1;
 	}
+	if( text_call && ( text_stride < 1 || n_hits > ( int64_t( 1 ) << 40 ) / text_stride ) ){
+		snprintf( err, errlen, "%s: %lld records, rows of %d bytes: bad arguments", who, ( long long )n_hits, text_stride );
+		return 1;
+	}
+	if( text_call && ( rma::check_device_bytes( d_text, sc->device, 0, n_hits * text_stride, "the text", err, errlen ) ||
+		rma::check_device_bytes( d_text_len, sc->device, 0, n_hits * 4, "the text's lengths", err, errlen ) ) )
+		return 1;
 	if( rma::check_device_bytes( d_accept, sc->device, 0, n_hits, "the accept flags", err, errlen ) ||
 		( d_score != nullptr && rma::check_device_bytes( d_score, sc->device, 0, n_hits * 8, "the scores", err, errlen ) ) ||
 		( d_kind != nullptr && rma::check_device_bytes( d_kind, sc->device, 0, n_hits, "the kinds", err, errlen ) ) )
@@ -881,7 +892,15 @@ extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const r
 	rma::HitPost	&p = *sc->post;
 	rma::HitWindowScratch	*s = p.win;
 	hipStream_t	st = s->stream.get(), caller = static_cast<hipStream_t>( stream );
-	const size_t	n = size_t( n_hits ), flags = ( n + 7 ) & ~size_t( 7 ), want = SC_RESULTS_AT + 2 * flags + 8 * n;
+	const bool	img_text = ( m->flags & RMS_IMG_TEXT ) != 0, text_kernel = text_call || img_text;
+	const size_t	n = size_t( n_hits ), flags = ( n + 7 ) & ~size_t( 7 ), rows = text_call ? ( n * size_t( text_stride ) + 7 ) & ~size_t( 7 ) : 0;
+	const size_t	want = SC_RESULTS_AT + 2 * flags + 8 * n + rows + ( text_call ? 4 * n : 0 );
+	const int	heap_cap = img_text ? sc->opt.score_heap : 0;
+	const size_t	heap = rma::score_heap_bytes( ( long long )std::min( HW_CHUNK, n_hits ), heap_cap );
+	if( heap > p.d_sc_heap.bytes() ){
+		HIPCHK( hipStreamSynchronize( st ) );
+		HIPCHK( p.d_sc_heap.room( heap ) );
+	}
 	if( want > p.d_sc.bytes() )		// (the copies of the call before this one may still read the block that goes)
 		HIPCHK( hipStreamSynchronize( st ) );
 	HIPCHK( p.d_sc.room( want ) );
@@ -890,8 +909,11 @@ extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const r
 	if( p.sc_serial != sp->img.serial ){
 		HIPCHK( hipStreamSynchronize( st ) );
 		p.sc_serial = 0;		// (no image's until this one's bytes are in)
-		HIPCHK( p.d_sc_image.room( size_t( m->bytes ) ) );
+		const size_t	table = sp->img.bits_tab.size() * sizeof( double );
+		HIPCHK( p.d_sc_image.room( size_t( m->bytes ) + table ) );
 		HIPCHK( hipMemcpy( p.d_sc_image.as<void>(), m, size_t( m->bytes ), hipMemcpyHostToDevice ) );
+		if( table > 0 )
+			HIPCHK( hipMemcpy( p.d_sc_image.as<char>() + m->bytes, sp->img.bits_tab.data(), table, hipMemcpyHostToDevice ) );
 		p.sc_serial = sp->img.serial;
 	}
 	const uint8_t	*tab = nullptr;
@@ -906,12 +928,27 @@ extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const r
 	uint8_t	*acc = reinterpret_cast<uint8_t *>( base + SC_RESULTS_AT );
 	int8_t	*kind = reinterpret_cast<int8_t *>( acc + flags );
 	double	*score = reinterpret_cast<double *>( acc + 2 * flags );
+	uint8_t	*text = reinterpret_cast<uint8_t *>( score + n );
+	int32_t	*text_len = reinterpret_cast<int32_t *>( text + rows );
+	const double	*bits_tab = sp->img.bits_tab.empty() ? nullptr : reinterpret_cast<const double *>( p.d_sc_image.as<char>() + m->bytes );
 	HIPCHK( hipMemsetAsync( d_words, 0xff, 2 * sizeof( unsigned long long ), st ) );
 	const int	stride = rma_hit_stride( &sc->prog );
 	auto batch = [&]( int64_t c0, int64_t cn, RmsResult *detail ){
-		return rma::ScoreBatch{ p.d_sc_image.as<RmsImage>(), m->bytes, m->stack, m->n_vars, d_hits + c0 * stride, ( long long )cn, ( long long )c0, stride,
+		rma::ScoreBatch	b{ p.d_sc_image.as<RmsImage>(), m->bytes, m->stack, m->n_vars, d_hits + c0 * stride, ( long long )cn, ( long long )c0, stride,
 			rma::hitwin_shape( sc->prog ), db->d_slen, db->d_text_start, db->n_seq, db->text, tab, codes, sc->opt.score_budget,
 			acc + c0, score + c0, kind + c0, d_words, d_words + 1, detail };
+		if( text_kernel ){
+			b.text_kernel = 1;
+			b.heap = heap > 0 ? p.d_sc_heap.as<uint8_t>() : nullptr;
+			b.heap_cap = heap_cap;
+			b.bits_tab = bits_tab;
+			if( text_call ){
+				b.col = text + c0 * text_stride;
+				b.col_stride = text_stride;
+				b.col_len = text_len + c0;
+			}
+		}
+		return b;
 	};
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
 		HIPCHK( rma::score_records( batch( c0, std::min( HW_CHUNK, n_hits - c0 ), nullptr ), st ) );
@@ -934,7 +971,25 @@ extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const r
 		HIPCHK( hipMemcpyAsync( d_score, score, 8 * n, hipMemcpyDeviceToDevice, st ) );
 	if( d_kind != nullptr )
 		HIPCHK( hipMemcpyAsync( d_kind, kind, n, hipMemcpyDeviceToDevice, st ) );
+	if( text_call ){
+		HIPCHK( rma::score_text_copy( d_text, text, text_len, ( long long )n_hits, text_stride, st ) );
+		HIPCHK( hipMemcpyAsync( d_text_len, text_len, 4 * n, hipMemcpyDeviceToDevice, st ) );
+	}
 	return rma::stream_after( caller, st, err, errlen );
+}
+
+extern "C" int rma_score_hits( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, uint8_t *d_accept, double *d_score, int8_t *d_kind, void *stream, char *err, size_t errlen )
+{
+	return score_hits( "rma_score_hits", false, sc, sp, db, d_hits, n_hits, letters, d_accept, d_score, d_kind, nullptr, 0, nullptr, stream, err, errlen );
+}
+
+extern "C" int rma_score_hits_text( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_t *db, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, uint8_t *d_accept, double *d_score, int8_t *d_kind, uint8_t *d_text, int32_t text_stride, int32_t *d_text_len,
+	void *stream, char *err, size_t errlen )
+{
+	return score_hits( "rma_score_hits_text", true, sc, sp, db, d_hits, n_hits, letters, d_accept, d_score, d_kind, d_text, text_stride, d_text_len,
+		stream, err, errlen );
 }
 
 extern "C" void rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] )
@@ -954,7 +1009,7 @@ extern "C" void rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] )
 	info[ 5 ] = waves;
 	info[ 6 ] = m->bytes + RMS_LDS_TABLES + waves * wave;
 	int	priv = -1, lds = -1, regs = -1;
-	if( rma::score_kernel_attributes( &priv, &lds, &regs ) != hipSuccess )
+	if( rma::score_kernel_attributes( &priv, &lds, &regs, ( m->flags & RMS_IMG_TEXT ) != 0 ) != hipSuccess )
 		( void )hipGetLastError();
 	info[ 7 ] = priv;
 	info[ 8 ] = lds;

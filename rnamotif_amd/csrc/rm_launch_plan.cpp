@@ -52,6 +52,7 @@ bool Options::set( const std::string &n, int value )
 	else if( n == "search_wgs" ) search_wgs = std::max( 0, value );
 	else if( n == "struct_wgs" ) struct_wgs = std::max( 0, value );
 	else if( n == "score_budget" ) score_budget = std::max( 1, value );
+	else if( n == "score_heap" ) score_heap = std::min( std::max( 0, value ), 1 << 16 );
 	else if( n == "flush" ) flush = value;
 	else if( n == "efn_light" ) efn_light = value;
 	else if( n == "host_sort" ) host_sort = value;

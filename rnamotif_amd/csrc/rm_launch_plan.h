@@ -27,6 +27,7 @@ struct Options {
 	int	search_wgs = 0;		// > 0: workgroups of a lean search kernel per CU (fewer than fit: another scanner's drain kernel runs beside it)
 	int	struct_wgs = 0;		// > 0: workgroups of the kernels of rma_structure_energies (tests: a grid-stride loop over a few hundred structures)
 	int	score_budget = 1 << 20;	// instructions of the score section a record of rma_score_hits may take before it stops (RMS_DEFAULT_BUDGET)
+	int	score_heap = 256;	// bytes of heap a record of a score program with text has for the strings it makes (RMS_DEFAULT_HEAP)
 	int	host_sort = 0, timing = 0;
 	int	short_force = -1;	// -1: by the mean entry length, 0 never, 1 always groups of small tiles, 2 always tiles over the concatenation
 	int	tile = 0, qcap = 0;	// forced tile size / queue entries, 0: computed

@@ -289,7 +289,7 @@ extern "C" int rma_scanner_set_option( rma_scanner_t *sc, const char *name, int 
 		sc->last_relabelled = false;
 	}else if( !sc->opt.set( n, value ) ){
 		snprintf( err, errlen, "rma_scanner_set_option: no option '%s' that can change after creation "
-			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, struct_wgs, score_budget, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
+			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, struct_wgs, score_budget, score_heap, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
 		return 1;
 	}
 	return 0;

@@ -13,6 +13,14 @@
 // rms_stop_text() (rm_score_image.cpp) makes the host VM's words of them.  One stop the host VM does not have: more
 // than `budget` instructions for one record.
 //
+// An image opened with RMS_IMG_TEXT (rm_score_image.h) has a third string type, RMS_T_HSTR: a slice of the lane's heap,
+// an arena of `heap_cap` bytes a record that only grows (RmsMem::HB; on the device dwords interleaved by lane in global
+// memory).  String + concatenates into it, sprintf() (do_sprintf, directive for directive, through rm_score_fmt.h)
+// writes into it, bits() (do_bits) reads its logarithms from the image's table (RmsText::bits_tab), and a string in
+// SCORE at ACCEPT is kind 3.  With a row to write (RmsText::row) ACCEPT leaves the score column HitPrinter::print
+// writes: %8d, %8.3lf or %8s.  Every directive on which the host VM only notes an error stops here.  rms_run_t< false >
+// is the rule without any of this, what rms_run() is.
+//
 // Where the host VM would read what it has freed or never wrote -- a string slot after && / || / ! (its pointer's low
 // word is overwritten), substr() of something that is no string, $ on an entry of rm_xdescr behind rm_descr's end --
 // the rule stops with "type mismatch" or the $ stop.  The value an assignment leaves on the stack is the host's
@@ -26,6 +34,7 @@
 #include <cstdint>
 #include <cstring>
 #include "rm_score_image.h"
+#include "rm_score_fmt.h"
 
 #ifndef RMD_FN
 #define RMD_FN	static inline
@@ -37,7 +46,8 @@
 // value types: T_* of rm_host.h, then the rule's own
 enum { RMS_T_UNDEF, RMS_T_INT, RMS_T_FLOAT, RMS_T_STRING, RMS_T_PAIRSET, RMS_T_POS, RMS_T_IDENT, RMS_T_HIT,
 	RMS_T_BSTR,		// a string: a slice of the record's strand
-	RMS_T_DEAD		// a string slot whose pointer && / || / ! overwrote: only its int view is left
+	RMS_T_DEAD,		// a string slot whose pointer && / || / ! overwrote: only its int view is left
+	RMS_T_HSTR		// a string: a slice of the lane's heap
 };
 // op codes and builtins: OP_* and SC_* of rm_score.h
 enum {
@@ -52,7 +62,7 @@ enum {
 };
 
 enum { RMS_REJECT, RMS_ACCEPT, RMS_STOPPED };
-enum { RMS_KIND_NONE, RMS_KIND_INT, RMS_KIND_FLOAT };
+enum { RMS_KIND_NONE, RMS_KIND_INT, RMS_KIND_FLOAT, RMS_KIND_STRING };
 
 // why a record stopped; a0, a1, a2 as the words need them (rms_stop_text)
 enum {
@@ -85,6 +95,22 @@ enum {
 	RMS_STOP_LOC_RANGE, RMS_STOP_LOC_POS_NEG, RMS_STOP_LOC_LEN, RMS_STOP_LOC_POS_BIG,
 	RMS_STOP_PAIRED_POS, RMS_STOP_PAIRED_LEN, RMS_STOP_PAIRED_SS,
 	RMS_STOP_SUBSTR_POS, RMS_STOP_SUBSTR_LEN,
+	// an image with RMS_IMG_TEXT
+	RMS_STOP_HEAP,			// a0: bytes asked for, a1: score_heap, a2: bytes in use
+	RMS_STOP_TEXT_ROOM,		// a0: the score column's length, a1: text_stride
+	RMS_STOP_TEXT_RANGE,		// SCORE is a float %8.3lf cannot be written alike on host and device
+	RMS_STOP_SPF_FIRST,		// sprintf: the first argument is no string
+	RMS_STOP_SPF_BAD,		// no conversion letter; a0: string type, a1: offset, a2: length of the format's rest
+	RMS_STOP_SPF_STAR,		// * or $
+	RMS_STOP_SPF_NO_ARG,		// a0: the argument
+	RMS_STOP_SPF_NEED_FLOAT, RMS_STOP_SPF_NEED_INT, RMS_STOP_SPF_NEED_STRING, RMS_STOP_SPF_UNSUPPORTED,	// a0: the letter
+	RMS_STOP_SPF_EG,		// a0: the letter, one of e E g G
+	RMS_STOP_SPF_MODIFIER,		// a0: the letter
+	RMS_STOP_SPF_PREC,		// a0: the precision
+	RMS_STOP_SPF_RANGE,		// %f of a double that is not finite or not below 2^63
+	RMS_STOP_BITS_POS1_NEG, RMS_STOP_BITS_LEN1, RMS_STOP_BITS_POS1_BIG, RMS_STOP_BITS_ORDER, RMS_STOP_BITS_POS2_NEG, RMS_STOP_BITS_LEN2,
+	RMS_STOP_BITS_POS2_BIG,
+	RMS_STOP_BITS_SPAN,		// a0: bases, a1: the table's L
 	RMS_N_STOP
 };
 
@@ -93,6 +119,14 @@ struct RmsResult {
 	int32_t	kind;		// of SCORE, for an accepted record
 	double	score;		// an int SCORE as its exact double
 	int32_t	stop, pc, a0, a1, a2;
+	int32_t	text_len;	// bytes of the score column in RmsText::row
+};
+
+// what the rule of an image with RMS_IMG_TEXT reads and writes beside the planes
+struct RmsText {
+	const double	*bits_tab = nullptr;	// 3.32... * log10( b / len ) at ( len - 1 ) * len / 2 + b - 1, 1 <= b <= len <= RmsImage::bits_L
+	uint8_t	*row = nullptr;		// not null: where ACCEPT writes the score column, row_cap bytes
+	int	row_cap = 0;
 };
 
 // the parts of an image
@@ -110,6 +144,10 @@ template< int STRIDE > struct RmsMem {
 	int32_t	*w;
 	uint8_t	*e;
 	int	stack, n_vars;
+	uint8_t	*heap = nullptr;	// the lane's arena: byte k at ( k >> 2 ) * 4 * STRIDE + ( k & 3 )
+	int	heap_cap = 0;
+	static constexpr int	stride = STRIDE;
+	RMD_FN_MEMBER uint8_t	&HB( int k ) const { return heap[ ( ( k < 0 ? 0 : k >= heap_cap ? heap_cap - 1 : k ) >> 2 ) * 4 * STRIDE + ( k & 3 ) ]; }
 	RMD_FN_MEMBER int	slot( int k ) const { return k < 0 ? 0 : k >= stack ? stack - 1 : k; }
 	RMD_FN_MEMBER int	var( int v ) const { return stack + ( v < 0 ? 0 : v >= n_vars ? n_vars - 1 : v ); }
 	RMD_FN_MEMBER int32_t	&T( int k ) const { return w[ ( 3 * slot( k ) ) * STRIDE ]; }
@@ -136,7 +174,7 @@ RMD_FN void rms_words( double d, int32_t *lo, int32_t *hi )
 	*hi = int32_t( uint32_t( u >> 32 ) );
 }
 
-RMD_FN int rms_is_string( int t ) { return t == RMS_T_STRING || t == RMS_T_BSTR; }
+RMD_FN int rms_is_string( int t ) { return t == RMS_T_STRING || t == RMS_T_BSTR || t == RMS_T_HSTR; }
 
 // b2bc[], compile.c:180-187
 RMD_FN int rms_b2bc( unsigned char c )
@@ -171,6 +209,38 @@ template< class Bases > RMD_FN int rms_strcmp( const RmsImage *m, const Bases &b
 	return n1 < n2 ? -1 : n1 > n2;
 }
 
+// the same with the heap's slices; TEXT false: the two above
+template< bool TEXT, class Mem, class Bases > RMD_FN unsigned char rms_char_t( const RmsImage *m, const Bases &bases, const Mem &mem, int type, int off, int i )
+{
+	if( TEXT && type == RMS_T_HSTR ){
+		const unsigned	at = unsigned( off ) + unsigned( i );
+		return at < unsigned( mem.heap_cap ) ? mem.HB( int( at ) ) : 0;
+	}
+	return rms_char( m, bases, type, off, i );
+}
+template< bool TEXT, class Mem, class Bases >
+RMD_FN int rms_strcmp_t( const RmsImage *m, const Bases &bases, const Mem &mem, int t1, int o1, int n1, int t2, int o2, int n2 )
+{
+	if( !TEXT )
+		return rms_strcmp( m, bases, t1, o1, n1, t2, o2, n2 );
+	const int	n = n1 < n2 ? n1 : n2;
+	for( int i = 0; i < n; i++ ){
+		const int	a = rms_char_t<TEXT>( m, bases, mem, t1, o1, i ), b = rms_char_t<TEXT>( m, bases, mem, t2, o2, i );
+		if( a != b )
+			return a < b ? -1 : 1;
+	}
+	return n1 < n2 ? -1 : n1 > n2;
+}
+
+// the bytes of a string value, for the formatter
+template< bool TEXT, class Mem, class Bases > struct RmsStr {
+	const RmsImage	*m;
+	const Bases	&bases;
+	const Mem	&mem;
+	int	type, off;
+	RMD_FN_MEMBER unsigned char	operator()( int i ) const { return rms_char_t<TEXT>( m, bases, mem, type, off, i ); }
+};
+
 // where a row of the element table has its offset and length in the record
 RMD_FN int rms_row_word( const RmsImage *m, int row )
 {
@@ -179,9 +249,11 @@ RMD_FN int rms_row_word( const RmsImage *m, int row )
 
 // The rule.  w: the record; slen: its entry's length; bases( i ): the letter at position i of the record's strand;
 // mem: the lane's planes, sized for m->stack slots and m->n_vars variables.
-template< class Mem, class Bases >
-RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases &bases, const Mem &mem, int budget, RmsResult *r )
+template< bool TEXT, class Mem, class Bases >
+RMD_FN void rms_run_t( const RmsImage *m, const int32_t *w, int slen, const Bases &bases, const Mem &mem, int budget, RmsResult *r, const RmsText &tx )
 {
+	const bool	text = TEXT && ( m->flags & RMS_IMG_TEXT ) != 0;
+	int	hp = 0;		// bytes of the heap in use
 	const RmsInst	*prog = rms_inst( m );
 	const int32_t	*xd = rms_xd( m );
 	const RmsElem	*rows = rms_rows( m );
@@ -192,6 +264,7 @@ RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases 
 	r->score = 0.0;
 	r->stop = RMS_STOP_NONE;
 	r->pc = r->a0 = r->a1 = r->a2 = 0;
+	r->text_len = 0;
 #define RMS_STOP( code, x, y, z )	do{ r->outcome = RMS_STOPPED; r->stop = ( code ); r->pc = pc - 1; r->a0 = ( x ); r->a1 = ( y ); r->a2 = ( z ); return; }while( 0 )
 #define RMS_MLEN( row )	( w[ rms_row_word( m, ( row ) ) + 1 ] )
 #define RMS_MOFF( row )	( w[ rms_row_word( m, ( row ) ) ] )
@@ -384,7 +457,7 @@ RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases 
 			for( int i = 0; i < l0 && rv; i++ ){
 				int	ix = 0;
 				for( int k = 0; k < n_bases; k++ )
-					ix = ix * 5 + rms_b2bc( rms_char( m, bases, mem.T( mp + 1 + k ), mem.L( mp + 1 + k ), i ) );
+					ix = ix * 5 + rms_b2bc( rms_char_t<TEXT>( m, bases, mem, mem.T( mp + 1 + k ), mem.L( mp + 1 + k ), i ) );
 				if( n_bases == 2 )
 					rv = ( ps->mat2 >> ix ) & 1;
 				else if( n_bases == 3 )
@@ -412,7 +485,7 @@ RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases 
 				const double	b = t2 == RMS_T_INT ? double( mem.L( top ) ) : rms_double( mem.L( top ), mem.H( top ) );
 				c = a < b ? -1 : a > b ? 1 : a == b ? 0 : 2;
 			}else if( rms_is_string( t1 ) && rms_is_string( t2 ) )
-				c = rms_strcmp( m, bases, t1, mem.L( sp ), mem.H( sp ), t2, mem.L( top ), mem.H( top ) );
+				c = rms_strcmp_t<TEXT>( m, bases, mem, t1, mem.L( sp ), mem.H( sp ), t2, mem.L( top ), mem.H( top ) );
 			else
 				RMS_STOP( RMS_STOP_TYPE, 0, 0, 0 );
 			int	rv;
@@ -458,8 +531,21 @@ RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases 
 					mem.L( sp ) = lo;
 					mem.H( sp ) = hi;
 				}
-			}else if( rms_is_string( t1 ) && rms_is_string( t2 ) && op == RMS_OP_ADD )
-				RMS_STOP( RMS_STOP_STRCAT, 0, 0, 0 );
+			}else if( rms_is_string( t1 ) && rms_is_string( t2 ) && op == RMS_OP_ADD ){
+				if( !text )
+					RMS_STOP( RMS_STOP_STRCAT, 0, 0, 0 );
+				const int	n1 = mem.H( sp ), n2 = mem.H( top );
+				if( n1 < 0 || n2 < 0 || n1 + n2 > mem.heap_cap - hp )
+					RMS_STOP( RMS_STOP_HEAP, n1 + n2, mem.heap_cap, hp );
+				for( int i = 0; i < n1; i++ )
+					mem.HB( hp + i ) = rms_char_t<TEXT>( m, bases, mem, t1, mem.L( sp ), i );
+				for( int i = 0; i < n2; i++ )
+					mem.HB( hp + n1 + i ) = rms_char_t<TEXT>( m, bases, mem, t2, mem.L( top ), i );
+				mem.T( sp ) = RMS_T_HSTR;
+				mem.L( sp ) = hp;
+				mem.H( sp ) = n1 + n2;
+				hp += n1 + n2;
+			}
 			else
 				RMS_STOP( RMS_STOP_TYPE, 0, 0, 0 );
 			break;
@@ -545,7 +631,7 @@ RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases 
 				}else if( rms_is_string( t ) ){
 					for( int s = 0; s < n_xd && idx < 0; s++ ){
 						const RmsElem	&el = rows[ xd[ s ] ];
-						if( el.tag_len < 0 || rms_strcmp( m, bases, RMS_T_STRING, el.tag_off, el.tag_len, t, mem.L( sp ), mem.H( sp ) ) )
+						if( el.tag_len < 0 || rms_strcmp_t<TEXT>( m, bases, mem, RMS_T_STRING, el.tag_off, el.tag_len, t, mem.L( sp ), mem.H( sp ) ) )
 							continue;
 						if( el.type == stype || ( el.type == m->sym_ss && stype == m->sym_se ) )
 							idx = s;
@@ -698,7 +784,158 @@ RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases 
 				rh = len;
 				break;
 			}
-			default :		// bits, sprintf, mismatches( string, pattern ): no image holds them
+			case RMS_SC_BITS : {		// do_bits
+				if( !text )
+					RMS_STOP( RMS_STOP_INTERNAL, 6, 0, 0 );
+				const int	idx = mem.L( sp - 5 ), idx2 = mem.L( sp - 2 );
+				int	pos = mem.L( sp - 4 ), pos2 = mem.L( sp - 1 );
+				if( idx < 0 || idx >= n_xd )
+					RMS_STOP( RMS_STOP_XD, RMS_SC_BITS, idx + 1, n_xd );
+				const int	mlen = RMS_MLEN( xd[ idx ] );
+				if( pos == -1 )
+					pos = 1;
+				else if( pos <= 0 )
+					RMS_STOP( RMS_STOP_BITS_POS1_NEG, pos, 0, 0 );
+				else if( mlen == 0 )
+					RMS_STOP( RMS_STOP_BITS_LEN1, 0, 0, 0 );
+				else if( pos > mlen )
+					RMS_STOP( RMS_STOP_BITS_POS1_BIG, pos, mlen, 0 );
+				pos--;
+				if( idx2 < 0 || idx2 >= n_xd )
+					RMS_STOP( RMS_STOP_XD, RMS_SC_BITS, idx2 + 1, n_xd );
+				if( idx >= idx2 )
+					RMS_STOP( RMS_STOP_BITS_ORDER, idx + 1, idx2 + 1, 0 );	// (sic) the other way round than efn's
+				const int	mlen2 = RMS_MLEN( xd[ idx2 ] );
+				if( pos2 == -1 )
+					pos2 = mlen2;
+				else if( pos2 < 0 )
+					RMS_STOP( RMS_STOP_BITS_POS2_NEG, pos2, 0, 0 );
+				else if( mlen2 == 0 )
+					RMS_STOP( RMS_STOP_BITS_LEN2, 0, 0, 0 );
+				else if( pos2 > mlen2 )
+					RMS_STOP( RMS_STOP_BITS_POS2_BIG, pos2, mlen2, 0 );
+				pos2--;
+				const int	start = RMS_MOFF( xd[ idx ] ) + pos, stop = RMS_MOFF( xd[ idx2 ] ) + pos2, len = stop - start + 1;
+				if( len > m->bits_L || ( len > 0 && tx.bits_tab == nullptr ) )
+					RMS_STOP( RMS_STOP_BITS_SPAN, len, m->bits_L, 0 );
+				// bvec[] in bindex[]'s order: the counts by letter, 16 bits each, and the letters in the order they first occur
+				uint64_t	counts = 0;
+				unsigned	seen = 0, order = 0;
+				int	bn = 0;
+				for( int i = start; i <= stop; i++ ){
+					const int	bc = rms_b2bc( bases( i ) );
+					if( bc != RMA_BC_N ){
+						if( !( ( seen >> bc ) & 1 ) ){
+							seen |= 1u << bc;
+							order |= unsigned( bc ) << ( 2 * bn++ );
+						}
+						counts += uint64_t( 1 ) << ( 16 * bc );
+					}
+				}
+#ifdef RMS_ON_BITS
+				RMS_ON_BITS( bn, len );		// (a host checker counts the windows and their distinct letters)
+#endif
+				double	bits = 0.0;
+				for( int i = 0; i < bn; i++ ){
+					const int	b = int( ( counts >> ( 16 * ( ( order >> ( 2 * i ) ) & 3 ) ) ) & 0xffff );
+					bits += b * tx.bits_tab[ ( len - 1 ) * len / 2 + b - 1 ];
+				}
+				bits /= -len;
+				const float	rval = float( bits );
+				rt = RMS_T_FLOAT;
+				rms_words( double( rval ), &rl, &rh );
+				break;
+			}
+			case RMS_SC_SPRINTF : {		// do_sprintf
+				if( !text )
+					RMS_STOP( RMS_STOP_INTERNAL, 6, 0, 0 );
+				const int	n_args = sp - mp;
+				if( mp < 0 || n_args < 1 || !rms_is_string( mem.T( mp + 1 ) ) )
+					RMS_STOP( RMS_STOP_SPF_FIRST, 0, 0, 0 );
+				const RmsStr<TEXT, Mem, Bases>	f{ m, bases, mem, mem.T( mp + 1 ), mem.L( mp + 1 ) };
+				const int	fn = mem.H( mp + 1 );
+				RmsSink	o{ mem.heap, Mem::stride, hp, mem.heap_cap, 0 };
+				int	c_arg = 0, fp = 0;
+				for( ; ; ){
+					int	pp = fp;
+					while( pp < fn && f( pp ) != '%' )
+						pp++;
+					if( pp >= fn )
+						break;
+					for( int i = fp; i < pp; i++ )
+						o.put( f( i ) );
+					int	epp = pp + 1;
+					while( epp < fn && !rms_fmt_is_conv( f( epp ) ) )
+						epp++;
+					if( epp >= fn )
+						RMS_STOP( RMS_STOP_SPF_BAD, f.type, f.off + pp, fn - pp );
+					const int	type = f( epp );
+					for( int i = pp; i <= epp; i++ )
+						if( f( i ) == '*' || f( i ) == '$' )
+							RMS_STOP( RMS_STOP_SPF_STAR, 0, 0, 0 );
+					const int	r_arg = c_arg + 1;
+					if( r_arg >= n_args )
+						RMS_STOP( RMS_STOP_SPF_NO_ARG, r_arg, 0, 0 );
+					const int	v = mp + r_arg + 1, vt = mem.T( v );
+					c_arg++;
+					RmsSpec	spec;
+					const int	plain = rms_fmt_parse( f, pp + 1, epp, &spec );
+					switch( type ){
+					case 'e' : case 'E' : case 'f' : case 'g' : case 'G' : {
+						if( vt != RMS_T_FLOAT )
+							RMS_STOP( RMS_STOP_SPF_NEED_FLOAT, type, 0, 0 );
+						if( type != 'f' )
+							RMS_STOP( RMS_STOP_SPF_EG, type, 0, 0 );
+						if( !plain )
+							RMS_STOP( RMS_STOP_SPF_MODIFIER, type, 0, 0 );
+						const int	rc = rms_fmt_f( o, spec, rms_double( mem.L( v ), mem.H( v ) ) );
+						if( rc == RMS_FMT_PREC )
+							RMS_STOP( RMS_STOP_SPF_PREC, spec.prec, 0, 0 );
+						if( rc != RMS_FMT_OK )
+							RMS_STOP( RMS_STOP_SPF_RANGE, 0, 0, 0 );
+						break;
+					}
+					case 'd' : case 'i' : case 'o' : case 'u' : case 'x' : case 'X' :
+						if( vt != RMS_T_INT )
+							RMS_STOP( RMS_STOP_SPF_NEED_INT, type, 0, 0 );
+						if( !plain )
+							RMS_STOP( RMS_STOP_SPF_MODIFIER, type, 0, 0 );
+						rms_fmt_int( o, spec, static_cast<unsigned char>( type ), mem.L( v ) );
+						break;
+					case 's' :
+						if( !rms_is_string( vt ) )
+							RMS_STOP( RMS_STOP_SPF_NEED_STRING, type, 0, 0 );
+						if( !plain )
+							RMS_STOP( RMS_STOP_SPF_MODIFIER, type, 0, 0 );
+						rms_fmt_str( o, spec, RmsStr<TEXT, Mem, Bases>{ m, bases, mem, vt, mem.L( v ) }, mem.H( v ) );
+						break;
+					case 'n' :		// (the argument's slot is set to 0, nothing is written)
+						if( vt == RMS_T_INT )
+							mem.L( v ) = 0;
+						else if( vt == RMS_T_FLOAT )
+							mem.L( v ) = mem.H( v ) = 0;
+						else
+							RMS_STOP( RMS_STOP_SPF_NEED_INT, type, 0, 0 );
+						break;
+					case '%' :		// (sic) it has taken an argument's place
+						o.put( '%' );
+						break;
+					default :
+						RMS_STOP( RMS_STOP_SPF_UNSUPPORTED, type, 0, 0 );
+					}
+					fp = epp + 1;
+				}
+				for( int i = fp; i < fn; i++ )
+					o.put( f( i ) );
+				if( o.n > mem.heap_cap - hp )
+					RMS_STOP( RMS_STOP_HEAP, o.n, mem.heap_cap, hp );
+				rt = RMS_T_HSTR;
+				rl = hp;
+				rh = o.n;
+				hp += o.n;
+				break;
+			}
+			default :		// mismatches( string, pattern ): no image holds it
 				RMS_STOP( RMS_STOP_INTERNAL, 6, 0, 0 );
 			}
 			if( mp < 0 )
@@ -718,18 +955,51 @@ accept:
 	// what print_match() reads of SCORE
 	{
 		const int	t = m->v_score >= 0 ? mem.VT( m->v_score ) : RMS_T_UNDEF;
-		if( rms_is_string( t ) )
+		if( rms_is_string( t ) && !( TEXT && tx.row != nullptr ) )
 			RMS_STOP( RMS_STOP_SCORE_STRING, 0, 0, 0 );
-		r->outcome = RMS_ACCEPT;
 		if( t == RMS_T_INT ){
 			r->kind = RMS_KIND_INT;
 			r->score = double( mem.VL( m->v_score ) );
 		}else if( t == RMS_T_FLOAT ){
 			r->kind = RMS_KIND_FLOAT;
 			r->score = rms_double( mem.VL( m->v_score ), mem.VH( m->v_score ) );
+		}else if( rms_is_string( t ) )
+			r->kind = RMS_KIND_STRING;
+		if( TEXT && tx.row != nullptr ){
+			// the score column of HitPrinter::print: %8d, %8s, %8.3lf (of 0.0 where SCORE is none of these)
+			RmsSink	o{ tx.row, 1, 0, tx.row_cap, 0 };
+			if( t == RMS_T_INT )
+				rms_fmt_int( o, RmsSpec{ 0, 8, -1 }, 'd', mem.VL( m->v_score ) );
+			else if( rms_is_string( t ) )
+				rms_fmt_str( o, RmsSpec{ 0, 8, -1 }, RmsStr<TEXT, Mem, Bases>{ m, bases, mem, t, mem.VL( m->v_score ) }, mem.VH( m->v_score ) );
+			else if( rms_fmt_f( o, RmsSpec{ 0, 8, 3 }, r->score ) != RMS_FMT_OK ){
+				r->kind = RMS_KIND_NONE;
+				r->score = 0.0;
+				RMS_STOP( RMS_STOP_TEXT_RANGE, 0, 0, 0 );
+			}
+			if( o.n > tx.row_cap ){
+				r->kind = RMS_KIND_NONE;
+				r->score = 0.0;
+				RMS_STOP( RMS_STOP_TEXT_ROOM, o.n, tx.row_cap, 0 );
+			}
+			r->text_len = o.n;
 		}
+		r->outcome = RMS_ACCEPT;
 	}
 #undef RMS_STOP
 #undef RMS_MLEN
 #undef RMS_MOFF
+}
+
+// the rule of an image opened without RMS_IMG_TEXT, and of a call that delivers numbers
+template< class Mem, class Bases >
+RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases &bases, const Mem &mem, int budget, RmsResult *r )
+{
+	rms_run_t<false>( m, w, slen, bases, mem, budget, r, RmsText() );
+}
+// with the heap (RmsMem::heap), the table of bits() and, where tx.row is set, the score column
+template< class Mem, class Bases >
+RMD_FN void rms_run( const RmsImage *m, const int32_t *w, int slen, const Bases &bases, const Mem &mem, int budget, RmsResult *r, const RmsText &tx )
+{
+	rms_run_t<true>( m, w, slen, bases, mem, budget, r, tx );
 }

@@ -12,6 +12,16 @@
 //                      and reads bases from the database's text through the accessor: table, strand-1 complement, 'n'
 //                      outside the entry.  A stopped record's index goes into *stopped the same way.
 //                      The dynamic LDS is sized at launch: the image, 512 bytes of tables, waves * rms_wave_bytes().
+//   rma_score_text_kernel   the same for an image with RMS_IMG_TEXT or a call that wants the score column as bytes
+//                      (rma_score_hits_text): the rule with its heap, sprintf(), bits() and the column's formatter.  A
+//                      lane's heap is global memory of the scanner's, sized per launch: the 64 lanes of wave v (counted
+//                      over the launch) own 64 * W dwords at v * 64 * W, W = ceil( heap_cap / 4 ); dword j of lane l is
+//                      word j * 64 + l of them, so that the lanes of a wave writing the same offset of their strings
+//                      touch 64 consecutive dwords.  The table of bits() stays in global memory.  A lane writes its
+//                      row of the column itself; col_len[ h ] is the column's length, 0 for a record that is not accepted.
+//                      rma_score_kernel is compiled from the rule without any of this (rms_run_t< false >).
+//   rma_score_text_copy_kernel   bytes [ 0, len[ h ] ) of every row from the scratch to the caller's rows: what lies
+//                      behind a row's length is not written.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
@@ -39,6 +49,14 @@ struct ScoreBatch {
 	int8_t	*kind;			// [ n ]
 	unsigned long long	*bad, *stopped;	// the least index of a bad / a stopped record, preset to ~0
 	RmsResult	*detail;		// not null: where a stopped record leaves its result (a launch of one record)
+	// an image with RMS_IMG_TEXT, or a call with text outputs: rma_score_text_kernel
+	int32_t	text_kernel = 0;
+	uint8_t	*heap = nullptr;	// score_heap_bytes( n, heap_cap ) bytes of the scanner's
+	int32_t	heap_cap = 0;		// bytes of heap a record has
+	const double	*bits_tab = nullptr;	// the image's table of bits(), behind the image in device memory
+	uint8_t	*col = nullptr;		// [ n, col_stride ] the score column, or null
+	int32_t	col_stride = 0;
+	int32_t	*col_len = nullptr;	// [ n ]
 };
 
 #if defined( __HIPCC__ )
@@ -61,7 +79,11 @@ struct ScoreBases {
 int	score_waves( int image_bytes, int stack, int n_vars );
 // Enqueue on s the rule over the batch's records.
 hipError_t	score_records( const ScoreBatch &b, hipStream_t s );
-// the kernel's private bytes, static LDS and registers as the runtime reports them (rma_score_info)
-hipError_t	score_kernel_attributes( int *private_bytes, int *static_lds, int *regs );
+// the kernel's private bytes, static LDS and registers as the runtime reports them (rma_score_info); text: the text kernel's
+hipError_t	score_kernel_attributes( int *private_bytes, int *static_lds, int *regs, bool text = false );
+// bytes of heap a launch of n records takes
+size_t	score_heap_bytes( long long n, int heap_cap );
+// Enqueue on s: bytes [ 0, len[ h ] ) of row h of src to row h of dst, n rows of `stride` bytes.
+hipError_t	score_text_copy( uint8_t *dst, const uint8_t *src, const int32_t *len, long long n, int stride, hipStream_t s );
 
 }	// namespace rma

@@ -12,8 +12,7 @@ namespace {
 
 constexpr int	SC_MAX_WAVES = 4;
 
-__global__ void __launch_bounds__( SC_MAX_WAVES * 64 )
-rma_score_kernel( ScoreBatch b )
+template< bool TEXT > __device__ inline void score_body( const ScoreBatch &b )
 {
 	extern __shared__ __attribute__(( aligned( 16 ) )) uint64_t	lds[];
 	const int	t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -44,10 +43,24 @@ rma_score_kernel( ScoreBatch b )
 	else{
 		const int	wave_words = rms_wave_bytes( b.stack, b.n_vars ) / 4;
 		int32_t	*planes = reinterpret_cast<int32_t *>( cmp + 256 ) + wave * wave_words;
-		const RmsMem<64>	mem{ planes + lane, reinterpret_cast<uint8_t *>( planes + ( b.stack + b.n_vars ) * 3 * 64 ) + lane, b.stack, b.n_vars };
+		RmsMem<64>	mem{ planes + lane, reinterpret_cast<uint8_t *>( planes + ( b.stack + b.n_vars ) * 3 * 64 ) + lane, b.stack, b.n_vars };
 		const int	seq = w[ 0 ], slen = b.slen[ seq ];
 		const ScoreBases	bases{ b.text + b.start[ seq ], let, cmp, w[ 1 ], slen };
-		rms_run( m, w, slen, bases, mem, b.budget, &r );
+		if( TEXT ){
+			RmsText	tx;
+			tx.bits_tab = b.bits_tab;
+			if( b.col != nullptr ){
+				tx.row = b.col + h * b.col_stride;
+				tx.row_cap = b.col_stride;
+			}
+			if( b.heap != nullptr ){
+				const long long	heap_words = ( b.heap_cap + 3 ) / 4;
+				mem.heap = b.heap + ( ( h >> 6 ) * 64 * heap_words + lane ) * 4;
+				mem.heap_cap = b.heap_cap;
+			}
+			rms_run( m, w, slen, bases, mem, b.budget, &r, tx );
+		}else
+			rms_run( m, w, slen, bases, mem, b.budget, &r );
 		if( r.outcome == RMS_STOPPED ){
 			atomicMin( b.stopped, static_cast<unsigned long long>( b.first + h ) );
 			if( b.detail != nullptr )
@@ -58,6 +71,31 @@ rma_score_kernel( ScoreBatch b )
 	b.accept[ h ] = ok ? 1 : 0;
 	b.score[ h ] = ok ? r.score : 0.0;
 	b.kind[ h ] = ok ? int8_t( r.kind ) : int8_t( 0 );
+	if( TEXT && b.col_len != nullptr )
+		b.col_len[ h ] = ok ? r.text_len : 0;
+}
+
+__global__ void __launch_bounds__( SC_MAX_WAVES * 64 )
+rma_score_kernel( ScoreBatch b )
+{
+	score_body<false>( b );
+}
+
+__global__ void __launch_bounds__( SC_MAX_WAVES * 64 )
+rma_score_text_kernel( ScoreBatch b )
+{
+	score_body<true>( b );
+}
+
+__global__ void __launch_bounds__( 256 )
+rma_score_text_copy_kernel( uint8_t *dst, const uint8_t *src, const int32_t *len, long long n, int stride )
+{
+	const long long	i = blockIdx.x * ( long long )blockDim.x + threadIdx.x;
+	if( i >= n * stride )
+		return;
+	const long long	h = i / stride;
+	if( int( i - h * stride ) < len[ h ] )
+		dst[ i ] = src[ i ];
 }
 
 }	// namespace
@@ -78,14 +116,33 @@ hipError_t score_records( const ScoreBatch &b, hipStream_t s )
 		return hipErrorInvalidValue;
 	const int	block = waves * 64;
 	const size_t	lds = size_t( b.image_bytes ) + RMS_LDS_TABLES + size_t( waves ) * size_t( rms_wave_bytes( b.stack, b.n_vars ) );
-	hipLaunchKernelGGL( rma_score_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
+	if( b.text_kernel ){
+		if( b.heap_cap < 0 || ( b.heap_cap > 0 && b.heap == nullptr ) || ( b.col != nullptr && ( b.col_stride < 1 || b.col_len == nullptr ) ) )
+			return hipErrorInvalidValue;
+		hipLaunchKernelGGL( rma_score_text_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
+	}else
+		hipLaunchKernelGGL( rma_score_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
 	return hipGetLastError();
 }
 
-hipError_t score_kernel_attributes( int *private_bytes, int *static_lds, int *regs )
+size_t score_heap_bytes( long long n, int heap_cap )
+{
+	return size_t( ( n + 63 ) / 64 ) * 64 * size_t( ( heap_cap + 3 ) / 4 ) * 4;
+}
+
+hipError_t score_text_copy( uint8_t *dst, const uint8_t *src, const int32_t *len, long long n, int stride, hipStream_t s )
+{
+	if( n <= 0 || stride <= 0 )
+		return hipSuccess;
+	const long long	total = n * stride;
+	hipLaunchKernelGGL( rma_score_text_copy_kernel, dim3( unsigned( ( total + 255 ) / 256 ) ), dim3( 256 ), 0, s, dst, src, len, n, stride );
+	return hipGetLastError();
+}
+
+hipError_t score_kernel_attributes( int *private_bytes, int *static_lds, int *regs, bool text )
 {
 	hipFuncAttributes	a;
-	const hipError_t	e = hipFuncGetAttributes( &a, reinterpret_cast<const void *>( rma_score_kernel ) );
+	const hipError_t	e = hipFuncGetAttributes( &a, reinterpret_cast<const void *>( text ? rma_score_text_kernel : rma_score_kernel ) );
 	if( e == hipSuccess ){
 		*private_bytes = int( a.localSizeBytes );
 		*static_lds = int( a.sharedSizeBytes );

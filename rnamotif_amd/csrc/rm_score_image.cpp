@@ -4,6 +4,7 @@
 #include "rm_score_core.h"
 #include <atomic>
 #include <cstdarg>
+#include <cmath>
 #include <cstring>
 #include <map>
 
@@ -89,6 +90,12 @@ struct Builder {
 
 std::string score_image_make( const Descriptor &d, const rma_program_t &prog, ScoreImage *out, bool checked )
 {
+	return score_image_make_flags( d, prog, out, checked ? 1u : 0u );
+}
+
+std::string score_image_make_flags( const Descriptor &d, const rma_program_t &prog, ScoreImage *out, unsigned flags )
+{
+	const bool	checked = ( flags & 1u ) != 0, text = ( flags & 2u ) != 0;
 	static std::atomic<uint64_t>	serials{ 0 };
 	const char	*who = "the score section cannot run on the device: ";
 	for( int e = 0; e < prog.n_elems && !checked; e++ )
@@ -133,6 +140,7 @@ std::string score_image_make( const Descriptor &d, const rma_program_t &prog, Sc
 	if( score_id == nullptr || !( why = b.variable( score_id, &v ) ).empty() )
 		return std::string( who ) + ( score_id == nullptr ? "no SCORE" : why );
 	std::map<std::string, int>	file_ix;
+	std::vector<size_t>	marks;		// the MRK of every call and `in` that is open
 	for( size_t pc = 0; pc < pr.size(); pc++ ){
 		const Inst	&ip = pr[ pc ];
 		const std::string	at = fmt( "%s:%d ", ip.filename, ip.lineno );
@@ -142,18 +150,42 @@ std::string score_image_make( const Descriptor &d, const rma_program_t &prog, Sc
 			return std::string( who ) + at + "the =~ and !~ operators need the host's regular expressions";
 		case OP_HOLD : case OP_RLSE : case OP_FCL : case OP_HALT :
 			return std::string( who ) + at + "an instruction MAIN cannot hold";
-		case OP_SCL :
+		case OP_MRK :
+			marks.push_back( pc );
+			break;
+		case OP_INS :
+			if( !marks.empty() )
+				marks.pop_back();
+			break;
+		case OP_SCL : {
 			o.kind = RMS_K_INT;
 			o.a = ip.val.ival;
-			if( o.a == SC_SPRINTF )
+			const size_t	mark = marks.empty() ? pr.size() : marks.back();
+			if( !marks.empty() )
+				marks.pop_back();
+			// a format that is a constant of the pool: the first argument is one LDC, the next instruction pushes or calls
+			if( o.a == SC_SPRINTF && text && mark + 2 <= pc && pr[ mark + 1 ].op == OP_LDC && pr[ mark + 1 ].val.type == T_STRING &&
+				( mark + 2 == pc || pr[ mark + 2 ].op == OP_LDC || pr[ mark + 2 ].op == OP_LOD || pr[ mark + 2 ].op == OP_LDA || pr[ mark + 2 ].op == OP_MRK ) ){
+				const char	*f = static_cast<const char *>( pr[ mark + 1 ].val.pval );
+				for( const char *pp = f; ( pp = strchr( pp, '%' ) ) != nullptr; ){
+					const char	*epp = strpbrk( pp + 1, "bBdiouxXfeEgGcCsSpn%" );
+					if( epp == nullptr )
+						break;
+					if( strchr( "eEgG", *epp ) != nullptr )
+						return std::string( who ) + at + fmt( "sprintf(): the format '%s' holds %%%c, whose digits the host's C library chooses", f, *epp );
+					pp = epp + 1;
+				}
+			}
+			if( o.a == SC_SPRINTF && !text )
 				return std::string( who ) + at + "sprintf() formats text, which the host does";
-			if( o.a == SC_BITS )
+			if( o.a == SC_BITS && !text )
 				return std::string( who ) + at + "bits() is computed on the host";
 			if( o.a == SC_MISMATCHES_2 )
 				return std::string( who ) + at + "mismatches( string, pattern ) needs the host's regular expressions";
 			if( o.a < 0 || o.a >= N_SC || o.a == SC_MISMATCHES )
 				return std::string( who ) + at + "an unknown builtin";
 			break;
+		}
 		case OP_LDA :
 		case OP_LOD : {
 			const Ident	*idp = static_cast<const Ident *>( ip.val.pval );
@@ -305,6 +337,16 @@ std::string score_image_make( const Descriptor &d, const rma_program_t &prog, Sc
 	place( &h.o_efn, sites.size() * sizeof( rma_efn_site_t ) );
 	place( &h.o_pool, b.pool.size() );
 	h.bytes = int32_t( at );
+	if( text ){
+		// the largest span two elements can enclose: every element at its longest, the contexts too
+		int64_t	L = 0;
+		for( int e = 0; e < prog.n_elems; e++ )
+			L += std::max( 0, prog.elems[ e ].maxlen );
+		if( prog.has_lctx ) L += std::max( 0, prog.lctx.maxlen );
+		if( prog.has_rctx ) L += std::max( 0, prog.rctx.maxlen );
+		h.flags |= RMS_IMG_TEXT;
+		h.bits_L = int32_t( std::min<int64_t>( std::max<int64_t>( L, 1 ), RMS_BITS_MAX_L ) );
+	}
 	const int	wave = rms_wave_bytes( stack, h.n_vars );
 	if( h.bytes + RMS_LDS_TABLES + wave > RMS_LDS_BYTES )
 		return std::string( who ) + fmt( "an image of %d bytes and a wave's %d bytes of stack and variables leave no room for one wave in %d bytes of LDS",
@@ -326,6 +368,13 @@ std::string score_image_make( const Descriptor &d, const rma_program_t &prog, Sc
 	put( h.o_pool, b.pool.data(), b.pool.size() );
 	img.prog.reset( new rma_program_t );
 	memcpy( img.prog.get(), &prog, sizeof( rma_program_t ) );	// (every byte, padding too: rma_score_hits compares bytes)
+	if( text ){
+		// (the host VM's own expression, do_bits: its log10, its order of operations)
+		img.bits_tab.reserve( size_t( h.bits_L ) * size_t( h.bits_L + 1 ) / 2 );
+		for( int len = 1; len <= h.bits_L; len++ )
+			for( int b = 1; b <= len; b++ )
+				img.bits_tab.push_back( 3.32192809488736234789 * log10( 1.0 * b / len ) );
+	}
 	img.serial = ++serials;
 	return "";
 }
@@ -338,8 +387,8 @@ std::string score_stop_text( const ScoreImage &img, const RmsResult &r )
 	const int	l = in ? img.line_of[ size_t( r.pc ) ] : UNDEF;
 	const char	*wd = img.wdfname.c_str();
 	// (the rule's two string types are the VM's one)
-	auto vm_type = []( int t ){ return t == RMS_T_BSTR || t == RMS_T_DEAD ? int( T_STRING ) : t; };
-	auto who = []( int sc ){ return sc == RMS_SC_EFN ? "efn" : sc == RMS_SC_MISMATCHES_1 ? "mismatches" : sc == RMS_SC_MISPAIRS ? "mispairs" : "paired"; };
+	auto vm_type = []( int t ){ return t == RMS_T_BSTR || t == RMS_T_DEAD || t == RMS_T_HSTR ? int( T_STRING ) : t; };
+	auto who = []( int sc ){ return sc == RMS_SC_BITS ? "bits" : sc == RMS_SC_EFN ? "efn" : sc == RMS_SC_MISMATCHES_1 ? "mismatches" : sc == RMS_SC_MISPAIRS ? "mispairs" : "paired"; };
 	switch( r.stop ){
 	case RMS_STOP_BUDGET : return fmt( "%s:%d more than %d instructions for one record (option score_budget).", f, l, r.a0 );
 	case RMS_STOP_TYPE : return fmt( "%s:%d type mismatch.", f, l );
@@ -387,6 +436,35 @@ std::string score_stop_text( const ScoreImage &img, const RmsResult &r )
 	case RMS_STOP_PAIRED_SS : return "paired() does not accept descr type 'ss'.";
 	case RMS_STOP_SUBSTR_POS : return fmt( "%s:%d substr: bad positiion %d, must be between 1 and %d.", f, l, r.a0, r.a1 );
 	case RMS_STOP_SUBSTR_LEN : return fmt( "%s:%d substr: bad len %d, must be >= 1.", f, l, r.a0 );
+	case RMS_STOP_HEAP :
+		return fmt( "%s:%d a string of %d bytes does not fit a record's heap: %d of its %d bytes are in use (option score_heap).", f, l, r.a0, r.a2, r.a1 );
+	case RMS_STOP_TEXT_ROOM : return fmt( "%s:%d the score column has %d bytes, a row of the text has room for %d (text_stride).", f, l, r.a0, r.a1 );
+	case RMS_STOP_TEXT_RANGE : return fmt( "%s:%d SCORE is not finite or not below 2^63: %%8.3lf of it is not written alike on host and device.", f, l );
+	case RMS_STOP_SPF_FIRST : return fmt( "%s:%d sprintf: first argument must be a format string.", f, l );
+	case RMS_STOP_SPF_BAD : {
+		std::string	rest = "(a string made for the record)";
+		if( r.a0 == RMS_T_STRING && r.a1 >= 0 && r.a2 >= 0 && r.a1 + r.a2 <= m->n_pool )
+			rest.assign( reinterpret_cast<const char *>( rms_pool( m ) ) + r.a1, size_t( r.a2 ) );
+		return fmt( "%s:%d sprintf: bad format '%s'.", f, l, rest.c_str() );
+	}
+	case RMS_STOP_SPF_STAR : return fmt( "%s:%d sprintf: '*' and '$' in formats are not supported by this build.", f, l );
+	case RMS_STOP_SPF_NO_ARG : return fmt( "%s:%d No such argument %d.", f, l, r.a0 );
+	case RMS_STOP_SPF_NEED_FLOAT : return fmt( "%s:%d '%c' format requires float arg.", f, l, r.a0 );
+	case RMS_STOP_SPF_NEED_INT : return fmt( "%s:%d '%c' format requires int arg.", f, l, r.a0 );
+	case RMS_STOP_SPF_NEED_STRING : return fmt( "%s:%d '%c' format requires string/seq arg.", f, l, r.a0 );
+	case RMS_STOP_SPF_UNSUPPORTED : return fmt( "%s:%d '%c' unsupported format.", f, l, r.a0 );
+	case RMS_STOP_SPF_EG : return fmt( "%s:%d sprintf: '%c' format: its digits are the host's C library's, the device writes %%f only.", f, l, r.a0 );
+	case RMS_STOP_SPF_MODIFIER : return fmt( "%s:%d sprintf: '%c' format with something else than flags, a width and a precision.", f, l, r.a0 );
+	case RMS_STOP_SPF_PREC : return fmt( "%s:%d sprintf: a precision of %d, the device writes at most %d digits behind the point.", f, l, r.a0, int( RMS_FMT_MAX_PREC ) );
+	case RMS_STOP_SPF_RANGE : return fmt( "%s:%d sprintf: 'f' format of a float that is not finite or not below 2^63.", f, l );
+	case RMS_STOP_BITS_POS1_NEG : return fmt( "%s:%d bits: bad pos1 %d, must be > 0.", f, l, r.a0 );
+	case RMS_STOP_BITS_LEN1 : return fmt( "%s:%d bits: descr1 must have match len > 0.", f, l );
+	case RMS_STOP_BITS_POS1_BIG : return fmt( "%s:%d bits: bad pos1 %d, must be <= %d.", f, l, r.a0, r.a1 );
+	case RMS_STOP_BITS_ORDER : return fmt( "%s:%d bits: bad 2nd descr index %d, must follow 1st descr index %d.", f, l, r.a0, r.a1 );
+	case RMS_STOP_BITS_POS2_NEG : return fmt( "%s:%d bits: bad pas2 %d, must be > 0", f, l, r.a0 );
+	case RMS_STOP_BITS_LEN2 : return fmt( "%s:%d bits: descr2 must have match len > 0.", f, l );
+	case RMS_STOP_BITS_POS2_BIG : return fmt( "%s:%d bits: bad pos2 %d, must be <= %d.", f, l, r.a0, r.a1 );
+	case RMS_STOP_BITS_SPAN : return fmt( "%s:%d bits() over %d bases, the table of its logarithms ends at %d.", f, l, r.a0, r.a1 );
 	default :
 		return fmt( "%s:%d the image holds what the rule does not run (stop %d, %d).", f, l, r.stop, r.a0 );
 	}

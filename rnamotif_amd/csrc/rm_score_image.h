@@ -65,7 +65,12 @@ struct RmsImage {
 	int32_t	sym_se, sym_ss;	// SYM_SE, SYM_SS
 	int32_t	v_score, v_comp, v_pos, v_len, v_slen;	// variables of these names, or -1
 	int32_t	o_inst, o_dbl, o_vars, o_xd, o_rows, o_ps, o_efn, o_pool;
+	int32_t	flags;		// RMS_IMG_*
+	int32_t	bits_L;		// bits() reads at most this many bases: its table (ScoreImage::bits_tab) ends there
 };
+// the image may hold sprintf() and bits(); string + concatenates; a lane has a heap (rm_score_core.h)
+#define RMS_IMG_TEXT	1
+enum { RMS_BITS_MAX_L = 1024, RMS_DEFAULT_HEAP = 256 };
 
 // bytes of LDS a wave's planes take: three words a stack slot and variable, a byte a slot of the element stack
 constexpr int rms_wave_bytes( int stack, int n_vars ) { return ( stack + n_vars ) * 3 * 64 * 4 + RMS_ESTK * 64; }
@@ -91,12 +96,18 @@ struct ScoreImage {
 	std::unique_ptr<rma_program_t>	prog;		// the descriptor's program: a scanner's must be the same, byte for byte
 	uint64_t	serial = 0;			// of this image among all that were made (a scanner keeps the last one's on its device)
 	int	deepest = 0;				// the deepest operand stack MAIN can reach
+	// RMS_IMG_TEXT: 3.32192809488736234789 * log10( 1.0 * b / len ) at ( len - 1 ) * len / 2 + b - 1 for 1 <= b <= len <= bits_L,
+	// by this host's log10 in the host VM's expression (do_bits); a scanner uploads it behind the image
+	std::vector<double>	bits_tab;
 };
 
 // The image of d's MAIN program, made from a private copy of d compiled as ParallelReplayer compiles its workers'
 // (BEGIN run on the copy; d itself untouched).  Returns "" or, with no image made, why not.  checked: a loose descriptor
 // is not refused -- the caller's records have passed rma_seqcheck_hits (rm_seqcheck.h) and are its fixed rows.
 std::string	score_image_make( const Descriptor &d, const rma_program_t &prog, ScoreImage *out, bool checked = false );
+// the same by flags (RMA_SCORE_CHECKED 1: as checked; RMA_SCORE_TEXT 2: sprintf() and bits() are not refused, the image has
+// RMS_IMG_TEXT and its table; a constant format with %e %E %g %G is refused)
+std::string	score_image_make_flags( const Descriptor &d, const rma_program_t &prog, ScoreImage *out, unsigned flags );
 // the host VM's words for a stop
 std::string	score_stop_text( const ScoreImage &img, const RmsResult &r );
 
