@@ -241,6 +241,12 @@ int	rma_scan_device( rma_scanner_t *sc, const rma_db_t *db, int64_t *n_hits, flo
  * drain kernel that walked the items the search kernel left in its list (0: the search kernel walked
  * them itself), ms[2] the efn kernel (0: none).  search_ms above is ms[0] + ms[1]. */
 int	rma_scanner_last_kernel_ms( rma_scanner_t *sc, float ms[ 3 ], char *err, size_t errlen );
+/* The shape of the scanner's last search launch: out[0] workgroups of the search kernel, out[1] bytes of
+ * dynamic LDS a workgroup, out[2] workgroups of the drain kernel behind it (0: none), out[3] 1 when the
+ * shape was chosen to leave another scanner's drain kernel room on every CU (option "beside": -1, the
+ * default, when another scanner of the device has a scan in flight as this one begins; 0 never; 1 always).
+ * All 0 before the first launch.  Returns 0. */
+int	rma_scanner_last_launch( rma_scanner_t *sc, int out[ 4 ] );
 
 /* Records from several scans (the slices of one database searched by several GPUs or hosts, word 0
  * already the database-wide entry number) into the reference's output order: by the five header

@@ -123,6 +123,8 @@ def lib() -> C.CDLL:
     L.rma_db_bases.restype = C.c_int64
     L.rma_scan.argtypes = [vp, vp, C.POINTER(i32p), i64p, C.c_char_p, C.c_size_t]
     L.rma_scanner_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
+    if hasattr(L, "rma_scanner_last_launch"):       # (RNAMOTIF_AMD_LIB may name a build from before the call: comparisons in turns)
+        L.rma_scanner_last_launch.argtypes = [vp, C.POINTER(C.c_int)]
     L.rma_scan_device.argtypes = [vp, vp, i64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                   C.c_char_p, C.c_size_t]
     L.rma_replay_open.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_size_t]
@@ -1095,6 +1097,13 @@ class Scanner:
         err = C.create_string_buffer(_ERRLEN)
         _check(lib().rma_scanner_last_kernel_ms(self._h, ms, err, _ERRLEN), err)
         return ms[0], ms[1], ms[2]
+
+    def last_launch(self) -> Tuple[int, int, int, int]:
+        """(search workgroups, bytes of dynamic LDS a workgroup, drain workgroups, beside) of the last search launch
+        (rma_scanner_last_launch); beside is 1 when the shape leaves another scanner's drain kernel room."""
+        out = (C.c_int * 4)()
+        lib().rma_scanner_last_launch(self._h, out)
+        return out[0], out[1], out[2], out[3]
 
     def close(self) -> None:
         if getattr(self, "_seq_check", None) is not None:

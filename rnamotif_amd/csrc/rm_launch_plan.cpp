@@ -25,6 +25,7 @@ void Options::latch()
 	glist = env_int( "RNAMOTIF_GLIST", 0 );
 	drain_waves = env_int( "RNAMOTIF_DRAIN_WAVES", 6 );
 	search_wgs = env_int( "RNAMOTIF_SEARCH_WGS", 0 );
+	set( "beside", env_int( "RNAMOTIF_BESIDE", -1 ) );
 	struct_wgs = std::max( 0, env_int( "RNAMOTIF_STRUCT_WGS", 0 ) );
 	flush = env_int( "RNAMOTIF_FLUSH", -1 );
 	efn_light = env_int( "RNAMOTIF_EFN_LIGHT", -1 );
@@ -50,6 +51,7 @@ bool Options::set( const std::string &n, int value )
 	else if( n == "glist" ) glist = std::max( 0, value );
 	else if( n == "drain_waves" ) drain_waves = std::max( 0, value );
 	else if( n == "search_wgs" ) search_wgs = std::max( 0, value );
+	else if( n == "beside" ) beside = value < 0 ? -1 : value != 0;
 	else if( n == "struct_wgs" ) struct_wgs = std::max( 0, value );
 	else if( n == "score_budget" ) score_budget = std::max( 1, value );
 	else if( n == "score_heap" ) score_heap = std::min( std::max( 0, value ), 1 << 16 );
@@ -364,6 +366,34 @@ void make_tiling( const LayoutKey &k, const std::vector<int32_t> &slen, const st
 	}
 }
 
+// The instance that walks nothing, shaped so that the drain kernel of ANOTHER scanner's scan is sure of room beside it
+// (option beside; two scanners that take the steps in turns).  Capping the grid at four workgroups a CU is not enough:
+// at the hand-over two such kernels are in flight, five workgroups of any mix fit a CU, and a SIMD with five of their
+// waves has 512 - 5 * 88 = 72 registers left where a drain wave needs 128 -- the grid is persistent, so such a CU is
+// closed to the drain kernel for the whole launch.  So the dynamic LDS is padded until five do NOT fit, which holds for
+// any mix of kernels planned this way, and the drain kernel gets as many waves a CU as find LDS beside four of them,
+// one a SIMD at most (4 * 96 + 128 registers).  Instance, tiles and layout key stay: the kernel lays out its LDS from
+// tile_bytes and prog_bytes and never asks how much there is, and both shapes share the database's tiling.
+static void plan_beside( const Options &o, int cus, LaunchPlan *out )
+{
+	LaunchPlan	&p = *out;
+	const size_t	cu_lds = 160 * 1024, SEARCH_STATIC_LDS = 1152;
+	const int	wgs = FLUSH_WGS_PER_CU - 1;
+	const size_t	lds = std::max( p.lds, ( cu_lds / FLUSH_WGS_PER_CU / 64 + 1 ) * 64 );	// (the instance's own, where that is more than a fifth already)
+	// (what four of them take includes their static __shared__, the 1152 bytes plan_program() budgets for: three drain waves
+	// of trna.descr's 10 400 bytes fit beside 4 * 32 832 on paper, two beside 4 * 33 984 on the device -- and a third that
+	// waits for room only shrinks the shares of the two that run: 0.637 against 0.619 ms a step)
+	const size_t	taken = wgs * ( lds + SEARCH_STATIC_LDS );
+	const size_t	left = cu_lds > taken ? cu_lds - taken : 0;
+	const int	n = int( std::min<size_t>( std::min( o.drain_waves > 0 ? o.drain_waves : 16, 4 ), left / ( p.drain_lds + 64 ) ) );
+	if( n < 2 )		// (no room worth the fifth workgroup: the solo shape)
+		return;
+	p.lds = lds;
+	p.grid = std::min( p.grid, wgs * cus );
+	p.drain_grid = cus * n;
+	p.beside = true;
+}
+
 int plan_launch( const LayoutKey &k, int64_t n_tiles, const ProgramPlan &pp, const Options &o, int cus, LaunchPlan *out,
 	char *err, size_t errlen )
 {
@@ -412,6 +442,8 @@ int plan_launch( const LayoutKey &k, int64_t n_tiles, const ProgramPlan &pp, con
 	// (behind the search instance that walks nothing: workgroups of one wave that find room next to another scanner's search
 	// kernel -- the staged form's 136 KB of LDS wait until that kernel is through)
 	p.efn_light = !dp.efn_big && ( o.efn_light < 0 ? p.walks_nothing : o.efn_light != 0 );
+	if( o.beside == 1 && p.walks_nothing )
+		plan_beside( o, cus, &p );
 	return 0;
 }
 

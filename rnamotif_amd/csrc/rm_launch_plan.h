@@ -21,10 +21,13 @@ struct Options {
 	int	drain = 1;		// pooled instance: the items are walked by a kernel of their own (0: by the workgroup that found them)
 	int	glist = 0;		// > 0: items of the drain kernel's list (tests: a list that overflows), 0: by the database's size
 	int	drain_waves = 6;	// workgroups (of one wave) of the drain kernel per CU; 0: what LDS and registers allow (16).  Six: the kernel alone
-				// is as fast as with 16 (profiles/overlap_try.py: 0.29 ms), and the next scan's search kernel starts beside it
+				// is as fast as with 16 (profiles/overlap_try.py: 0.29 ms).  (Five search workgroups a CU leave a SIMD 72 registers and
+				// this kernel needs 128: it starts beside another scanner's search kernel only under a plan made for that -- `beside`)
 	int	flush = -1;		// pooled instance that walks nothing (RMK_LEAN_FLUSH): -1 where the descriptor has a look-ahead chain, 0 never, 1 wherever the pooled instance runs
 	int	efn_light = -1;		// the energy kernel in workgroups of one wave that stage no tables (rma_efn_light_kernel): -1 by the scan's instance, 0 never, 1 always
 	int	search_wgs = 0;		// > 0: workgroups of a lean search kernel per CU (fewer than fit: another scanner's drain kernel runs beside it)
+	int	beside = -1;		// the instance that walks nothing, planned so that another scanner's drain kernel is sure of room beside it (plan_beside):
+				// -1 when another scanner of the device has a scan in flight (rma_scan_begin resolves it), 0 never, 1 always; plan_launch reads 1 as on
 	int	struct_wgs = 0;		// > 0: workgroups of the kernels of rma_structure_energies (tests: a grid-stride loop over a few hundred structures)
 	int	score_budget = 1 << 20;	// instructions of the score section a record of rma_score_hits may take before it stops (RMS_DEFAULT_BUDGET)
 	int	score_heap = 256;	// bytes of heap a record of a score program with text has for the strings it makes (RMS_DEFAULT_HEAP)
@@ -100,6 +103,7 @@ struct LaunchPlan {
 	bool	listed = false;		// the instance hands items to the drain kernel's list
 	bool	walks_nothing = false;	// ... all of them (RMK_LEAN_FLUSH, RMK_LEAN_CONCAT_FLUSH)
 	bool	efn_light = false;	// the energy kernel behind it is rma_efn_light_kernel
+	bool	beside = false;		// grid, lds and drain_grid leave another scanner's drain kernel room on every CU (option beside)
 };
 // 1 and err: the scan cannot be launched
 int	plan_launch( const LayoutKey &k, int64_t n_tiles, const ProgramPlan &pp, const Options &o, int cus, LaunchPlan *out,

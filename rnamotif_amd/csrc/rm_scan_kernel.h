@@ -701,6 +701,12 @@ __global__ void __launch_bounds__( BLOCK, DRAIN_WAVES_PER_SIMD )
 rma_drain_kernel( const rmd_program_t *gP, int prog_bytes, DbView db, HitBuf hb, int n_nib, int dbg )
 {
 	static_assert( BLOCK == 64, "one wave per workgroup" );
+	// This kernel's time is the chain of instructions of its slowest waves.  Beside another scanner's search kernel
+	// (rm_launch_plan.cpp: plan_beside) its waves are the youngest on their SIMDs, and a SIMD issues by priority, then
+	// age: at the search waves' priority 0 they would live on the slots those leave.  (A scalar instruction, once a wave.)
+	// Measured under the beside shape, the same build without this line: 0.664 against 0.619 ms a step, the drain kernel
+	// 0.40 against 0.34 ms; without guaranteed room it decides nothing.
+	__builtin_amdgcn_s_setprio( 3 );
 	extern __shared__ __align__( 16 ) unsigned char	smem[];
 	rmd_program_t	*P = reinterpret_cast<rmd_program_t *>( smem );
 	const int	tid = threadIdx.x, lane_id = tid & 63;
@@ -2575,6 +2581,9 @@ __global__ void __launch_bounds__( 64, 4 )
 rma_efn_light_kernel( const rmd_program_t *gP, DbView db, int32_t *hits, long long n_hits,
 	const int16_t *g16, const int32_t *tlkey, const int32_t *loginc, const rma_efn2data_t *e2 )
 {
+	// (like the drain kernel in front of it on the stream it runs beside another scanner's search kernel, the youngest wave
+	// on its SIMD: at priority 3 it takes 0.147 against 0.18 ms there and the step of two scanners in turns 0.605 against 0.619)
+	__builtin_amdgcn_s_setprio( 3 );
 	efn_body<64, BIG, false>( gP, db, hits, n_hits, g16, tlkey, loginc, e2 );
 }
 

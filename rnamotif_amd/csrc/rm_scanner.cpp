@@ -289,7 +289,7 @@ extern "C" int rma_scanner_set_option( rma_scanner_t *sc, const char *name, int 
 		sc->last_relabelled = false;
 	}else if( !sc->opt.set( n, value ) ){
 		snprintf( err, errlen, "rma_scanner_set_option: no option '%s' that can change after creation "
-			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, struct_wgs, score_budget, score_heap, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
+			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, beside, struct_wgs, score_budget, score_heap, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
 		return 1;
 	}
 	return 0;
@@ -1111,6 +1111,10 @@ static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
 	HIPCHK( hipEventRecord( sc->ev[ 0 ].get(), sc->stream.get() ) );
 	HIPCHK( rmk_launch_search( f.plan.inst, f.plan.grid, f.plan.lds, sc->stream.get(), a ) );
 	sc->drained = drain;
+	sc->last_launch[ 0 ] = f.plan.grid;
+	sc->last_launch[ 1 ] = int( f.plan.lds );
+	sc->last_launch[ 2 ] = drain ? f.plan.drain_grid : 0;
+	sc->last_launch[ 3 ] = int( f.plan.beside );
 	sc->searched = true;
 	sc->efn_ran = false;
 	if( drain ){	// the items the search kernel left in the list: walked by a kernel of their own
@@ -1171,13 +1175,19 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 			std::lock_guard<std::mutex>	lk( mdb->mu );
 			mdb->busy.erase( std::find( mdb->busy.begin(), mdb->busy.end(), sc ) );
 			sc->fly.db = nullptr;
+			sc->flying.lower();
 		} } }	unfly{ sc, true };
 	f.plan = rma::LaunchPlan();
 	if( lay->n_tiles == 0 ){
 		unfly.armed = false;
 		return 0;
 	}
-	if( rma::plan_launch( *lay, lay->n_tiles, sc->plan, sc->opt, sc->grid_blocks / 8, &f.plan, err, errlen ) )
+	// (option beside at -1: room for the other scanner's drain kernel when another scanner of this device has a scan in
+	// flight -- two scanners taking the steps in turns, from the second step on; this scan is not counted yet.  The shape
+	// holds for the scan: search_finish()'s repeat launches read f.plan)
+	rma::Options	opt = sc->opt;
+	opt.beside = opt.beside < 0 ? rma::flights( sc->device ) > 0 : opt.beside;
+	if( rma::plan_launch( *lay, lay->n_tiles, sc->plan, opt, sc->grid_blocks / 8, &f.plan, err, errlen ) )
 		return 1;
 	if( f.plan.pooled ){
 		// The list of the drain kernel: room for an item per 32 bases (trna.descr leaves one per 70 before the
@@ -1196,6 +1206,7 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 	// the database's upload and the tiling's, on the device's upload stream, come first
 	HIPCHK( hipStreamWaitEvent( sc->stream.get(), db->ready.get(), 0 ) );
 	HIPCHK( hipStreamWaitEvent( sc->stream.get(), lay->ready.get(), 0 ) );
+	sc->flying.raise( sc->device );		// (nothing is left that can refuse the scan; a launch that fails lowers it again: unfly)
 	if( launch_search( sc, err, errlen ) )
 		return 1;
 	unfly.armed = false;
@@ -1302,6 +1313,7 @@ static int launch_efn( rma_scanner_t *sc, int64_t count, char *err, size_t errle
 
 static void scan_done( rma_scanner_t *sc )
 {
+	sc->flying.lower();
 	if( sc->fly.db == nullptr )
 		return;
 	rma_db	*mdb = const_cast<rma_db *>( sc->fly.db );
@@ -1353,6 +1365,16 @@ extern "C" int rma_scanner_last_kernel_ms( rma_scanner_t *sc, float ms[ 3 ], cha
 		HIPCHK( hipEventElapsedTime( &ms[ 0 ], sc->ev[ 0 ].get(), sc->ev[ 1 ].get() ) );
 	if( sc->efn_ran )
 		HIPCHK( hipEventElapsedTime( &ms[ 2 ], sc->ev[ 2 ].get(), sc->ev[ 3 ].get() ) );
+	return 0;
+}
+
+// The shape of the scanner's last search launch: out[ 0 ] workgroups asked for, out[ 1 ] bytes of dynamic LDS a workgroup,
+// out[ 2 ] workgroups of the drain kernel behind it (0: none), out[ 3 ] 1 when the shape leaves another scanner's drain
+// kernel room (option beside).  All 0 before the first launch.
+extern "C" int rma_scanner_last_launch( rma_scanner_t *sc, int out[ 4 ] )
+{
+	for( int i = 0; i < 4; i++ )
+		out[ i ] = sc->last_launch[ i ];
 	return 0;
 }
 

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "rm_hip_own.h"
+#include "rm_flight_count.h"
 #include "rm_launch_plan.h"
 #include "rm_hitsort.h"
 #include "rm_hitsort_dev.h"
@@ -110,6 +111,8 @@ struct rma_scanner {
 		const rma::Layout	*lay = nullptr;
 		rma::LaunchPlan	plan;
 	}	fly;
+	rma::FlightMark	flying;			// ... counted among its device's scans in flight (rm_flight_count.h), from its launch to scan_done()
+	int	last_launch[ 4 ] = { 0, 0, 0, 0 };	// grid, dynamic LDS, the drain kernel's grid and beside of the last search launch (rma_scanner_last_launch)
 	// what the last scan left on the device, in order (rma_scan_end): for rma_gather_hits()
 	const int32_t	*d_last = nullptr;
 	int64_t	n_last = 0;
