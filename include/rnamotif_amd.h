@@ -454,7 +454,9 @@ void	rma_score_close( rma_score_t *sp );
 /* What an image and its kernel take (profiles/score_device.py): info[ 0 ] bytes of the image, [ 1 ] instructions,
  * [ 2 ] variables, [ 3 ] slots of the operand stack, [ 4 ] bytes of LDS a wave's stack and variables take, [ 5 ] waves of
  * a workgroup, [ 6 ] bytes of dynamic LDS of a workgroup; from the runtime, -1 each where no device answers: [ 7 ] bytes
- * of private memory a lane of rma_score_kernel has, [ 8 ] its static LDS, [ 9 ] its registers. */
+ * of private memory a lane of rma_score_kernel has, [ 8 ] its static LDS, [ 9 ] its registers -- of the instance that
+ * would run the image: rma_score_text_kernel with RMA_SCORE_TEXT, rma_score_match_kernel / rma_score_match_text_kernel
+ * for a program opened with RMA_SCORE_MATCH that has a pattern, whose [ 4 ] and [ 6 ] then hold the matcher's stack too. */
 void	rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] );
 /* rma_score_hits(): MAIN on each of the n_hits records at d_hits, one record per lane.  d_accept[ h ] = 1 where record h
  * is a hit (ACCEPT, or MAIN's end is never reached without one), 0 where MAIN rejects it; d_score[ h ] the SCORE the
@@ -531,9 +533,23 @@ int	rma_score_open_checked( const rma_descr_t *d, rma_score_t **out, char *err, 
  * argument type, no such argument, an unsupported conversion -- stops the record, as do '*', '$' and length modifiers,
  * %e %E %g %G (refused when the program is opened where the format is a constant), a larger precision and a double %f
  * cannot write.  bits() reads the host's own logarithms from a table made when the program is opened, for windows of up
- * to L bases -- the sum of the elements' greatest lengths, at most 1024; a longer window stops the record. */
+ * to L bases -- the sum of the elements' greatest lengths, at most 1024; a longer window stops the record.
+ * With RMA_SCORE_MATCH the refusals of =~, !~ and mismatches( string, pattern ) fall, in any combination with the other
+ * two flags: the pattern of each is compiled when the program is opened (compile() of the reference's regexp.c, as
+ * rma_seqcheck_open() compiles a loose seq=) and applied to each record's string by the reference's step() / advance() /
+ * mm_step(), the rule of csrc/rm_seqcheck.h, whose stack lives in LDS beside the program's.  Refused when opened, each
+ * with file and line: a pattern that is not one string constant (a variable, an element reference, sprintf(), string +:
+ * it would have to be compiled for every record), a constant compile() rejects (the words name it and the regerr
+ * code; "" alone opens, and matches nothing, as on the host), more than 32 patterns, more than 255 ops in one, an image
+ * that with the matcher's stack leaves no room for one wave in 64 KB of LDS.  NAME, HOLD / RELEASE and a variable
+ * carried from hit to hit stay refused.  =~ on something that is no string stops the record with the host VM's word,
+ * "typemismatch."; every op the matcher visits counts against option "score_budget" with the instructions, so that a
+ * backtracking pattern over a long made string holds the device no longer than a loop may.  Without the flag every
+ * refusal keeps its words, and a program opened with it that has no such pattern runs the kernels it ran. */
 #define RMA_SCORE_CHECKED 1u   /* as rma_score_open_checked() */
 #define RMA_SCORE_TEXT    2u   /* sprintf(), bits(), string +, a string in SCORE */
+/* (8, not 4: bit 4 stays refused, "flags other than ...", as callers and tests of rma_score_open_flags() know it) */
+#define RMA_SCORE_MATCH   8u   /* =~, !~ and mismatches( string, pattern ) with a constant pattern */
 int	rma_score_open_flags( const rma_descr_t *d, unsigned flags, rma_score_t **out, char *err, size_t errlen );
 /* rma_score_hits() with the score column as bytes.  Row h of d_text (text_stride bytes a row) is the field
  * HitPrinter::print writes behind the one blank after the name: %8d of an int SCORE, %8.3lf of a float or of none, %8s

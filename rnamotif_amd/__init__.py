@@ -475,33 +475,40 @@ class ScoreProgram:
     """The MAIN program of a descriptor's score section as an image the GPU runs, one record per lane
     (rma_score_open; Scanner.score() takes it).  Raises RnamotifError with the reason where the program cannot be
     judged record by record on the device: HOLD / RELEASE or a variable carried from one hit to the next, sprintf(),
-    bits(), mismatches( string, pattern ), =~ / !~, a read of NAME, a loose descriptor, an image beyond the limits of
-    csrc/rm_score_image.h.  The descriptor itself is not touched: the image is made from a private copy.
+    bits() (without text=True), mismatches( string, pattern ), =~ / !~ (without match=True), a read of NAME, a loose
+    descriptor (without checked=True), an image beyond the limits of csrc/rm_score_image.h.  The descriptor itself is not touched: the image is made from a private copy.
     checked=True (rma_score_open_checked) opens a loose descriptor too: the caller promises to score only
     r.hits[r.keep] of r = Scanner.seq_check(db, hits), the records that are rnamotif's candidates, as fixed rows.
     text=True (rma_score_open_flags with RMA_SCORE_TEXT) opens a program with sprintf(), bits(), string + and a string
     in SCORE: the rule then makes strings in a heap of option "score_heap" bytes a record, writes printf's %d %s %f
     with the host's bytes and reads bits()'s logarithms from a table made here; %e %E %g %G in a constant format is
-    refused.  Scanner.score(..., text=True) delivers the score column of such a program."""
+    refused.  Scanner.score(..., text=True) delivers the score column of such a program.
+    match=True (RMA_SCORE_MATCH, with either of the others) opens a program with =~, !~ and mismatches( string, pattern )
+    whose patterns are string constants: each is compiled here, once, and applied to every record's string by the
+    reference's matcher in LDS (csrc/rm_seqcheck.h), its steps counted against option "score_budget".  A pattern from a
+    variable, an element reference or sprintf(), one the reference's compile() rejects, more than 32 patterns are
+    refused; NAME and HOLD / RELEASE stay refused.  info() reports the kernel that would run: a program without a
+    pattern runs what it runs without the flag."""
 
-    def __init__(self, descr: Descriptor, checked: bool = False, text: bool = False):
+    def __init__(self, descr: Descriptor, checked: bool = False, text: bool = False, match: bool = False):
         h = C.c_void_p()
         err = C.create_string_buffer(_ERRLEN)
         L = lib()
-        if text:
-            _check(L.rma_score_open_flags(descr._h, (1 if checked else 0) | 2, C.byref(h), err, _ERRLEN), err)
+        if text or match:
+            _check(L.rma_score_open_flags(descr._h, (1 if checked else 0) | (2 if text else 0) | (8 if match else 0), C.byref(h), err, _ERRLEN), err)
         else:
             _check((L.rma_score_open_checked if checked else L.rma_score_open)(descr._h, C.byref(h), err, _ERRLEN), err)
         self._h = h
         self.descr = descr
         self.checked = bool(checked)
         self.text = bool(text)
+        self.match = bool(match)
 
     @staticmethod
-    def reason(descr: Descriptor, checked: bool = False, text: bool = False) -> Optional[str]:
-        """Why ScoreProgram(descr, checked, text) would refuse, or None where it opens."""
+    def reason(descr: Descriptor, checked: bool = False, text: bool = False, match: bool = False) -> Optional[str]:
+        """Why ScoreProgram(descr, checked, text, match) would refuse, or None where it opens."""
         try:
-            ScoreProgram(descr, checked, text).close()
+            ScoreProgram(descr, checked, text, match).close()
         except RnamotifError as e:
             return str(e)
         return None

@@ -147,10 +147,10 @@ extern "C" int rma_score_open_checked( const rma_descr_t *d, rma_score_t **out, 
 
 extern "C" int rma_score_open_flags( const rma_descr_t *d, unsigned flags, rma_score_t **out, char *err, size_t errlen )
 {
-	if( flags & ~( RMA_SCORE_CHECKED | RMA_SCORE_TEXT ) ){
+	if( flags & ~( RMA_SCORE_CHECKED | RMA_SCORE_TEXT | RMA_SCORE_MATCH ) ){
 		if( out != nullptr )
 			*out = nullptr;
-		return set_err( err, errlen, "rma_score_open_flags: flags other than RMA_SCORE_CHECKED and RMA_SCORE_TEXT" );
+		return set_err( err, errlen, "rma_score_open_flags: flags other than RMA_SCORE_CHECKED, RMA_SCORE_TEXT and RMA_SCORE_MATCH" );
 	}
 	return score_open( d, out, flags, "rma_score_open_flags: no descriptor", err, errlen );
 }

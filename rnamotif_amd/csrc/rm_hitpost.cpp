@@ -885,7 +885,8 @@ static int score_hits( const char *who, bool text_call, rma_scanner_t *sc, const
 				return 1;
 			}
 	const RmsImage	*m = sp->img.image();
-	if( rma::score_waves( m->bytes, m->stack, m->n_vars ) < 1 ){
+	const int	frames = rms_frames( m );	// (>= 0: an image with expressions, which runs the match kernels)
+	if( rma::score_waves( m->bytes, m->stack, m->n_vars, frames ) < 1 ){
 		snprintf( err, errlen, "%s: the image leaves no room for a wave", who );
 		return 1;
 	}
@@ -948,6 +949,10 @@ static int score_hits( const char *who, bool text_call, rma_scanner_t *sc, const
 				b.col_len = text_len + c0;
 			}
 		}
+		if( frames >= 0 ){
+			b.match_kernel = 1;
+			b.frames = frames;
+		}
 		return b;
 	};
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
@@ -1000,7 +1005,8 @@ extern "C" void rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] )
 		return;
 	}
 	const RmsImage	*m = sp->img.image();
-	const int	waves = rma::score_waves( m->bytes, m->stack, m->n_vars ), wave = rms_wave_bytes( m->stack, m->n_vars );
+	const int	frames = rms_frames( m );
+	const int	waves = rma::score_waves( m->bytes, m->stack, m->n_vars, frames ), wave = rms_wave_bytes( m->stack, m->n_vars, frames );
 	info[ 0 ] = m->bytes;
 	info[ 1 ] = m->n_inst;
 	info[ 2 ] = m->n_vars;
@@ -1009,7 +1015,7 @@ extern "C" void rma_score_info( const rma_score_t *sp, int32_t info[ 10 ] )
 	info[ 5 ] = waves;
 	info[ 6 ] = m->bytes + RMS_LDS_TABLES + waves * wave;
 	int	priv = -1, lds = -1, regs = -1;
-	if( rma::score_kernel_attributes( &priv, &lds, &regs, ( m->flags & RMS_IMG_TEXT ) != 0 ) != hipSuccess )
+	if( rma::score_kernel_attributes( &priv, &lds, &regs, ( m->flags & RMS_IMG_TEXT ) != 0, frames >= 0 ) != hipSuccess )
 		( void )hipGetLastError();
 	info[ 7 ] = priv;
 	info[ 8 ] = lds;

@@ -21,6 +21,15 @@
 // writes: %8d, %8.3lf or %8s.  Every directive on which the host VM only notes an error stops here.  rms_run_t< false >
 // is the rule without any of this, what rms_run() is.
 //
+// An image opened with RMS_IMG_MATCH holds =~ / !~ (MAT; !~ is MAT and NOT) and mismatches( string, pattern ), each with
+// the index of an expression the image has compiled (RmsMatch): rms_run_t< TEXT, true > runs do_mat and the builtin through
+// rmq_step() and rmq_mm_step() of rm_seqcheck.h -- the reference's step(), advance() and mm_step() -- over the left
+// operand, a string of any of the three types read through an accessor that ends it with a 0 at its length and reads
+// nothing behind it.  The pattern on the stack is the constant the expression was compiled from and is not read.  The
+// matcher's frames and its bra[] / ket[] are planes of their own (RmsMem::mq: an RmqMem); every op it visits counts
+// against the record's budget with the instructions.  MAT on something that is no string stops with the host VM's word
+// for it, "typemismatch.".
+//
 // Where the host VM would read what it has freed or never wrote -- a string slot after && / || / ! (its pointer's low
 // word is overwritten), substr() of something that is no string, $ on an entry of rm_xdescr behind rm_descr's end --
 // the rule stops with "type mismatch" or the $ stop.  The value an assignment leaves on the stack is the host's
@@ -111,6 +120,8 @@ enum {
 	RMS_STOP_BITS_POS1_NEG, RMS_STOP_BITS_LEN1, RMS_STOP_BITS_POS1_BIG, RMS_STOP_BITS_ORDER, RMS_STOP_BITS_POS2_NEG, RMS_STOP_BITS_LEN2,
 	RMS_STOP_BITS_POS2_BIG,
 	RMS_STOP_BITS_SPAN,		// a0: bases, a1: the table's L
+	// an image with RMS_IMG_MATCH
+	RMS_STOP_MAT_TYPE,		// =~ / !~ on something that is no string: "typemismatch."
 	RMS_N_STOP
 };
 
@@ -146,6 +157,8 @@ template< int STRIDE > struct RmsMem {
 	int	stack, n_vars;
 	uint8_t	*heap = nullptr;	// the lane's arena: byte k at ( k >> 2 ) * 4 * STRIDE + ( k & 3 )
 	int	heap_cap = 0;
+	int32_t	*mq = nullptr;		// the matcher's planes (RmqMem< STRIDE >, rm_seqcheck.h), mq_frames frames of them
+	int	mq_frames = 0;
 	static constexpr int	stride = STRIDE;
 	RMD_FN_MEMBER uint8_t	&HB( int k ) const { return heap[ ( ( k < 0 ? 0 : k >= heap_cap ? heap_cap - 1 : k ) >> 2 ) * 4 * STRIDE + ( k & 3 ) ]; }
 	RMD_FN_MEMBER int	slot( int k ) const { return k < 0 ? 0 : k >= stack ? stack - 1 : k; }
@@ -241,6 +254,15 @@ template< bool TEXT, class Mem, class Bases > struct RmsStr {
 	RMD_FN_MEMBER unsigned char	operator()( int i ) const { return rms_char_t<TEXT>( m, bases, mem, type, off, i ); }
 };
 
+// a string value as the matcher's text: byte k of the slice, 0 at its length and wherever else it is asked
+template< bool TEXT, class Mem, class Bases > struct RmsMatchText {
+	const RmsImage	*m;
+	const Bases	&bases;
+	const Mem	&mem;
+	int	type, off, len;
+	RMD_FN_MEMBER int	operator()( int k ) const { return unsigned( k ) < unsigned( len ) ? int( rms_char_t<TEXT>( m, bases, mem, type, off, k ) ) : 0; }
+};
+
 // where a row of the element table has its offset and length in the record
 RMD_FN int rms_row_word( const RmsImage *m, int row )
 {
@@ -249,7 +271,7 @@ RMD_FN int rms_row_word( const RmsImage *m, int row )
 
 // The rule.  w: the record; slen: its entry's length; bases( i ): the letter at position i of the record's strand;
 // mem: the lane's planes, sized for m->stack slots and m->n_vars variables.
-template< bool TEXT, class Mem, class Bases >
+template< bool TEXT, bool MATCH = false, class Mem, class Bases >
 RMD_FN void rms_run_t( const RmsImage *m, const int32_t *w, int slen, const Bases &bases, const Mem &mem, int budget, RmsResult *r, const RmsText &tx )
 {
 	const bool	text = TEXT && ( m->flags & RMS_IMG_TEXT ) != 0;
@@ -431,6 +453,30 @@ RMD_FN void rms_run_t( const RmsImage *m, const int32_t *w, int slen, const Base
 				mem.T( sp ) = RMS_T_DEAD;
 			}else
 				RMS_STOP( RMS_STOP_TYPE, 0, 0, 0 );
+			break;
+		}
+		case RMS_OP_MAT : {		// do_mat
+			if( !MATCH || !( m->flags & RMS_IMG_MATCH ) || unsigned( ip.a ) >= unsigned( m->n_expr ) )
+				RMS_STOP( RMS_STOP_INTERNAL, 8, 0, 0 );
+			const int	top = sp--;
+			if( sp < 0 )
+				RMS_STOP( RMS_STOP_INTERNAL, 9, 0, 0 );
+			const int	t1 = mem.T( sp ), t2 = mem.T( top );
+			if( !( rms_is_string( t1 ) || t1 == RMS_T_DEAD ) || !( rms_is_string( t2 ) || t2 == RMS_T_DEAD ) )
+				RMS_STOP( RMS_STOP_MAT_TYPE, 0, 0, 0 );
+			if( t1 == RMS_T_DEAD )		// (the host reads a pointer && / || / ! overwrote)
+				RMS_STOP( RMS_STOP_TYPE, 0, 0, 0 );
+			const RmsMatchExpr	ex = rms_match_expr( m )[ ip.a ];
+			int	rv = 0;
+			if( ex.n_ops >= 0 ){
+				const RmsMatchText<TEXT, Mem, Bases>	text{ m, bases, mem, t1, mem.L( sp ), mem.H( sp ) };
+				const RmqMem<Mem::stride>	mq{ mem.mq, mem.mq_frames };
+				rv = rmq_step( rms_match_ops( m ) + ex.first, ex.n_ops, text, mq, ex.anchored != 0, budget, &steps );
+				if( rv < 0 )
+					RMS_STOP( RMS_STOP_BUDGET, budget, 0, 0 );
+			}
+			mem.T( sp ) = RMS_T_INT;
+			mem.L( sp ) = rv;
 			break;
 		}
 		case RMS_OP_INS : {		// do_ins
@@ -935,7 +981,22 @@ RMD_FN void rms_run_t( const RmsImage *m, const int32_t *w, int slen, const Base
 				hp += o.n;
 				break;
 			}
-			default :		// mismatches( string, pattern ): no image holds it
+			case RMS_SC_MISMATCHES_2 : {	// (the host takes both for strings unasked)
+				if( !MATCH || !( m->flags & RMS_IMG_MATCH ) || unsigned( ip.len ) >= unsigned( m->n_expr ) )
+					RMS_STOP( RMS_STOP_INTERNAL, 6, 0, 0 );
+				if( sp - 1 <= mp || !rms_is_string( mem.T( sp - 1 ) ) )
+					RMS_STOP( RMS_STOP_TYPE, 0, 0, 0 );
+				const RmsMatchExpr	ex = rms_match_expr( m )[ ip.len ];
+				int	n_mm = 0;
+				if( ex.n_ops >= 0 ){
+					const RmsMatchText<TEXT, Mem, Bases>	text{ m, bases, mem, mem.T( sp - 1 ), mem.L( sp - 1 ), mem.H( sp - 1 ) };
+					if( rmq_mm_step( rms_match_ops( m ) + ex.first, ex.n_ops, text, ex.anchored != 0, 20 * ex.pat_len, &n_mm, budget, &steps ) < 0 )
+						RMS_STOP( RMS_STOP_BUDGET, budget, 0, 0 );
+				}
+				rl = n_mm;
+				break;
+			}
+			default :		// no image holds it
 				RMS_STOP( RMS_STOP_INTERNAL, 6, 0, 0 );
 			}
 			if( mp < 0 )
@@ -947,7 +1008,7 @@ RMD_FN void rms_run_t( const RmsImage *m, const int32_t *w, int slen, const Base
 			mem.H( sp ) = rh;
 			break;
 		}
-		default :		// HALT, HOLD, RLSE, FCL, MAT: no image holds them
+		default :		// HALT, HOLD, RLSE, FCL: no image holds them
 			RMS_STOP( RMS_STOP_INTERNAL, 8, 0, 0 );
 		}
 	}

@@ -20,6 +20,13 @@
 //                      touch 64 consecutive dwords.  The table of bits() stays in global memory.  A lane writes its
 //                      row of the column itself; col_len[ h ] is the column's length, 0 for a record that is not accepted.
 //                      rma_score_kernel is compiled from the rule without any of this (rms_run_t< false >).
+//   rma_score_match_kernel, rma_score_match_text_kernel   the two above for an image with expressions (RMS_IMG_MATCH and
+//                      a =~, a !~ or a mismatches( string, pattern ) in MAIN): score_body< TEXT, true >, the rule with
+//                      do_mat and the builtin.  The expressions' ops come to LDS with the image.  A wave's planes are
+//                      followed by its matcher's (rmq_wave_bytes( frames ), rm_seqcheck.h: 18 words of bra[] and ket[]
+//                      and four words a frame, slot k of lane l at word k * 64 + l), so that the matcher's state, all of
+//                      it indexed at run time, is in LDS like the rest and no lane has private memory for it.  Every
+//                      other image runs the two kernels above, which are compiled from the rule without the matcher.
 //   rma_score_text_copy_kernel   bytes [ 0, len[ h ] ) of every row from the scratch to the caller's rows: what lies
 //                      behind a row's length is not written.
 #pragma once
@@ -57,6 +64,9 @@ struct ScoreBatch {
 	uint8_t	*col = nullptr;		// [ n, col_stride ] the score column, or null
 	int32_t	col_stride = 0;
 	int32_t	*col_len = nullptr;	// [ n ]
+	// an image with expressions: rma_score_match_kernel / rma_score_match_text_kernel
+	int32_t	match_kernel = 0;
+	int32_t	frames = 0;		// of the matcher's planes (rms_frames())
 };
 
 #if defined( __HIPCC__ )
@@ -75,12 +85,14 @@ struct ScoreBases {
 };
 #endif
 
-// waves of a workgroup: as many of 4 as RMS_LDS_BYTES hold next to the image (0: not one)
-int	score_waves( int image_bytes, int stack, int n_vars );
+// waves of a workgroup: as many of 4 as RMS_LDS_BYTES hold next to the image (0: not one); frames: of the matcher's planes
+// behind each wave's own (rms_frames()), < 0 for an image without expressions
+int	score_waves( int image_bytes, int stack, int n_vars, int frames = -1 );
 // Enqueue on s the rule over the batch's records.
 hipError_t	score_records( const ScoreBatch &b, hipStream_t s );
-// the kernel's private bytes, static LDS and registers as the runtime reports them (rma_score_info); text: the text kernel's
-hipError_t	score_kernel_attributes( int *private_bytes, int *static_lds, int *regs, bool text = false );
+// the kernel's private bytes, static LDS and registers as the runtime reports them (rma_score_info); text: the text
+// kernel's; match: the instance for an image with expressions
+hipError_t	score_kernel_attributes( int *private_bytes, int *static_lds, int *regs, bool text = false, bool match = false );
 // bytes of heap a launch of n records takes
 size_t	score_heap_bytes( long long n, int heap_cap );
 // Enqueue on s: bytes [ 0, len[ h ] ) of row h of src to row h of dst, n rows of `stride` bytes.

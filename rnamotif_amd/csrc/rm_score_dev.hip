@@ -12,7 +12,7 @@ namespace {
 
 constexpr int	SC_MAX_WAVES = 4;
 
-template< bool TEXT > __device__ inline void score_body( const ScoreBatch &b )
+template< bool TEXT, bool MATCH = false > __device__ inline void score_body( const ScoreBatch &b )
 {
 	extern __shared__ __attribute__(( aligned( 16 ) )) uint64_t	lds[];
 	const int	t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -41,9 +41,14 @@ template< bool TEXT > __device__ inline void score_body( const ScoreBatch &b )
 	if( hitwin_span( w, b.shape, b.n_seq, b.slen, &lo, &hi, &which ) != HW_OK )
 		atomicMin( b.bad, static_cast<unsigned long long>( b.first + h ) );
 	else{
-		const int	wave_words = rms_wave_bytes( b.stack, b.n_vars ) / 4;
+		const int	wave_words = ( MATCH ? rms_wave_bytes( b.stack, b.n_vars, b.frames ) : rms_wave_bytes( b.stack, b.n_vars ) ) / 4;
 		int32_t	*planes = reinterpret_cast<int32_t *>( cmp + 256 ) + wave * wave_words;
 		RmsMem<64>	mem{ planes + lane, reinterpret_cast<uint8_t *>( planes + ( b.stack + b.n_vars ) * 3 * 64 ) + lane, b.stack, b.n_vars };
+		if( MATCH ){
+			// the matcher's planes behind the wave's own: slot k of lane l at word k * 64 + l
+			mem.mq = planes + rms_wave_bytes( b.stack, b.n_vars ) / 4 + lane;
+			mem.mq_frames = b.frames;
+		}
 		const int	seq = w[ 0 ], slen = b.slen[ seq ];
 		const ScoreBases	bases{ b.text + b.start[ seq ], let, cmp, w[ 1 ], slen };
 		if( TEXT ){
@@ -58,8 +63,13 @@ template< bool TEXT > __device__ inline void score_body( const ScoreBatch &b )
 				mem.heap = b.heap + ( ( h >> 6 ) * 64 * heap_words + lane ) * 4;
 				mem.heap_cap = b.heap_cap;
 			}
-			rms_run( m, w, slen, bases, mem, b.budget, &r, tx );
-		}else
+			if( MATCH )
+				rms_run_t<true, true>( m, w, slen, bases, mem, b.budget, &r, tx );
+			else
+				rms_run( m, w, slen, bases, mem, b.budget, &r, tx );
+		}else if( MATCH )
+			rms_run_t<false, true>( m, w, slen, bases, mem, b.budget, &r, RmsText() );
+		else
 			rms_run( m, w, slen, bases, mem, b.budget, &r );
 		if( r.outcome == RMS_STOPPED ){
 			atomicMin( b.stopped, static_cast<unsigned long long>( b.first + h ) );
@@ -87,6 +97,19 @@ rma_score_text_kernel( ScoreBatch b )
 	score_body<true>( b );
 }
 
+// the two for an image with expressions (RMS_IMG_MATCH and a =~, a !~ or a mismatches( string, pattern ) in MAIN)
+__global__ void __launch_bounds__( SC_MAX_WAVES * 64 )
+rma_score_match_kernel( ScoreBatch b )
+{
+	score_body<false, true>( b );
+}
+
+__global__ void __launch_bounds__( SC_MAX_WAVES * 64 )
+rma_score_match_text_kernel( ScoreBatch b )
+{
+	score_body<true, true>( b );
+}
+
 __global__ void __launch_bounds__( 256 )
 rma_score_text_copy_kernel( uint8_t *dst, const uint8_t *src, const int32_t *len, long long n, int stride )
 {
@@ -100,9 +123,9 @@ rma_score_text_copy_kernel( uint8_t *dst, const uint8_t *src, const int32_t *len
 
 }	// namespace
 
-int score_waves( int image_bytes, int stack, int n_vars )
+int score_waves( int image_bytes, int stack, int n_vars, int frames )
 {
-	const int	room = RMS_LDS_BYTES - RMS_LDS_TABLES - image_bytes, wave = rms_wave_bytes( stack, n_vars );
+	const int	room = RMS_LDS_BYTES - RMS_LDS_TABLES - image_bytes, wave = rms_wave_bytes( stack, n_vars, frames );
 	const int	n = room < wave ? 0 : room / wave;
 	return n > SC_MAX_WAVES ? SC_MAX_WAVES : n;
 }
@@ -111,16 +134,24 @@ hipError_t score_records( const ScoreBatch &b, hipStream_t s )
 {
 	if( b.n <= 0 )
 		return hipSuccess;
-	const int	waves = score_waves( b.image_bytes, b.stack, b.n_vars );
-	if( waves < 1 || b.image_bytes % 8 != 0 || b.stack < 1 || b.n_vars < 1 )
+	const int	frames = b.match_kernel ? b.frames : -1;
+	const int	waves = score_waves( b.image_bytes, b.stack, b.n_vars, frames );
+	if( waves < 1 || b.image_bytes % 8 != 0 || b.stack < 1 || b.n_vars < 1 || ( b.match_kernel && ( b.frames < 0 || b.frames > RMQ_MAX_OPS ) ) )
 		return hipErrorInvalidValue;
 	const int	block = waves * 64;
-	const size_t	lds = size_t( b.image_bytes ) + RMS_LDS_TABLES + size_t( waves ) * size_t( rms_wave_bytes( b.stack, b.n_vars ) );
+	const size_t	lds = size_t( b.image_bytes ) + RMS_LDS_TABLES + size_t( waves ) * size_t( rms_wave_bytes( b.stack, b.n_vars, frames ) );
+	if( lds > size_t( RMS_LDS_BYTES ) )
+		return hipErrorInvalidValue;
 	if( b.text_kernel ){
 		if( b.heap_cap < 0 || ( b.heap_cap > 0 && b.heap == nullptr ) || ( b.col != nullptr && ( b.col_stride < 1 || b.col_len == nullptr ) ) )
 			return hipErrorInvalidValue;
-		hipLaunchKernelGGL( rma_score_text_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
-	}else
+		if( b.match_kernel )
+			hipLaunchKernelGGL( rma_score_match_text_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
+		else
+			hipLaunchKernelGGL( rma_score_text_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
+	}else if( b.match_kernel )
+		hipLaunchKernelGGL( rma_score_match_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
+	else
 		hipLaunchKernelGGL( rma_score_kernel, dim3( unsigned( ( b.n + block - 1 ) / block ) ), dim3( unsigned( block ) ), lds, s, b );
 	return hipGetLastError();
 }
@@ -139,10 +170,12 @@ hipError_t score_text_copy( uint8_t *dst, const uint8_t *src, const int32_t *len
 	return hipGetLastError();
 }
 
-hipError_t score_kernel_attributes( int *private_bytes, int *static_lds, int *regs, bool text )
+hipError_t score_kernel_attributes( int *private_bytes, int *static_lds, int *regs, bool text, bool match )
 {
 	hipFuncAttributes	a;
-	const hipError_t	e = hipFuncGetAttributes( &a, reinterpret_cast<const void *>( text ? rma_score_text_kernel : rma_score_kernel ) );
+	const void	*k = match ? ( text ? reinterpret_cast<const void *>( rma_score_match_text_kernel ) : reinterpret_cast<const void *>( rma_score_match_kernel ) ) :
+		( text ? reinterpret_cast<const void *>( rma_score_text_kernel ) : reinterpret_cast<const void *>( rma_score_kernel ) );
+	const hipError_t	e = hipFuncGetAttributes( &a, k );
 	if( e == hipSuccess ){
 		*private_bytes = int( a.localSizeBytes );
 		*static_lds = int( a.sharedSizeBytes );

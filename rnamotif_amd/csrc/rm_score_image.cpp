@@ -2,6 +2,7 @@
 // what is refused, and the host VM's words for a stop.
 #include "rm_score.h"
 #include "rm_score_core.h"
+#include "rm_regex.h"
 #include <atomic>
 #include <cstdarg>
 #include <cmath>
@@ -95,7 +96,7 @@ std::string score_image_make( const Descriptor &d, const rma_program_t &prog, Sc
 
 std::string score_image_make_flags( const Descriptor &d, const rma_program_t &prog, ScoreImage *out, unsigned flags )
 {
-	const bool	checked = ( flags & 1u ) != 0, text = ( flags & 2u ) != 0;
+	const bool	checked = ( flags & 1u ) != 0, text = ( flags & 2u ) != 0, match = ( flags & 8u ) != 0;
 	static std::atomic<uint64_t>	serials{ 0 };
 	const char	*who = "the score section cannot run on the device: ";
 	for( int e = 0; e < prog.n_elems && !checked; e++ )
@@ -141,13 +142,54 @@ std::string score_image_make_flags( const Descriptor &d, const rma_program_t &pr
 		return std::string( who ) + ( score_id == nullptr ? "no SCORE" : why );
 	std::map<std::string, int>	file_ix;
 	std::vector<size_t>	marks;		// the MRK of every call and `in` that is open
+	// RMA_SCORE_MATCH: the expressions of =~ / !~ and mismatches( string, pattern ), compiled here once for all records
+	std::vector<RmsMatchExpr>	exprs;
+	std::vector<RmqOp>	ops;
+	int	frames = 0;
+	std::vector<char>	landed( pr.size() + 1, 0 );	// a jump of MAIN lands on this instruction
+	for( const Inst &ip : pr )
+		if( ( ip.op == OP_FJP || ip.op == OP_JMP || ip.op == OP_AND || ip.op == OP_IOR ) && ip.val.ival >= 0 && size_t( ip.val.ival ) <= pr.size() )
+			landed[ size_t( ip.val.ival ) ] = 1;
+	// The pattern of the MAT or the SCL at pc as an expression of the table; *x: its index.  The pattern is a constant
+	// where the instruction that leaves it on the stack is an LDC of a string directly in front and no jump lands between
+	// the two; one a record makes would have to be compiled for every record.
+	auto expression = [&]( size_t pc, const char *what, int *x ) -> std::string {
+		if( pc == 0 || pr[ pc - 1 ].op != OP_LDC || pr[ pc - 1 ].val.type != T_STRING || landed[ pc ] )
+			return fmt( "the pattern of %s is not one string constant: it would have to be compiled for every record", what );
+		const char	*pat = static_cast<const char *>( pr[ pc - 1 ].val.pval );
+		if( exprs.size() >= size_t( RMS_MAX_EXPR ) )
+			return fmt( "more than %d patterns of =~, !~ and mismatches( string, pattern ), the image holds %d expressions", int( RMS_MAX_EXPR ), int( RMS_MAX_EXPR ) );
+		RmsMatchExpr	ex{ *pat == '^', int32_t( ops.size() ), -1, int32_t( strlen( pat ) ) };
+		ReProg	re;
+		if( re_compile( pat, re ) ){
+			if( re.ops.size() > size_t( RMQ_MAX_OPS ) )
+				return fmt( "the pattern '%s' of %s has %zu ops, the image holds %d an expression", pat, what, re.ops.size(), int( RMQ_MAX_OPS ) );
+			int	repeats = 0;
+			if( !rmq_flatten( re, &ops, &repeats ) )
+				return fmt( "the pattern '%s' of %s has a group number beyond 9", pat, what );
+			ex.n_ops = int32_t( re.ops.size() );
+			frames = std::max( frames, repeats );
+		}else if( re.err != 41 )	// ("" is no expression at all -- regerr 41, no remembered search string: the host VM answers 0, and so does the rule)
+			return fmt( "the pattern '%s' of %s is no regular expression (regerr %d)", pat, what, re.err );
+		*x = int( exprs.size() );
+		exprs.push_back( ex );
+		return "";
+	};
 	for( size_t pc = 0; pc < pr.size(); pc++ ){
 		const Inst	&ip = pr[ pc ];
 		const std::string	at = fmt( "%s:%d ", ip.filename, ip.lineno );
 		RmsInst	o{ uint8_t( ip.op ), RMS_K_NONE, 0, 0 };
 		switch( ip.op ){
-		case OP_MAT :
-			return std::string( who ) + at + "the =~ and !~ operators need the host's regular expressions";
+		case OP_MAT : {
+			if( !match )
+				return std::string( who ) + at + "the =~ and !~ operators need the host's regular expressions";
+			int	x = 0;
+			if( !( why = expression( pc, "=~ / !~", &x ) ).empty() )
+				return std::string( who ) + at + why;
+			o.kind = RMS_K_INT;
+			o.a = x;
+			break;
+		}
 		case OP_HOLD : case OP_RLSE : case OP_FCL : case OP_HALT :
 			return std::string( who ) + at + "an instruction MAIN cannot hold";
 		case OP_MRK :
@@ -180,8 +222,14 @@ std::string score_image_make_flags( const Descriptor &d, const rma_program_t &pr
 				return std::string( who ) + at + "sprintf() formats text, which the host does";
 			if( o.a == SC_BITS && !text )
 				return std::string( who ) + at + "bits() is computed on the host";
-			if( o.a == SC_MISMATCHES_2 )
-				return std::string( who ) + at + "mismatches( string, pattern ) needs the host's regular expressions";
+			if( o.a == SC_MISMATCHES_2 ){
+				if( !match )
+					return std::string( who ) + at + "mismatches( string, pattern ) needs the host's regular expressions";
+				int	x = 0;
+				if( !( why = expression( pc, "mismatches( string, pattern )", &x ) ).empty() )
+					return std::string( who ) + at + why;
+				o.len = uint16_t( x );
+			}
 			if( o.a < 0 || o.a >= N_SC || o.a == SC_MISMATCHES )
 				return std::string( who ) + at + "an unknown builtin";
 			break;
@@ -336,6 +384,13 @@ std::string score_image_make_flags( const Descriptor &d, const rma_program_t &pr
 	place( &h.o_ps, b.ps.size() * sizeof( rma_pairset_t ) );
 	place( &h.o_efn, sites.size() * sizeof( rma_efn_site_t ) );
 	place( &h.o_pool, b.pool.size() );
+	const size_t	match_at = at;		// (rms_match(): behind the pool, on the next multiple of 8)
+	if( match ){
+		h.flags |= RMS_IMG_MATCH;
+		h.n_expr = int32_t( exprs.size() );
+		if( !exprs.empty() )
+			at += sizeof( RmsMatch ) + exprs.size() * sizeof( RmsMatchExpr ) + ops.size() * sizeof( RmqOp );
+	}
 	h.bytes = int32_t( at );
 	if( text ){
 		// the largest span two elements can enclose: every element at its longest, the contexts too
@@ -351,6 +406,9 @@ std::string score_image_make_flags( const Descriptor &d, const rma_program_t &pr
 	if( h.bytes + RMS_LDS_TABLES + wave > RMS_LDS_BYTES )
 		return std::string( who ) + fmt( "an image of %d bytes and a wave's %d bytes of stack and variables leave no room for one wave in %d bytes of LDS",
 			h.bytes, wave, int( RMS_LDS_BYTES ) );
+	if( !exprs.empty() && h.bytes + RMS_LDS_TABLES + rms_wave_bytes( stack, h.n_vars, frames ) > RMS_LDS_BYTES )
+		return std::string( who ) + fmt( "an image of %d bytes, a wave's %d bytes of stack and variables and the %d bytes of its matcher's %d frames leave no room "
+			"for one wave in %d bytes of LDS", h.bytes, wave, rmq_wave_bytes( frames ), frames, int( RMS_LDS_BYTES ) );
 	img.blob.assign( at / 8, 0 );
 	char	*p = reinterpret_cast<char *>( img.blob.data() );
 	auto put = [&]( int32_t o, const void *src, size_t bytes ){
@@ -366,6 +424,12 @@ std::string score_image_make_flags( const Descriptor &d, const rma_program_t &pr
 	put( h.o_ps, b.ps.data(), b.ps.size() * sizeof( rma_pairset_t ) );
 	put( h.o_efn, sites.data(), sites.size() * sizeof( rma_efn_site_t ) );
 	put( h.o_pool, b.pool.data(), b.pool.size() );
+	if( !exprs.empty() ){
+		const RmsMatch	mh{ int32_t( ops.size() ), frames };
+		put( int32_t( match_at ), &mh, sizeof( mh ) );
+		put( int32_t( match_at + sizeof( mh ) ), exprs.data(), exprs.size() * sizeof( RmsMatchExpr ) );
+		put( int32_t( match_at + sizeof( mh ) + exprs.size() * sizeof( RmsMatchExpr ) ), ops.data(), ops.size() * sizeof( RmqOp ) );
+	}
 	img.prog.reset( new rma_program_t );
 	memcpy( img.prog.get(), &prog, sizeof( rma_program_t ) );	// (every byte, padding too: rma_score_hits compares bytes)
 	if( text ){
@@ -465,6 +529,7 @@ std::string score_stop_text( const ScoreImage &img, const RmsResult &r )
 	case RMS_STOP_BITS_LEN2 : return fmt( "%s:%d bits: descr2 must have match len > 0.", f, l );
 	case RMS_STOP_BITS_POS2_BIG : return fmt( "%s:%d bits: bad pos2 %d, must be <= %d.", f, l, r.a0, r.a1 );
 	case RMS_STOP_BITS_SPAN : return fmt( "%s:%d bits() over %d bases, the table of its logarithms ends at %d.", f, l, r.a0, r.a1 );
+	case RMS_STOP_MAT_TYPE : return fmt( "%s:%d typemismatch.", f, l );
 	default :
 		return fmt( "%s:%d the image holds what the rule does not run (stop %d, %d).", f, l, r.stop, r.a0 );
 	}

@@ -8,11 +8,6 @@
 
 namespace rma {
 
-static_assert( int( RMQ_CHR ) == RE_CHR && int( RMQ_DOT ) == RE_DOT && int( RMQ_CCL ) == RE_CCL && int( RMQ_NCCL ) == RE_NCCL && int( RMQ_DOL ) == RE_DOL &&
-	int( RMQ_BRA ) == RE_BRA && int( RMQ_KET ) == RE_KET && int( RMQ_BACK ) == RE_BACK && int( RMQ_BRC ) == RE_BRC && int( RMQ_LET ) == RE_LET,
-	"the rule's op kinds are RE_*" );
-static_assert( int( RMQ_ONE ) == REP_ONE && int( RMQ_STAR ) == REP_STAR && int( RMQ_RANGE ) == REP_RANGE, "the rule's repeats are REP_*" );
-
 std::string seqcheck_image_make( const Descriptor &d, const rma_program_t &prog, SeqImage *out )
 {
 	static std::atomic<uint64_t>	serials{ 0 };
@@ -47,21 +42,8 @@ std::string seqcheck_image_make( const Descriptor &d, const rma_program_t &prog,
 		ex.first = int32_t( ops.size() );
 		ex.n_ops = int32_t( s.re->ops.size() );
 		int	repeats = 0;
-		for( const ReOp &op : s.re->ops ){
-			RmqOp	o;
-			memset( &o, 0, sizeof( o ) );
-			o.kind = op.kind;
-			o.rep = op.rep;
-			o.c = op.c;
-			o.lo = op.lo;
-			o.hi = op.hi;
-			memcpy( o.set, op.set, sizeof( o.set ) );	// (little endian: bit ch of the 128 is bit ch & 31 of word ch >> 5)
-			if( ( op.kind == RE_BRA || op.kind == RE_KET || op.kind == RE_BACK ) && op.c >= RMQ_NBRA )
-				return who + "a group number beyond 9";
-			if( op.rep != REP_ONE )
-				repeats++;
-			ops.push_back( o );
-		}
+		if( !rmq_flatten( *s.re, &ops, &repeats ) )
+			return who + "a group number beyond 9";
 		if( repeats > hdr.frames )
 			hdr.frames = repeats;
 	}

@@ -372,13 +372,44 @@ RMQ_FN void rmq_run( const RmqImage *m, const int32_t *w, const Bases &bases, co
 
 #ifndef RMQ_POD_ONLY
 // ---- the host's half (rm_seqcheck.cpp)
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
+#include "rm_regex.h"
 
 namespace rma {
 
 struct Descriptor;
+
+static_assert( int( RMQ_CHR ) == RE_CHR && int( RMQ_DOT ) == RE_DOT && int( RMQ_CCL ) == RE_CCL && int( RMQ_NCCL ) == RE_NCCL && int( RMQ_DOL ) == RE_DOL &&
+	int( RMQ_BRA ) == RE_BRA && int( RMQ_KET ) == RE_KET && int( RMQ_BACK ) == RE_BACK && int( RMQ_BRC ) == RE_BRC && int( RMQ_LET ) == RE_LET,
+	"the rule's op kinds are RE_*" );
+static_assert( int( RMQ_ONE ) == REP_ONE && int( RMQ_STAR ) == REP_STAR && int( RMQ_RANGE ) == REP_RANGE, "the rule's repeats are REP_*" );
+
+// The ops of a compiled expression, flattened, behind *ops; *repeats: how many of them repeat (the frames its matcher
+// needs).  false: a group number beyond 9.  (seqcheck_image_make and score_image_make_flags, rm_score_image.cpp, both
+// make their ops here; in the header, so that a checker built from the front end alone has it.)
+inline bool rmq_flatten( const ReProg &re, std::vector<RmqOp> *ops, int *repeats )
+{
+	*repeats = 0;
+	for( const ReOp &op : re.ops ){
+		RmqOp	o;
+		memset( &o, 0, sizeof( o ) );
+		o.kind = op.kind;
+		o.rep = op.rep;
+		o.c = op.c;
+		o.lo = op.lo;
+		o.hi = op.hi;
+		memcpy( o.set, op.set, sizeof( o.set ) );	// (little endian: bit ch of the 128 is bit ch & 31 of word ch >> 5)
+		if( ( op.kind == RE_BRA || op.kind == RE_KET || op.kind == RE_BACK ) && op.c >= RMQ_NBRA )
+			return false;
+		if( op.rep != REP_ONE )
+			++*repeats;
+		ops->push_back( o );
+	}
+	return true;
+}
 
 struct SeqImage {
 	std::vector<uint64_t>	blob;			// the image, 8-byte aligned
