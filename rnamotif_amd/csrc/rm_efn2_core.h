@@ -298,19 +298,20 @@ template< class X > RMD_FN int rme2_efn2( const X &x )	// RM_efn2 :1103
 }
 
 // Energy of efn2 site k for the hit record w (do_sc_efnx, score.c:1672-1679, before the 0.01).
-template< class Seq, int BIG = 0 >
+template< class Seq, int BIG = 0, bool FACTS = false >
 RMD_FN int rme2_site_energy( const rmd_program_t *P, const rma_efn2data_t *E, const Seq *sq, const int32_t *w, int k,
-	int16_t *bpbuf = nullptr, uint8_t *bcbuf = nullptr, int cache = 0 )
+	int16_t *bpbuf = nullptr, uint8_t *bcbuf = nullptr, int cache = 0, const rme_el_t *el = nullptr )
 {
-	rme_cand_t<Seq>	c;
+	rme_cand_t<Seq, FACTS>	c;
 	c.P = P;
 	c.w = w;
 	c.sq = sq;
+	c.F = el;
 	if( !c.setup( rmd_efn_sites( P )[ k ] ) )
 		return RME_INF;
 	if( bpbuf != nullptr && c.len <= cache )
 		c.fill_cache( bpbuf, bcbuf );
-	rme2_ctx_t< rme_cand_t<Seq>, BIG >	x;
+	rme2_ctx_t< rme_cand_t<Seq, FACTS>, BIG >	x;
 	x.E = E;
 	x.C = &c;
 	x.l_base = c.len - 1;

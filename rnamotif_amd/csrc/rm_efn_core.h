@@ -12,7 +12,10 @@
 // Plain C++ like rm_scan_core.h: compiled for the device by the kernel and for
 // the CPU by tests/hostsim.
 #pragma once
+#include <type_traits>
+#include <utility>
 #include "rm_dev_program.h"
+#include "rm_seq_window.h"
 
 #ifndef RMD_FN
 #define RMD_FN	static inline
@@ -397,12 +400,44 @@ template< class X > RMD_FN int rme_efn( const X &x )
 }
 
 // The candidate view: elements idx..idx2 of a hit record laid over a sequence.
-// Seq::code( p ) returns the base code at strand position p.
-template< class Seq >
+// Seq::code( p ) returns the base code at strand position p; a Seq may also have
+// window( p, n, out ): the codes of positions p .. p + n - 1, n <= RMW_MAX, into out[ 0 .. n ).
+template< class Seq, class = void > struct rme_has_window : std::false_type {};
+template< class Seq > struct rme_has_window< Seq,
+	std::void_t< decltype( std::declval<const Seq &>().window( 0, 0, static_cast<uint8_t *>( nullptr ) ) ) > > : std::true_type {};
+
+// What a call needs to know of an element, the same for every candidate: the energy kernels lay these out in LDS once
+// per workgroup (rme_cand_t::F), so that no loop over elements or bases reads the program image.
+struct rme_el_t {
+	uint32_t	mat2;		// helix strands: the pair matrix efn pairs by (efn_stdbp or the element's own), else 0
+	int8_t	type, proper, mate, pad;
+};
+RMD_FN rme_el_t rme_el_of( const rmd_program_t *P, int d )
+{
+	const rmd_elem_t	&st = P->elems[ d ];
+	rme_el_t	e{ 0, st.type, st.proper, st.mates[ 0 ], 0 };
+	if( st.type == RMA_T_H5 || st.type == RMA_T_H3 ){
+		const int	ps = P->efn_usestdbp ? P->efn_stdbp : st.pairset;
+		if( ps >= 0 )
+			e.mat2 = rmd_pairsets( P )[ ps ].mat2;
+	}
+	return e;
+}
+
+// FACTS: F is there (the kernels), and nothing of an element is read from P
+template< class Seq, bool FACTS = false >
 struct rme_cand_t {
 	const rmd_program_t	*P;
 	const int32_t	*w;		// hit record
 	const Seq	*sq;
+	const rme_el_t	*F = nullptr;	// [ n_elems ] with FACTS
+	RMD_FN_MEMBER rme_el_t	el( int d ) const
+	{
+		if constexpr( FACTS )
+			return F[ d ];
+		else
+			return rme_el_of( P, d );
+	}
 	int	idx, idx2, pos, pos2;	// pos2 resolved (last base of idx2 included)
 	int	off5, start, len;
 	// optional per-candidate arrays (the kernel keeps them in LDS for calls of up to
@@ -424,7 +459,7 @@ struct rme_cand_t {
 		start = off5 + pos;
 		len = 0;
 		for( int d = idx; d <= idx2; d++ ){
-			int	t = P->elems[ d ].type;
+			int	t = el( d ).type;
 			if( t != RMA_T_SS && t != RMA_T_H5 && t != RMA_T_H3 )
 				return 0;
 			len += mlen( d );
@@ -435,12 +470,12 @@ struct rme_cand_t {
 			return 0;
 		// setbp :3216 on every helix base: all partners must fall inside the call
 		for( int d = idx; d <= idx2; d++ ){
-			const rmd_elem_t	&st = P->elems[ d ];
+			const rme_el_t	st = el( d );
 			if( st.type == RMA_T_SS || ( st.type == RMA_T_H5 && d == idx2 ) || ( st.type == RMA_T_H3 && d == idx ) )
 				continue;
 			if( !st.proper )
 				return 0;
-			int	m = st.mates[ 0 ];
+			int	m = st.mate;
 			int	p0 = d == idx ? pos : 0, p1 = d == idx2 ? pos2 + 1 : mlen( d );
 			if( p0 >= p1 )
 				continue;
@@ -451,27 +486,37 @@ struct rme_cand_t {
 		}
 		return 1;
 	}
-	// fill cbc[] / cbp[] for the whole call: one pass over the elements
+	// fill cbc[] / cbp[] for the whole call (the elements idx .. idx2 lie one behind the other: strand positions
+	// start .. start + len - 1), in two passes:
+	// 1. the base codes, in one fetch where the Seq has window( p, n, out ) (rm_seq_window.h), base by base where not;
+	// 2. the partners, element by element: the element's and its mate's place and the pair set's matrix are read
+	//    once, both bases of a pair come from pass 1 (a call that begins inside its first element can have a
+	//    mate's base in front of it: that one is fetched as before)
 	RMD_FN_MEMBER void	fill_cache( int16_t *bpbuf, uint8_t *bcbuf )
 	{
+		if constexpr( rme_has_window<Seq>::value )
+			sq->window( start, len, bcbuf );
+		else
+			for( int i = 0; i < len; i++ )
+				bcbuf[ i ] = uint8_t( sq->code( start + i ) );
 		for( int d = idx; d <= idx2; d++ ){
-			const rmd_elem_t	&st = P->elems[ d ];
+			const rme_el_t	st = el( d );
+			const int	od = moff( d ) - start;
 			const int	p0 = d == idx ? pos : 0, p1 = d == idx2 ? pos2 + 1 : mlen( d );
 			const bool	ss = st.type == RMA_T_SS || ( st.type == RMA_T_H5 && d == idx2 ) || ( st.type == RMA_T_H3 && d == idx );
-			const int	m = st.mates[ 0 ];
-			const int	ps = P->efn_usestdbp ? P->efn_stdbp : st.pairset;
+			if( ss ){
+				for( int pq = p0; pq < p1; pq++ )
+					bpbuf[ od + pq ] = -1;
+				continue;
+			}
+			const int	m = st.mate;
+			const uint32_t	mat2 = st.mat2;
+			const int	qm = mlen( m ) - 1 + moff( m );		// strand position of the mate of pq = 0
 			for( int pq = p0; pq < p1; pq++ ){
-				const int	p = moff( d ) + pq, i = p - start;
-				const int	b = sq->code( p );
-				bcbuf[ i ] = uint8_t( b );
-				int	partner = -1;
-				if( !ss ){
-					const int	q1 = mlen( m ) - pq - 1;
-					const int	b1 = sq->code( q1 + moff( m ) );
-					if( ( rmd_pairsets( P )[ ps ].mat2 >> ( b * 5 + b1 ) ) & 1 )
-						partner = q1 + moff( m ) - off5;
-				}
-				bpbuf[ i ] = int16_t( partner );
+				const int	b = bcbuf[ od + pq ];
+				const int	j = qm - pq - start;
+				const int	b1 = j >= 0 && j < len ? bcbuf[ j ] : sq->code( qm - pq );
+				bpbuf[ od + pq ] = int16_t( ( ( mat2 >> ( b * 5 + b1 ) ) & 1 ) ? qm - pq - off5 : -1 );
 			}
 		}
 		cbp = bpbuf;
@@ -496,15 +541,14 @@ struct rme_cand_t {
 			int	o = moff( d ), l = mlen( d );
 			if( p < o || p >= o + l )
 				continue;
-			const rmd_elem_t	&st = P->elems[ d ];
+			const rme_el_t	st = el( d );
 			if( st.type == RMA_T_SS || ( st.type == RMA_T_H5 && d == idx2 ) || ( st.type == RMA_T_H3 && d == idx ) )
 				return -1;
 			int	pq = p - o;
-			int	m = st.mates[ 0 ];
+			int	m = st.mate;
 			int	q1 = mlen( m ) - pq - 1;
-			int	ps = P->efn_usestdbp ? P->efn_stdbp : st.pairset;
 			int	b = sq->code( p ), b1 = sq->code( q1 + moff( m ) );
-			return ( ( rmd_pairsets( P )[ ps ].mat2 >> ( b * 5 + b1 ) ) & 1 ) ? q1 + moff( m ) - off5 : -1;
+			return ( ( st.mat2 >> ( b * 5 + b1 ) ) & 1 ) ? q1 + moff( m ) - off5 : -1;
 		}
 		return -1;
 	}
@@ -514,19 +558,20 @@ struct rme_cand_t {
 // the 0.01 scaling (score.c:1672-1679).
 // (bpbuf/bcbuf: room for the base codes and partners of a call of up to cache bases; longer calls
 // compute them on demand from the hit record)
-template< class Seq, int BIG = 0 >
+template< class Seq, int BIG = 0, bool FACTS = false >
 RMD_FN int rme_site_energy( const rmd_program_t *P, const rme_tables_t *T, const Seq *sq, const int32_t *w, int k,
-	int16_t *bpbuf = nullptr, uint8_t *bcbuf = nullptr, int cache = 0 )
+	int16_t *bpbuf = nullptr, uint8_t *bcbuf = nullptr, int cache = 0, const rme_el_t *el = nullptr )
 {
-	rme_cand_t<Seq>	c;
+	rme_cand_t<Seq, FACTS>	c;
 	c.P = P;
 	c.w = w;
 	c.sq = sq;
+	c.F = el;
 	if( !c.setup( rmd_efn_sites( P )[ k ] ) )
 		return RME_INF;
 	if( bpbuf != nullptr && c.len <= cache )
 		c.fill_cache( bpbuf, bcbuf );
-	rme_ctx_t< rme_cand_t<Seq>, BIG >	x;
+	rme_ctx_t< rme_cand_t<Seq, FACTS>, BIG >	x;
 	x.T = T;
 	x.C = &c;
 	x.l_base = c.len - 1;

@@ -2508,11 +2508,23 @@ rma_search_kernel( const rmd_program_t *gP, int prog_bytes, int qcap, DbView db,
 }
 
 // ---------------------------------------------------------------- efn kernel
+// (the two arrays of the DbView and the entry's place, not the view: the energy functions get it by address, so it lies in
+// a lane's scratch memory)
 struct DevSeq {
-	DbView	db;
+	const uint32_t	*codes, *amask;
 	int64_t	off;
 	int	slen, comp;
-	__device__ inline int code( int p ) const { return db_strand_code( db, off, slen, comp, p ); }
+	// db_strand_code()'s rule
+	__device__ inline int code( int p ) const
+	{
+		const int64_t	base = off + ( comp ? slen - 1 - p : p );
+		if( ( amask[ base >> 5 ] >> ( base & 31 ) ) & 1 )
+			return RMA_BC_N;
+		const int	c = ( codes[ base >> 4 ] >> ( 2 * ( base & 15 ) ) ) & 3;
+		return comp ? 3 - c : c;
+	}
+	// positions p .. p + n - 1 at once, n <= RMW_MAX: the words that hold them fetched together (rm_seq_window.h)
+	__device__ inline void window( int p, int n, uint8_t *out ) const { rmw_window_codes( codes, amask, off, slen, comp, p, n, out ); }
 };
 
 #define RME_N16_PAD	( ( RME_N16 + 7 ) / 8 * 8 )
@@ -2520,7 +2532,10 @@ struct DevSeq {
 // workgroup, every lane keeps the base codes and partners of its call in LDS while it is no
 // longer than EFN_CACHE bases (a cloverleaf is under 96) -- 136 KB in all -- and the candidates
 // are taken in a grid-stride loop, so the staging is paid once per CU and four waves share it.
+// Both forms: a lane fetches the words of its call's window together and pairs the bases from LDS (rme_cand_t::fill_cache),
+// and reads the elements' types, mates and pair matrices from 800 bytes of LDS the workgroup fills once (rme_el_t).
 #define EFN_CACHE	96
+static_assert( EFN_CACHE <= RMW_MAX, "a cached call is one window of DevSeq::window()" );
 #define EFN_LIGHT_LDS	( 64 * ( ( EFN_CACHE + 2 ) * 2 + EFN_CACHE + 4 ) )	// dynamic LDS of rma_efn_light_kernel
 // BIG: for descriptors with an efn() / efn2() call over more than 15 helices (rmd_program_t::efn_big): the loops' stacks sized
 // for fifty (rm_efn_core.h)
@@ -2529,8 +2544,8 @@ struct DevSeq {
 // registers: it finds room on a CU next to the workgroups of a search kernel (the instance that walks nothing leaves 33 KB and
 // a wave per SIMD), where the staged form -- 136 KB -- waits until the other scanner's search kernel is through.
 template< int BLOCK, int BIG, bool STAGE >
-__device__ __forceinline__ void efn_body( const rmd_program_t *gP, const DbView &db, int32_t *hits, long long n_hits,
-	const int16_t *g16, const int32_t *tlkey, const int32_t *loginc, const rma_efn2data_t *e2 )
+__device__ __forceinline__ void efn_body( const rmd_program_t * __restrict__ gP, const DbView &db, int32_t * __restrict__ hits, long long n_hits,
+	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2 )
 {
 	// tables staged 16 bytes per lane and step (the device copy is padded to a multiple of 8 entries)
 	__shared__ __align__( 16 ) int16_t	t16_s[ STAGE ? RME_N16_PAD : 8 ];
@@ -2554,23 +2569,28 @@ __device__ __forceinline__ void efn_body( const rmd_program_t *gP, const DbView 
 		bpbuf = reinterpret_cast<int16_t *>( efn_dyn ) + threadIdx.x * ( EFN_CACHE + 2 );
 		bcbuf = efn_dyn + BLOCK * ( EFN_CACHE + 2 ) * sizeof( int16_t ) + threadIdx.x * ( EFN_CACHE + 4 );
 	}
+	// what the calls read of the elements, the same for every candidate: out of the program image once per workgroup
+	__shared__ rme_el_t	s_el[ RMD_MAX_ELEMS ];
+	for( int d = threadIdx.x; d < gP->n_elems; d += BLOCK )
+		s_el[ d ] = rme_el_of( gP, d );
+	__syncthreads();
 	const int	efn_off = RMA_HIT_HDR + 4 * gP->n_elems + 4;
 	for( long long h = ( long long )blockIdx.x * BLOCK + threadIdx.x; h < n_hits; h += ( long long )gridDim.x * BLOCK ){
 		int32_t	*w = hits + h * gP->hit_stride;
-		DevSeq	sq{ db, db.base_off[ w[ 0 ] ], db.slen[ w[ 0 ] ], w[ 1 ] };
+		DevSeq	sq{ db.codes, db.amask, db.base_off[ w[ 0 ] ], db.slen[ w[ 0 ] ], w[ 1 ] };
 		for( int k = 0; k < gP->n_efn; k++ ){
 			if( rmd_efn_sites( gP )[ k ].kind == RMA_EFN_KIND_EFN2 )
-				w[ efn_off + k ] = e2 != nullptr ? rme2_site_energy<DevSeq, BIG>( gP, e2, &sq, w, k, bpbuf, bcbuf, EFN_CACHE ) : RME2_INF;
+				w[ efn_off + k ] = e2 != nullptr ? rme2_site_energy<DevSeq, BIG, true>( gP, e2, &sq, w, k, bpbuf, bcbuf, EFN_CACHE, s_el ) : RME2_INF;
 			else if( g16 != nullptr )
-				w[ efn_off + k ] = rme_site_energy<DevSeq, BIG>( gP, &T, &sq, w, k, bpbuf, bcbuf, EFN_CACHE );
+				w[ efn_off + k ] = rme_site_energy<DevSeq, BIG, true>( gP, &T, &sq, w, k, bpbuf, bcbuf, EFN_CACHE, s_el );
 		}
 	}
 }
 
 template< int BLOCK, int BIG = 0 >
 __global__ void __launch_bounds__( BLOCK )
-rma_efn_kernel( const rmd_program_t *gP, DbView db, int32_t *hits, long long n_hits,
-	const int16_t *g16, const int32_t *tlkey, const int32_t *loginc, const rma_efn2data_t *e2 )
+rma_efn_kernel( const rmd_program_t * __restrict__ gP, DbView db, int32_t * __restrict__ hits, long long n_hits,
+	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2 )
 {
 	efn_body<BLOCK, BIG, true>( gP, db, hits, n_hits, g16, tlkey, loginc, e2 );
 }
@@ -2578,8 +2598,8 @@ rma_efn_kernel( const rmd_program_t *gP, DbView db, int32_t *hits, long long n_h
 // (120 registers: four workgroups of the search instance that walks nothing, at 96 each, leave a SIMD 128)
 template< int BIG = 0 >
 __global__ void __launch_bounds__( 64, 4 )
-rma_efn_light_kernel( const rmd_program_t *gP, DbView db, int32_t *hits, long long n_hits,
-	const int16_t *g16, const int32_t *tlkey, const int32_t *loginc, const rma_efn2data_t *e2 )
+rma_efn_light_kernel( const rmd_program_t * __restrict__ gP, DbView db, int32_t * __restrict__ hits, long long n_hits,
+	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2 )
 {
 	// (like the drain kernel in front of it on the stream it runs beside another scanner's search kernel, the youngest wave
 	// on its SIMD: at priority 3 it takes 0.147 against 0.18 ms there and the step of two scanners in turns 0.605 against 0.619)
