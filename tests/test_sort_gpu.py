@@ -1,7 +1,9 @@
 """GPU: the ordering of the hit stream on the device (rnamotif_amd/csrc/rm_hitsort_dev.hip: packed
 64-bit keys, radix sort, gather + renumbering kernel) against the host's (rm_hitsort.h,
-RNAMOTIF_HOSTSORT=1) and the oracle -- including records whose order word outgrows the key's field
-(the scan then falls back to the host sort, and widens the field for the scans after it)."""
+RNAMOTIF_HOSTSORT=1) and the oracle -- including a scan of 1.8 M records, fourteen times what a fresh scanner's hit buffer
+holds, with hundreds of records per (start, end).  (Order words that outgrow the key's field -- the scan then falls back to the
+host sort and widens the field for the scans after it -- are tests/test_scan_end_gpu.py's: the field has had 20 bits since the
+pieces of items count in their own ranges, and this descriptor's walks take 10.)"""
 import os
 
 import numpy as np
@@ -36,7 +38,10 @@ def test_device_order_equals_host_order(built, workdir, gbrna, name):
 
 
 def test_order_words_beyond_the_key_field(built, tmp_path):
-    """three single strands in a row: hundreds of candidates per (start, end) -- order words above 255"""
+    """Three single strands in a row: hundreds of candidates per (start, end) -- order words above 255, which was the key's field
+    when this test got its name.  The walks of the descriptor number 30 x 30 (ord_bits 10) and the field has 20 bits now, so every
+    scan here is ordered on the device; what the test still holds is the ordering of 1.8 M records with long runs of equal
+    (entry, strand, start, rank), behind a hit buffer that had to be regrown."""
     import rnamotif_amd as R
     from oracle_binding import oracle_scan
     p = tmp_path / "dense.descr"
@@ -47,8 +52,8 @@ def test_order_words_beyond_the_key_field(built, tmp_path):
     assert want[:, 4].max() > 255
     sc = R.Scanner(d)
     db = sc.database(seqs)
-    first = sc.scan(db)          # falls back to the host sort, widens the field
-    second = sc.scan(db)         # on the device with the wide field
+    first = sc.scan(db)          # counted, the hit buffer regrown, searched again; ordered on the device
+    second = sc.scan(db)         # no repeat: the buffers are there
     sc.set_option("host_sort", 1)
     host = sc.scan(db)
     assert np.array_equal(first, want) and np.array_equal(second, want) and np.array_equal(host, want)
