@@ -1127,7 +1127,9 @@ int ScoreVM::run( int comp, int slen, const char *sbuf, Ident **h_id, const int3
 				top.pval = dupstr( ( const char * )ip.val.pval );
 				break;
 			case T_POS :
-				if( esp_ < 0 )
+				// (an index of rm_xdescr applied to rm_descr: behind an explicit left context the last element's is one past
+				// the elements, where the reference reads whatever follows its array; here it is no element's reference)
+				if( esp_ < 0 || estk_[ esp_ ] >= int( d_.descr.size() ) )
 					fail( "%s:%d '$' used outside a structure element reference.", ip.filename, ip.lineno );
 				top.type = T_INT;
 				top.ival = d_.descr[ estk_[ esp_ ] ].matchlen;	// (sic) rm_descr, not rm_xdescr
