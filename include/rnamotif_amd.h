@@ -564,6 +564,42 @@ int	rma_score_hits_text( rma_scanner_t *sc, const rma_score_t *sp, const rma_db_
 		uint8_t *d_text /* n_hits * text_stride */, int32_t text_stride, int32_t *d_text_len /* n_hits */,
 		void *stream, char *err, size_t errlen );
 
+/* ---- hit records as rnamotif prints them, on the device: for each of the n_hits records at d_hits the two lines
+ * HitPrinter::print puts on stdout -- ">sid sdef" and the hit line: %-12s of sid, the score column, " %d %7d %4d" of
+ * strand, offset and length, one field per printed element -- as bytes in device memory (csrc/rm_hitprint.h has the
+ * rule, shared by the host and the kernels).  The score column of record h is the d_text_len[ h ] bytes of row h of
+ * d_text_bytes, as rma_score_hits_text() delivers them; a record whose d_accept[ h ] is 0 has no bytes (d_accept
+ * NULL: every record is printed).  Record h is bytes [ d_off[ h ], d_off[ h + 1 ] ) of d_out, in the order given:
+ * d_out copied to the host and written behind rma_print_header()'s bytes is rnamotif's output for these records.
+ * The names of the entries come from a table on the device.  rma_names_create() makes it for a database made by
+ * rma_db_create_device() or rma_db_create_device_fasta(): n (the database's number of entries) sids and sdefs, each a
+ * C string or, with sid_len / sdef_len given, that many bytes without a NUL; sids NULL or sids[ e ] NULL: the entry's
+ * number in decimal -- for a database made from FASTA text its own rma_db_entry_name() -- and sdefs likewise: "", or
+ * the database's own.  A sid of 2048 bytes or more is refused: the printer would cut it.  The table is uploaded once,
+ * on the device's upload stream behind the database, and the call does not wait; rma_names_destroy() waits for the
+ * kernels that read it.
+ * Arguments as rma_hit_structures takes them: any rows in any order, the checks (a bad record fails the call, naming
+ * its index, as does a d_text_len[ h ] outside [0, text_width]; nothing is written then), chunks of 2^17 records,
+ * pointers checked alike.  rma_hit_print_size() returns the bytes of all records in *total and synchronises once.
+ * rma_hit_print() checks and counts again, refuses a total that is not what it finds, then queues the kernel that
+ * fills d_out and d_off and returns without waiting for it: it runs behind what is queued on `stream` now and ahead of
+ * what is queued there next.  Names made for another database are refused.  rma_print_header() writes the three "#RM"
+ * lines HitPrinter::header prints in front of the first hit into buf (NUL-terminated, cut at buflen - 1 bytes) and
+ * returns their length, -1 when it cannot. */
+typedef struct rma_names	rma_names_t;
+int	rma_names_create( rma_scanner_t *sc, const rma_db_t *db, const char *const *sids, const int64_t *sid_len /* or NULL */,
+		const char *const *sdefs, const int64_t *sdef_len /* or NULL */, int32_t n, rma_names_t **out,
+		char *err, size_t errlen );
+void	rma_names_destroy( rma_names_t *names );
+int	rma_hit_print_size( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *d_accept /* n_hits or NULL: all */, const int32_t *d_text_len /* n_hits */,
+		int64_t *total, void *stream, char *err, size_t errlen );
+int	rma_hit_print( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *letters /* 256 or NULL */, const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width,
+		const int32_t *d_text_len, int64_t total, uint8_t *d_out /* total */, int64_t *d_off /* n_hits + 1 */,
+		void *stream, char *err, size_t errlen );
+int	rma_print_header( const rma_descr_t *d, char *buf, size_t buflen );
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,12 @@ def lib() -> C.CDLL:
     L.rma_seqcheck_hits.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, C.c_int32, vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_program_loose.argtypes = [vp]
     L.rma_program_loose.restype = C.c_int
+    L.rma_names_create.argtypes = [vp, vp, cpp, i64p, cpp, i64p, C.c_int32, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.rma_names_destroy.argtypes = [vp]
+    L.rma_names_destroy.restype = None
+    L.rma_hit_print_size.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_print.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, vp, vp, C.c_int32, vp, C.c_int64, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_print_header.argtypes = [vp, C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -314,6 +320,10 @@ class Database:
         _check(lib().rma_db_wait(self._h, err, _ERRLEN), err)
 
     def close(self) -> None:
+        # (the table of default names Scanner.print_hits() made for this database goes first: it waits for its readers)
+        names = self.__dict__.pop("_default_names", None)
+        if names is not None:
+            names.close()
         if self._h:
             lib().rma_db_destroy(self._h)
             self._h = None
@@ -670,6 +680,79 @@ class HitAlignment:
         return [row[i:i + self.LINE] for i in range(0, len(row), self.LINE)]
 
 
+class EntryNames:
+    """The names and definitions of a database's entries as a table on the GPU (rma_names_create), for
+    Scanner.print_hits().  db: a database made by database_from_tensor() or database_from_fasta_tensor(); sids / sdefs:
+    one bytes per entry, defaults as Replay.device() -- the entry's number in decimal and b"" -- and for a database made
+    from FASTA text its own db.sids / db.sdefs; a None among given names is that entry's default.  Uploaded once, behind the database, without a wait.  Refused with words
+    (RnamotifError): a count that is not the database's, a NUL inside a name or definition, a sid of 2048 bytes or more."""
+
+    def __init__(self, scanner: "Scanner", db: "Database", sids: Optional[Sequence[bytes]] = None, sdefs: Optional[Sequence[bytes]] = None):
+        if getattr(db, "_h", None) is None or not db._h:
+            raise ValueError("the database is closed")
+        n = None
+        lens = []
+        for what, names in (("sids", sids), ("sdefs", sdefs)):
+            if names is None:
+                lens.append(None)
+                continue
+            names = [None if x is None else bytes(x) for x in names]        # (None: that entry's default)
+            if n is not None and len(names) != n:
+                raise ValueError(f"sids and sdefs: {n} and {len(names)}")
+            n = len(names)
+            lens.append((names, np.ascontiguousarray([0 if x is None else len(x) for x in names] or [0], dtype=np.int64)))
+        if n is None:
+            n = db.n_seqs
+        i64p = C.POINTER(C.c_int64)
+        h = C.c_void_p()
+        err = C.create_string_buffer(_ERRLEN)
+        args = []
+        for item in lens:
+            args += [None, None] if item is None else [_cstr_array(item[0]), item[1].ctypes.data_as(i64p)]
+        _check(lib().rma_names_create(scanner._h, db._h, args[0], args[1], args[2], args[3], n, C.byref(h), err, _ERRLEN), err)
+        self._h = h
+        self.scanner, self.db, self.n = scanner, db, n
+
+    def close(self) -> None:
+        if self._h:
+            lib().rma_names_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HitPrint:
+    """Scanner.print_hits()'s result: what rnamotif writes for n records, as bytes on the scanner's device.
+
+    bytes   uint8 [T]     the '>sid sdef' line and the hit line of every printed record, in the order given
+    off     int64 [n+1]   record h is bytes[off[h]:off[h+1]], empty where it is not printed
+    header  bytes         the three '#RM' lines rnamotif writes in front of its first hit"""
+
+    def __init__(self, data, off, header: bytes):
+        self.bytes, self.off, self.header = data, off, header
+
+    def record(self, h: int) -> bytes:
+        """The two lines of record h (one copy), b"" for a record that is not printed."""
+        a, b = (int(x) for x in self.off[h:h + 2].cpu())
+        return bytes(self.bytes[a:b].cpu().numpy().tobytes())
+
+    def write(self, fp, header: bool = True) -> int:
+        """All the bytes to the binary file fp, one device-to-host copy; with header, the '#RM' lines first when at
+        least one record is printed -- nothing at all otherwise, as rnamotif writes nothing without a hit.  Returns the
+        bytes written."""
+        data = self.bytes.cpu().numpy().tobytes()
+        if not data:
+            return 0
+        if header:
+            fp.write(self.header)
+        fp.write(data)
+        return len(data) + (len(self.header) if header else 0)
+
+
 class Scanner:
     """The motif program on one GPU (RM_fm_init + RM_find_motif)."""
 
@@ -943,6 +1026,63 @@ class Scanner:
             # (the records are read by a kernel queued behind this stream: torch keeps their memory until it has run)
             hits.record_stream(stream)
         return HitScores(*out)
+
+    def print_hits(self, db: Database, hits, scores: HitScores, names: Optional[EntryNames] = None, accepted_only: bool = True,
+                   letters: Optional[bytes] = None) -> HitPrint:
+        """These records as rnamotif prints them, on the GPU (rma_hit_print; the rule is csrc/rm_hitprint.h's, what
+        HitPrinter::print does on the host): a HitPrint whose bytes, behind its header, are what Replay.device() writes
+        for the same records and names -- one device-to-host copy and a write away from rnamotif's stdout.  hits, db and
+        letters as score() takes them; scores: score(db, hits, program, text=True) of the same records, whose text_bytes
+        are the score column of every line (a HitScores without text is refused); names: EntryNames(scanner, db, sids,
+        sdefs), default: a table of the default names, made on the first such call and kept with the database until it
+        is closed; accepted_only: print scores.accept's records
+        (False: every record, a rejected one with the empty score column it has).  The tensors are torch's and ready on
+        torch's current stream; the call waits once, for the total length.  A malformed record and a text_len outside
+        its row are refused (RnamotifError naming the record) before anything is written.  Score programs the device
+        refuses -- HOLD / RELEASE, NAME, carried variables -- keep Replay.device()."""
+        import torch
+        hits, n, dev, cur, letters = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner",
+                                                  "its hits are printed by Replay.batch() or pack()", letters)
+        if not isinstance(scores, HitScores):
+            raise TypeError(f"scores is a {type(scores).__name__}, not a HitScores")
+        if scores.text_bytes is None or scores.text_len is None:
+            raise ValueError("scores has no text: the score column of every line is needed, score(..., text=True) delivers it")
+        tb, tl, acc = scores.text_bytes, scores.text_len, scores.accept
+        if tb.dtype != torch.uint8 or tb.ndim != 2 or int(tb.shape[0]) != n or tb.device != dev or not tb.is_contiguous():
+            raise ValueError(f"scores.text_bytes must be a contiguous uint8 tensor [{n}, W] on {dev}")
+        if tl.dtype != torch.int32 or tuple(tl.shape) != (n,) or tl.device != dev or not tl.is_contiguous():
+            raise ValueError(f"scores.text_len must be a contiguous int32 tensor [{n}] on {dev}")
+        if accepted_only and (acc.dtype != torch.bool or tuple(acc.shape) != (n,) or acc.device != dev or not acc.is_contiguous()):
+            raise ValueError(f"scores.accept must be a contiguous bool tensor [{n}] on {dev}")
+        if names is not None and (not isinstance(names, EntryNames) or not names._h):
+            raise ValueError("names: an open EntryNames is needed")
+        L = lib()
+        head = C.create_string_buffer(1 << 16)
+        m = L.rma_print_header(self.descr._h, head, len(head))
+        if m < 0 or m >= len(head):
+            raise RnamotifError(f"rma_print_header: {m}")
+        if names is None:
+            # the default table, made on the first such call and kept with the database until it is closed
+            names = getattr(db, "_default_names", None)
+            if names is None or not names._h:
+                names = db._default_names = EntryNames(self, db)
+        nh = names._h
+        width = int(tb.shape[1])
+        err = C.create_string_buffer(_ERRLEN)
+        stream = cur.cuda_stream
+        total = C.c_int64(0)
+        accept = acc.data_ptr() if accepted_only and n else None
+        _check(L.rma_hit_print_size(self._h, db._h, nh, hits.data_ptr() if n else None, n, accept, tl.data_ptr() if n else None,
+                                    C.byref(total), stream, err, _ERRLEN), err)
+        t = int(total.value)
+        p = HitPrint(torch.empty(t, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev), head.raw[:m])
+        _check(L.rma_hit_print(self._h, db._h, nh, hits.data_ptr() if n else None, n, letters, accept,
+                               tb.data_ptr() if n and width else None, width, tl.data_ptr() if n else None, t,
+                               p.bytes.data_ptr() if t else None, p.off.data_ptr(), stream, err, _ERRLEN), err)
+        # (the inputs are read by kernels queued behind this stream: torch keeps their memory until those have run)
+        for x in (hits, tb, tl) + ((acc,) if accepted_only else ()):
+            x.record_stream(cur)
+        return p
 
     def seq_check(self, db: Database, hits, check: Optional[SeqCheck] = None, letters: Optional[bytes] = None, budget: int = 0,
                   fixed: bool = True) -> SeqChecked:

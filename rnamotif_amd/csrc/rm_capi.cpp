@@ -10,8 +10,10 @@
 #include "rm_hitwin.h"
 #include "rm_score_image.h"
 #include "rm_seqcheck.h"
+#include <algorithm>
 #include <cctype>
 #include <cstddef>
+#include <cstdint>
 #include <cstring>
 #include <cstdlib>
 #include <memory>
@@ -70,23 +72,46 @@ extern "C" const rma_efndata_t *rma_descr_efndata( const rma_descr_t *d ) { retu
 extern "C" int rma_descr_minlen( const rma_descr_t *d ) { return d->pr.descr->dminlen; }
 extern "C" int rma_descr_maxlen( const rma_descr_t *d ) { return d->pr.descr->dmaxlen; }
 
-// the fields of the "#RM descr" line, as the printer writes them
-extern "C" size_t rma_descr_names( const rma_descr_t *d, char *buf, size_t buflen )
+// HitPrinter::header's three lines; false where no stream in memory opens
+static bool header_text( const rma_descr_t *d, std::string *out )
 {
 	char	*text = nullptr;
 	size_t	len = 0;
 	FILE	*fp = open_memstream( &text, &len );
 	if( fp == nullptr )
-		return 0;
+		return false;
 	rma::HitPrinter( *d->pr.descr, fp ).header( fp );
 	fclose( fp );
-	std::string	line;
-	const char	*key = "#RM descr ", *at = text != nullptr ? strstr( text, key ) : nullptr;
+	out->assign( text != nullptr ? text : "", text != nullptr ? len : 0 );
+	free( text );
+	return true;
+}
+
+// what rnamotif prints in front of its first hit
+extern "C" int rma_print_header( const rma_descr_t *d, char *buf, size_t buflen )
+{
+	std::string	text;
+	if( d == nullptr || !header_text( d, &text ) || text.size() > size_t( INT32_MAX ) )
+		return -1;
+	if( buf != nullptr && buflen > 0 ){
+		const size_t	m = std::min( text.size(), buflen - 1 );
+		memcpy( buf, text.data(), m );
+		buf[ m ] = '\0';
+	}
+	return int( text.size() );
+}
+
+// the fields of the "#RM descr" line, as the printer writes them
+extern "C" size_t rma_descr_names( const rma_descr_t *d, char *buf, size_t buflen )
+{
+	std::string	text, line;
+	if( !header_text( d, &text ) )
+		return 0;
+	const char	*key = "#RM descr ", *at = strstr( text.c_str(), key );
 	if( at != nullptr ){
 		at += strlen( key );
 		line.assign( at, strcspn( at, "\n" ) );
 	}
-	free( text );
 	if( buf != nullptr && buflen > 0 ){
 		strncpy( buf, line.c_str(), buflen - 1 );
 		buf[ buflen - 1 ] = '\0';

@@ -6,7 +6,9 @@
 // Of a scan they need nothing: a scanner's program and device, a database's tables and text (rm_scanner_impl.h), and
 // scratch of their own.  Last rma_score_hits (rm_score_dev.hip): the score section's MAIN over records, the rule of
 // rm_score_core.h on an image of rm_score_image.h -- and, for the records of a loose descriptor ahead of it,
-// rma_seqcheck_hits (rm_seqcheck_dev.hip): the seq= expressions themselves, the rule of rm_seqcheck.h.  What they all do
+// rma_seqcheck_hits (rm_seqcheck_dev.hip): the seq= expressions themselves, the rule of rm_seqcheck.h.  At the end of
+// the chain rma_hit_print (rm_hitprint_dev.hip): the records and their score columns as the lines rnamotif prints, the
+// rule of rm_hitprint.h, with the entries' names from a table rma_names_create puts on the device.  What they all do
 // first is written once:
 //   record_call_args    the database, the records and the device refused or accepted
 //   letters_on_device   the table the window bytes go through
@@ -23,6 +25,7 @@
 #include "rm_hitalign_dev.h"
 #define RMD_FN		static inline
 #define RMD_FN_MEMBER	inline
+#include "rm_hitprint_dev.h"
 #include "rm_structenergy.h"
 #include "rm_structenergy_dev.h"
 #include "rm_score_core.h"
@@ -1158,4 +1161,294 @@ extern "C" void rma_seqcheck_info( const rma_seqcheck_t *sq, int32_t info[ 8 ] )
 		( void )hipGetLastError();
 	info[ 6 ] = priv;
 	info[ 7 ] = regs;
+}
+
+// ---------------------------------------------------------------- the names of a database's entries on the device
+// rma_names_create(): every sid and sdef of a database as one run of bytes and 2 n + 1 offsets (rm_hitprint_dev.h), copied
+// once, on the upload stream of the database's device behind the database's own words.  The host copies stay with the
+// table: the copies read them.  rma_names_destroy() waits for the upload and for the last kernel that read the table.
+struct rma_names {
+	const rma_db	*db = nullptr;	// (for the words of a refusal only: the database may be gone)
+	uint64_t	db_serial = 0;	// rma_db::serial of the database the table was made for
+	int	device = 0;
+	int32_t	n = 0;
+	std::vector<int64_t>	h_off;
+	std::vector<uint8_t>	h_bytes;
+	rma::DevMem	d_off, d_bytes;
+	rma::Event	ready;		// the upload is complete (recorded on the upload stream)
+	rma::Event	used;		// behind the last kernels that read the table
+};
+
+extern "C" void rma_names_destroy( rma_names_t *names )
+{
+	if( names == nullptr )
+		return;
+	( void )hipSetDevice( names->device );
+	if( names->ready.get() != nullptr )
+		( void )hipEventSynchronize( names->ready.get() );
+	if( names->used.get() != nullptr )
+		( void )hipEventSynchronize( names->used.get() );
+	delete names;
+}
+
+extern "C" int rma_names_create( rma_scanner_t *sc, const rma_db_t *db, const char *const *sids, const int64_t *sid_len,
+	const char *const *sdefs, const int64_t *sdef_len, int32_t n, rma_names_t **out, char *err, size_t errlen )
+{
+	const char	*who = "rma_names_create";
+	if( out != nullptr )
+		*out = nullptr;
+	if( sc == nullptr || db == nullptr || out == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, sc == nullptr ? "scanner" : db == nullptr ? "database" : "room for the table" );
+		return 1;
+	}
+	if( !rma::is_device_db( db ) ){
+		snprintf( err, errlen, "%s: the database (%p) was not made by rma_db_create_device() or has been destroyed", who,
+			static_cast<const void *>( db ) );
+		return 1;
+	}
+	if( db->device != sc->device ){
+		snprintf( err, errlen, "%s: the database is on device %d, the scanner on device %d", who, db->device, sc->device );
+		return 1;
+	}
+	if( n != db->n_seq ){
+		snprintf( err, errlen, "%s: names of %d entries, the database has %d", who, n, db->n_seq );
+		return 1;
+	}
+	std::unique_ptr<rma_names, void ( * )( rma_names * )>	made( new rma_names, rma_names_destroy );
+	rma_names	*t = made.get();
+	t->db = db;
+	t->db_serial = db->serial;
+	t->device = db->device;
+	t->n = n;
+	t->h_off.reserve( 2 * size_t( n ) + 1 );
+	t->h_off.push_back( 0 );
+	// one name: the caller's (a length given: no NUL inside it), or the default
+	auto add = [&]( const char *p, const int64_t *len, int e, const std::string &dflt, const char *what ) -> int {
+		int64_t	m = int64_t( dflt.size() );
+		if( p == nullptr )
+			p = dflt.data();
+		else if( len == nullptr )
+			m = int64_t( strlen( p ) );
+		else{
+			m = len[ e ];
+			const void	*nul = m > 0 ? memchr( p, 0, size_t( m ) ) : nullptr;
+			if( m < 0 || nul != nullptr ){
+				if( m < 0 )
+					snprintf( err, errlen, "%s: entry %d: its %s has a length of %lld", who, e, what, ( long long )m );
+				else
+					snprintf( err, errlen, "%s: entry %d: its %s has a NUL at byte %lld of %lld: rnamotif would print it up to there", who, e, what,
+						( long long )( static_cast<const char *>( nul ) - p ), ( long long )m );
+				return 1;
+			}
+		}
+		t->h_bytes.insert( t->h_bytes.end(), p, p + m );
+		t->h_off.push_back( int64_t( t->h_bytes.size() ) );
+		return 0;
+	};
+	const bool	own = db->sids.size() == size_t( n ) && db->sdefs.size() == size_t( n );
+	for( int e = 0; e < n; e++ ){
+		// the defaults are the replay's: the entry's number, no definition -- or the names the database has read itself
+		// (for one missing name among given ones as for a missing array)
+		const std::string	sid = own ? db->sids[ size_t( e ) ] : std::to_string( e );
+		const std::string	sdef = own ? db->sdefs[ size_t( e ) ] : std::string();
+		if( add( sids != nullptr ? sids[ e ] : nullptr, sid_len, e, sid, "name" ) )
+			return 1;
+		const int64_t	m = t->h_off.back() - t->h_off[ t->h_off.size() - 2 ];
+		if( m > rma::HP_MAX_SID ){
+			snprintf( err, errlen, "%s: entry %d: its name has %lld bytes: rnamotif prints the first %d of a name, which the device does not restate",
+				who, e, ( long long )m, rma::HP_MAX_SID );
+			return 1;
+		}
+		if( add( sdefs != nullptr ? sdefs[ e ] : nullptr, sdef_len, e, sdef, "definition" ) )
+			return 1;
+	}
+	HIPCHK( hipSetDevice( db->device ) );
+	HIPCHK( t->d_off.exact( t->h_off.size() * sizeof( int64_t ) ) );
+	HIPCHK( t->d_bytes.exact( std::max<size_t>( t->h_bytes.size(), 256 ) ) );
+	HIPCHK( t->ready.create( hipEventDisableTiming ) );
+	HIPCHK( t->used.create( hipEventDisableTiming ) );
+	hipStream_t	up = rma::upload_stream( db );
+	HIPCHK( hipStreamWaitEvent( up, db->ready.get(), 0 ) );
+	HIPCHK( hipMemcpyAsync( t->d_off.as<void>(), t->h_off.data(), t->h_off.size() * sizeof( int64_t ), hipMemcpyHostToDevice, up ) );
+	if( !t->h_bytes.empty() )
+		HIPCHK( hipMemcpyAsync( t->d_bytes.as<void>(), t->h_bytes.data(), t->h_bytes.size(), hipMemcpyHostToDevice, up ) );
+	HIPCHK( hipEventRecord( t->ready.get(), up ) );
+	*out = made.release();
+	return 0;
+}
+
+// ---------------------------------------------------------------- hit records as rnamotif prints them
+// rma_hit_print_size() / rma_hit_print(): the size kernel of rm_hitprint_dev.hip and the scan of rm_hitwin_dev.hip in
+// chunks of HW_CHUNK records, then the fill kernel, on the stream of the scanner's span scratch as rma_hit_structures
+// runs its kernels: a chunk's offsets count from its first record, the bytes of the chunks before it wait in a word on
+// the device (*hs_carry), so no chunk needs the host.  The size kernel checks each record, so the calls have no pass of
+// their own for the check.  Words of the scratch's d_bad: [ 0 ] the least index of a bad record, [ 3 ] of a bad
+// text_len; [ 4 ], [ 5 ] where the fill call's second pass over a later chunk puts them (the same records, already judged).
+namespace {
+
+struct PrintCall {
+	rma_scanner_t	*sc;
+	const rma_db	*db;
+	rma_names	*names;
+	const int32_t	*d_hits;
+	int64_t	n_hits;
+	const uint8_t	*d_accept;
+	const int32_t	*d_text_len;
+	int32_t	text_width;
+};
+
+rma::HitPrintBatch print_batch( const PrintCall &c, int64_t c0, int64_t cn )
+{
+	const int	stride = rma_hit_stride( &c.sc->prog );
+	return rma::HitPrintBatch{ c.d_hits + c0 * stride, ( long long )cn, ( long long )c0, stride, rma::hitwin_shape( c.sc->prog ), c.db->d_slen,
+		c.db->d_text_start, c.db->n_seq, c.d_accept != nullptr ? c.d_accept + c0 : nullptr, c.d_text_len + c0, c.text_width,
+		rma::HitPrintNames{ c.names->d_bytes.as<uint8_t>(), c.names->d_off.as<int64_t>() } };
+}
+
+// What both calls do first: the scanner, the database, the records, the names and the two inputs every record has.
+int hit_print_args( const char *who, const PrintCall &c, char *err, size_t errlen )
+{
+	if( c.sc == nullptr || c.db == nullptr || c.names == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, c.sc == nullptr ? "scanner" : c.db == nullptr ? "database" : "names" );
+		return 1;
+	}
+	if( hit_structures_args( c.sc, c.db, c.d_hits, c.n_hits, who, err, errlen ) )
+		return 1;
+	// (by the database's serial number: a later database may lie where the table's lay)
+	if( c.names->db_serial != c.db->serial || c.names->n != c.db->n_seq ){
+		snprintf( err, errlen, "%s: the names were made for another database (%p) than this one (%p): nothing printed", who,
+			static_cast<const void *>( c.names->db ), static_cast<const void *>( c.db ) );
+		return 1;
+	}
+	if( c.n_hits == 0 )
+		return 0;
+	if( c.d_text_len == nullptr ){
+		snprintf( err, errlen, "%s: %lld records: bad arguments", who, ( long long )c.n_hits );
+		return 1;
+	}
+	if( rma::check_device_bytes( c.d_text_len, c.sc->device, 0, c.n_hits * 4, "the text's lengths", err, errlen ) ||
+		( c.d_accept != nullptr && rma::check_device_bytes( c.d_accept, c.sc->device, 0, c.n_hits, "the accept flags", err, errlen ) ) )
+		return 1;
+	return 0;
+}
+
+// One chunk's sizes and offsets into the scratch; the bad words as hit_print_sizes takes them
+int hit_print_sizes_of( const PrintCall &c, int64_t c0, int64_t cn, unsigned long long *bad, unsigned long long *bad_text, char *err, size_t errlen )
+{
+	rma::HitWindowScratch	*s = c.sc->post->win;
+	HIPCHK( rma::hit_print_sizes( print_batch( c, c0, cn ), s->d_len, bad, bad_text, s->stream.get() ) );
+	size_t	tb = s->d_tmp.bytes();
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp.as<void>(), &tb, s->stream.get() ) );
+	return 0;
+}
+
+// Every record checked on the device and the bytes of their lines counted (n_hits > 0, hit_print_args has passed): one
+// synchronisation.  A call of one chunk leaves that chunk's offsets in the scratch.
+int hit_print_count( const char *who, const PrintCall &c, void *stream, int64_t *total, char *err, size_t errlen )
+{
+	rma::HitPost	&p = *c.sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream.get();
+	if( check_records( s, c.db, c.sc->prog, c.d_hits, c.n_hits, stream, false, p.hs_carry(), sizeof( int64_t ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( st, c.names->ready.get(), 0 ) );
+	HIPCHK( hipMemsetAsync( s->d_bad + 3, 0xff, sizeof( unsigned long long ), st ) );
+	for( int64_t c0 = 0; c0 < c.n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, c.n_hits - c0 );
+		if( hit_print_sizes_of( c, c0, cn, s->d_bad, s->d_bad + 3, err, errlen ) )
+			return 1;
+		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
+	}
+	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + 2, s->d_bad + 3, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipEventRecord( c.names->used.get(), st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( s->h_bad[ 0 ] != ~0ull )
+		return bad_record( s, c.db, c.sc->prog, c.d_hits, int64_t( s->h_bad[ 0 ] ), nullptr, "printed", err, errlen );
+	if( s->h_bad[ 2 ] != ~0ull ){
+		const int64_t	h = int64_t( s->h_bad[ 2 ] );
+		int32_t	len = 0;
+		HIPCHK( hipMemcpyAsync( &len, c.d_text_len + h, sizeof( len ), hipMemcpyDeviceToHost, st ) );
+		HIPCHK( hipStreamSynchronize( st ) );
+		if( c.text_width == INT32_MAX )
+			snprintf( err, errlen, "%s: record %lld: a score column of %d bytes: nothing printed", who, ( long long )h, len );
+		else
+			snprintf( err, errlen, "%s: record %lld: a score column of %d bytes, outside the [0, %d] of text_width: nothing printed", who,
+				( long long )h, len, c.text_width );
+		return 1;
+	}
+	*total = int64_t( s->h_bad[ 1 ] );
+	return 0;
+}
+
+}	// namespace
+
+extern "C" int rma_hit_print_size( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *d_accept, const int32_t *d_text_len, int64_t *total, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_print_size";
+	if( total == nullptr ){
+		snprintf( err, errlen, "%s: no room for the total", who );
+		return 1;
+	}
+	*total = 0;
+	// (the size call knows no row width: any length from 0 passes here, the fill call holds it to its text_width)
+	const PrintCall	c{ sc, db, const_cast<rma_names_t *>( names ), d_hits, n_hits, d_accept, d_text_len, INT32_MAX };
+	if( hit_print_args( who, c, err, errlen ) )
+		return 1;
+	return n_hits == 0 ? 0 : hit_print_count( who, c, stream, total, err, errlen );
+}
+
+extern "C" int rma_hit_print( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *letters, const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width, const int32_t *d_text_len,
+	int64_t total, uint8_t *d_out, int64_t *d_off, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_print";
+	const PrintCall	c{ sc, db, const_cast<rma_names_t *>( names ), d_hits, n_hits, d_accept, d_text_len, text_width };
+	if( hit_print_args( who, c, err, errlen ) )
+		return 1;
+	if( total < 0 || total > INT64_MAX / 16 || d_off == nullptr || ( total > 0 && d_out == nullptr ) || text_width < 0 ||
+		( n_hits > 0 && text_width > 0 && ( d_text_bytes == nullptr || n_hits > ( int64_t( 1 ) << 40 ) / text_width ) ) ){
+		snprintf( err, errlen, "%s: %lld bytes, score columns in rows of %d bytes: bad arguments", who, ( long long )total, text_width );
+		return 1;
+	}
+	// the outputs and the score columns: the caller's, each inside its allocation on the scanner's device
+	if( rma::check_device_bytes( d_off, sc->device, 0, ( n_hits + 1 ) * 8, "the offsets", err, errlen ) ||
+		( total > 0 && rma::check_device_bytes( d_out, sc->device, 0, total, "the printed bytes", err, errlen ) ) ||
+		( n_hits > 0 && text_width > 0 && rma::check_device_bytes( d_text_bytes, sc->device, 0, n_hits * text_width, "the score columns", err, errlen ) ) )
+		return 1;
+	hipStream_t	caller = static_cast<hipStream_t>( stream );
+	int64_t	found = 0;
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	// the letters as rma_hit_structures takes them, on their way ahead of the count, whose synchronisation leaves the
+	// page-locked copy free for the next call
+	if( n_hits > 0 && ( letters_on_device( sc->post->win, db, letters, &tab, &codes, err, errlen ) ||
+		hit_print_count( who, c, stream, &found, err, errlen ) ) )
+		return 1;
+	if( found != total ){
+		snprintf( err, errlen, "%s: the lines of the %lld records have %lld bytes, not the %lld of `total`: nothing printed", who,
+			( long long )n_hits, ( long long )found, ( long long )total );
+		return 1;
+	}
+	if( n_hits == 0 ){
+		HIPCHK( hipMemsetAsync( d_off, 0, sizeof( int64_t ), caller ) );
+		return 0;
+	}
+	rma::HitPost	&p = *sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream.get();
+	HIPCHK( hipMemsetAsync( p.hs_carry(), 0, sizeof( int64_t ), st ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		// (a call of one chunk: the count's offsets are still there)
+		if( n_hits > HW_CHUNK && hit_print_sizes_of( c, c0, cn, s->d_bad + 4, s->d_bad + 5, err, errlen ) )
+			return 1;
+		HIPCHK( rma::hit_print_fill( print_batch( c, c0, cn ), db->text, tab, codes, d_text_bytes, s->d_off, p.hs_carry(), d_out, d_off + c0,
+			c0 + cn == n_hits, st ) );
+		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
+	}
+	HIPCHK( hipEventRecord( names->used.get(), st ) );
+	return rma::stream_after( caller, st, err, errlen );
 }

@@ -148,6 +148,11 @@ bool rma::is_device_db( const rma_db *db )
 	return g_device_dbs.count( db ) != 0;
 }
 
+hipStream_t rma::upload_stream( const rma_db *db )
+{
+	return db->ctx->upload.get();
+}
+
 extern "C" void rma_db_destroy( rma_db_t *db );
 extern "C" void rma_scanner_destroy( rma_scanner_t *sc );
 extern "C" int rma_scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, char *err, size_t errlen );

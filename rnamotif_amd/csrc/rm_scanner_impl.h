@@ -4,6 +4,8 @@
 // outside csrc/ includes it but the host check of the carved layouts (tests/hostsim/carve_check.cpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <atomic>
+#include <cstdint>
 #include <cstdio>
 #include <memory>
 #include <mutex>
@@ -51,6 +53,8 @@ void	hitpost_free( HitPost *p );	// (null: nothing; the scanner's device is curr
 int	check_device_bytes( const void *p, int device, int64_t lo, int64_t hi, const char *what, char *err, size_t errlen );
 int	stream_after( hipStream_t on, hipStream_t caller, char *err, size_t errlen );
 bool	is_device_db( const rma_db *db );
+// the upload stream of the database's device, on which db->ready was recorded
+hipStream_t	upload_stream( const rma_db *db );
 // efn()'s tables on the scanner's device (current), in the buffers that are there when they are large enough
 int	efn_tables_to_device( rma_scanner *sc, const rma_efndata_t *efn, char *err, size_t errlen );
 
@@ -121,7 +125,16 @@ struct rma_scanner {
 	rma::HitPost	*post = nullptr;	// rma_hit_structures, rma_hit_alignment, rma_prune_hits (rm_hitpost.cpp)
 };
 
+// a number no other database of the process has had: what outlives a database (a table of its entries' names) knows it
+// by this, not by an address the next database may be given
+inline uint64_t next_db_serial()
+{
+	static std::atomic<uint64_t>	last{ 0 };
+	return ++last;
+}
+
 struct rma_db {
+	const uint64_t	serial = next_db_serial();
 	int	device = 0;
 	rma::DevCtx	*ctx = nullptr;
 	rma::Block	blk;			// codes | amask | base_off | slen | pos_lo | pos_hi
