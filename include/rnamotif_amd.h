@@ -600,6 +600,32 @@ int	rma_hit_print( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *nam
 		void *stream, char *err, size_t errlen );
 int	rma_print_header( const rma_descr_t *d, char *buf, size_t buflen );
 
+/* ---- hit records as rmfmt lists them, on the device: what `rmfmt`, `rmfmt -l` (RMA_LIST_LOCUS) or `rmfmt -la`
+ * (RMA_LIST_ACC) makes of rma_hit_print()'s bytes for the same arguments -- the printed records sorted (best score
+ * first where the score column is one number, else by name and position), every field padded to its widest instance,
+ * elements of more than 20 letters abbreviated -- as n_lines lines of line_len bytes each in device memory, with the
+ * permutation: line r is record d_perm[ r ] (csrc/rm_hitlist.h has the rule, shared by the host and the kernels).
+ * The lines written behind rma_print_header()'s bytes are rmfmt's output.  smax <= 0 means rmfmt's 30 000 000: a
+ * listing whose raw temp file would be larger keeps the input order (*mode 0; 1: by score; 2: by name).
+ * Arguments, checks, chunks and names as rma_hit_print takes them.  Refused as well, the least record named and
+ * nothing written: printed records that do not all have the same number (at least one) of score fields -- rmfmt's
+ * result for them depends on the line it read last, which is not restated --, a newline in a score column, a line of
+ * more than 200 fields, a hit line of 50 000 bytes or more; an entry whose name is empty, trims to nothing or holds a
+ * blank, a tab or a newline; letters that map a byte to one of these three.
+ * rma_hit_list_shape() gives the lines, their length, the widths (host: name, score block, comp, offset, len, then one
+ * per column of rma_hit_alignment_shape(); room for 5 + RMA_MAX_ELEMS + 2) and the mode, and synchronises once.
+ * rma_hit_list() checks and measures again, refuses a shape that is not what it finds, then queues the sort and the
+ * fill and returns without waiting for them, ordered with `stream` as rma_hit_print() is. */
+enum { RMA_LIST_WHOLE = 0, RMA_LIST_LOCUS = 1, RMA_LIST_ACC = 2 };
+int	rma_hit_list_shape( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *d_accept /* n_hits or NULL: all */, const uint8_t *d_text_bytes, int32_t text_width,
+		const int32_t *d_text_len /* n_hits */, int32_t name_mode, int64_t smax, int64_t *n_lines, int64_t *line_len,
+		int32_t *widths, int32_t *mode, void *stream, char *err, size_t errlen );
+int	rma_hit_list( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width, const int32_t *d_text_len,
+		int32_t name_mode, int64_t smax, const uint8_t *letters /* 256 or NULL */, int64_t n_lines, int64_t line_len,
+		uint8_t *d_lines /* n_lines * line_len */, int64_t *d_perm /* n_lines */, void *stream, char *err, size_t errlen );
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,10 @@ def lib() -> C.CDLL:
     L.rma_names_destroy.restype = None
     L.rma_hit_print_size.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, vp, C.c_char_p, C.c_size_t]
     L.rma_hit_print.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_char_p, vp, vp, C.c_int32, vp, C.c_int64, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_list_shape.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, C.c_int32, C.c_int64, i64p, i64p,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_list.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_char_p, C.c_int64, C.c_int64,
+                               vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_print_header.argtypes = [vp, C.c_char_p, C.c_size_t]
     _lib = L
     return L
@@ -753,6 +757,34 @@ class HitPrint:
         return len(data) + (len(self.header) if header else 0)
 
 
+class HitList:
+    """Scanner.list_hits()'s result: rmfmt's listing of the printed records, as bytes on the scanner's device.
+
+    lines   uint8 [m, L]  line r of the listing, its newline included: every line has the same length
+    perm    int64 [m]     line r is record perm[r] of the hits given
+    mode    int           1: sorted by score, best first; 2: by name and position; 0: input order (more than smax bytes)
+    widths  int32 [5+c]   the widths of the name, the score block, comp, offset, len and the c element columns
+    header  bytes         the three '#RM' lines rmfmt copies from rnamotif's output"""
+
+    def __init__(self, lines, perm, mode: int, widths, header: bytes):
+        self.lines, self.perm, self.mode, self.widths, self.header = lines, perm, mode, widths, header
+
+    def line(self, r: int) -> bytes:
+        """Line r (one copy)."""
+        return bytes(self.lines[r].cpu().numpy().tobytes())
+
+    def write(self, fp, header: bool = True) -> int:
+        """The listing to the binary file fp, one device-to-host copy; with header, the '#RM' lines first.  Nothing at
+        all when nothing is listed, as rmfmt of empty input writes nothing.  Returns the bytes written."""
+        data = self.lines.cpu().numpy().tobytes() if int(self.lines.shape[0]) else b""
+        if not data:
+            return 0
+        if header:
+            fp.write(self.header)
+        fp.write(data)
+        return len(data) + (len(self.header) if header else 0)
+
+
 class Scanner:
     """The motif program on one GPU (RM_fm_init + RM_find_motif)."""
 
@@ -1027,19 +1059,9 @@ class Scanner:
             hits.record_stream(stream)
         return HitScores(*out)
 
-    def print_hits(self, db: Database, hits, scores: HitScores, names: Optional[EntryNames] = None, accepted_only: bool = True,
-                   letters: Optional[bytes] = None) -> HitPrint:
-        """These records as rnamotif prints them, on the GPU (rma_hit_print; the rule is csrc/rm_hitprint.h's, what
-        HitPrinter::print does on the host): a HitPrint whose bytes, behind its header, are what Replay.device() writes
-        for the same records and names -- one device-to-host copy and a write away from rnamotif's stdout.  hits, db and
-        letters as score() takes them; scores: score(db, hits, program, text=True) of the same records, whose text_bytes
-        are the score column of every line (a HitScores without text is refused); names: EntryNames(scanner, db, sids,
-        sdefs), default: a table of the default names, made on the first such call and kept with the database until it
-        is closed; accepted_only: print scores.accept's records
-        (False: every record, a rejected one with the empty score column it has).  The tensors are torch's and ready on
-        torch's current stream; the call waits once, for the total length.  A malformed record and a text_len outside
-        its row are refused (RnamotifError naming the record) before anything is written.  Score programs the device
-        refuses -- HOLD / RELEASE, NAME, carried variables -- keep Replay.device()."""
+    def _print_args(self, db: Database, hits, scores, names, accepted_only: bool, letters):
+        """What print_hits() and list_hits() check first: the records, the score columns, the names (None: the
+        database's default table) and the header."""
         import torch
         hits, n, dev, cur, letters = _record_args(db, hits, self.device, self.descr.hit_stride, "scanner",
                                                   "its hits are printed by Replay.batch() or pack()", letters)
@@ -1066,6 +1088,24 @@ class Scanner:
             names = getattr(db, "_default_names", None)
             if names is None or not names._h:
                 names = db._default_names = EntryNames(self, db)
+        return hits, n, dev, cur, letters, tb, tl, acc, names, head.raw[:m]
+
+    def print_hits(self, db: Database, hits, scores: HitScores, names: Optional[EntryNames] = None, accepted_only: bool = True,
+                   letters: Optional[bytes] = None) -> HitPrint:
+        """These records as rnamotif prints them, on the GPU (rma_hit_print; the rule is csrc/rm_hitprint.h's, what
+        HitPrinter::print does on the host): a HitPrint whose bytes, behind its header, are what Replay.device() writes
+        for the same records and names -- one device-to-host copy and a write away from rnamotif's stdout.  hits, db and
+        letters as score() takes them; scores: score(db, hits, program, text=True) of the same records, whose text_bytes
+        are the score column of every line (a HitScores without text is refused); names: EntryNames(scanner, db, sids,
+        sdefs), default: a table of the default names, made on the first such call and kept with the database until it
+        is closed; accepted_only: print scores.accept's records
+        (False: every record, a rejected one with the empty score column it has).  The tensors are torch's and ready on
+        torch's current stream; the call waits once, for the total length.  A malformed record and a text_len outside
+        its row are refused (RnamotifError naming the record) before anything is written.  Score programs the device
+        refuses -- HOLD / RELEASE, NAME, carried variables -- keep Replay.device()."""
+        import torch
+        hits, n, dev, cur, letters, tb, tl, acc, names, head = self._print_args(db, hits, scores, names, accepted_only, letters)
+        L = lib()
         nh = names._h
         width = int(tb.shape[1])
         err = C.create_string_buffer(_ERRLEN)
@@ -1075,7 +1115,7 @@ class Scanner:
         _check(L.rma_hit_print_size(self._h, db._h, nh, hits.data_ptr() if n else None, n, accept, tl.data_ptr() if n else None,
                                     C.byref(total), stream, err, _ERRLEN), err)
         t = int(total.value)
-        p = HitPrint(torch.empty(t, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev), head.raw[:m])
+        p = HitPrint(torch.empty(t, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev), head)
         _check(L.rma_hit_print(self._h, db._h, nh, hits.data_ptr() if n else None, n, letters, accept,
                                tb.data_ptr() if n and width else None, width, tl.data_ptr() if n else None, t,
                                p.bytes.data_ptr() if t else None, p.off.data_ptr(), stream, err, _ERRLEN), err)
@@ -1083,6 +1123,43 @@ class Scanner:
         for x in (hits, tb, tl) + ((acc,) if accepted_only else ()):
             x.record_stream(cur)
         return p
+
+    def list_hits(self, db: Database, hits, scores: HitScores, names: Optional[EntryNames] = None, accepted_only: bool = True,
+                  letters: Optional[bytes] = None, name: str = "whole", smax: Optional[int] = None) -> HitList:
+        """These records as rmfmt lists them, on the GPU (rma_hit_list; the rule is csrc/rm_hitlist.h's): a HitList
+        whose lines, behind its header, are what `rmfmt` (name="whole"), `rmfmt -l` ("locus") or `rmfmt -la` ("acc")
+        writes for print_hits(...).write() of the same arguments -- the hits best score first where the score column is
+        one number, else by name and position, every field padded to its widest instance, long elements abbreviated.
+        smax: rmfmt's -smax, default 30 000 000: a listing whose temp lines have more bytes keeps the input order.
+        Everything else as print_hits() takes it.  The call waits twice, for the listing's shape each time; the sort and
+        the fill are queued behind torch's current stream.  Refused (RnamotifError naming the record or the entry)
+        before anything is written: a malformed record, records whose score columns do not all have the same number
+        (at least one) of fields, a newline in a score column, a name that is empty or has a blank in it."""
+        import torch
+        modes = {"whole": 0, "locus": 1, "acc": 2}
+        if name not in modes:
+            raise ValueError(f"name: 'whole', 'locus' or 'acc', not {name!r}")
+        hits, n, dev, cur, letters, tb, tl, acc, names, head = self._print_args(db, hits, scores, names, accepted_only, letters)
+        L = lib()
+        width = int(tb.shape[1])
+        err = C.create_string_buffer(_ERRLEN)
+        stream = cur.cuda_stream
+        accept = acc.data_ptr() if accepted_only and n else None
+        n_lines, line_len, mode = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        widths = np.zeros(107, dtype=np.int32)
+        first = (self._h, db._h, names._h, hits.data_ptr() if n else None, n, accept, tb.data_ptr() if n and width else None, width,
+                 tl.data_ptr() if n else None, modes[name], int(smax) if smax is not None else 0)
+        _check(L.rma_hit_list_shape(*first, C.byref(n_lines), C.byref(line_len), widths.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(mode),
+                                    stream, err, _ERRLEN), err)
+        m, ll = int(n_lines.value), int(line_len.value)
+        out = HitList(torch.empty((m, ll), dtype=torch.uint8, device=dev), torch.empty(m, dtype=torch.int64, device=dev), int(mode.value),
+                      widths[:ll - int(widths.sum())].copy(), head)      # (a line: the widths, a blank or the newline behind each)
+        _check(L.rma_hit_list(*first, letters, m, ll, out.lines.data_ptr() if m else None, out.perm.data_ptr() if m else None,
+                              stream, err, _ERRLEN), err)
+        # (the inputs are read by kernels queued behind this stream: torch keeps their memory until those have run)
+        for x in (hits, tb, tl) + ((acc,) if accepted_only else ()):
+            x.record_stream(cur)
+        return out
 
     def seq_check(self, db: Database, hits, check: Optional[SeqCheck] = None, letters: Optional[bytes] = None, budget: int = 0,
                   fixed: bool = True) -> SeqChecked:

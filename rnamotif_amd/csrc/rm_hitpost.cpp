@@ -8,8 +8,9 @@
 // rm_score_core.h on an image of rm_score_image.h -- and, for the records of a loose descriptor ahead of it,
 // rma_seqcheck_hits (rm_seqcheck_dev.hip): the seq= expressions themselves, the rule of rm_seqcheck.h.  At the end of
 // the chain rma_hit_print (rm_hitprint_dev.hip): the records and their score columns as the lines rnamotif prints, the
-// rule of rm_hitprint.h, with the entries' names from a table rma_names_create puts on the device.  What they all do
-// first is written once:
+// rule of rm_hitprint.h, with the entries' names from a table rma_names_create puts on the device -- and beside it
+// rma_hit_list (rm_hitlist_dev.hip): the same records as rmfmt lists them, sorted and in columns, the rule of
+// rm_hitlist.h.  What they all do first is written once:
 //   record_call_args    the database, the records and the device refused or accepted
 //   letters_on_device   the table the window bytes go through
 //   check_records       behind the caller's stream, the bad-record word reset, every record judged by the span kernel
@@ -26,6 +27,7 @@
 #define RMD_FN		static inline
 #define RMD_FN_MEMBER	inline
 #include "rm_hitprint_dev.h"
+#include "rm_hitlist_dev.h"
 #include "rm_structenergy.h"
 #include "rm_structenergy_dev.h"
 #include "rm_score_core.h"
@@ -92,6 +94,10 @@ struct rma::HitPost {
 	DevMem	d_sq, d_sq_image;
 	PinMem	h_sq;
 	uint64_t	sq_serial = 0;
+	// rma_hit_list: the fixed block (a call's sums, layout and letters) on the device and page-locked; the measured
+	// records, the printed records' indices and the sort's work area of a call
+	DevMem	d_hl, d_hl_rec, d_hl_idx, d_hl_tmp;
+	PinMem	h_hl;
 };
 
 // (the scanner's device is current; the scratch stream is synchronised before anything goes)
@@ -1449,6 +1455,309 @@ extern "C" int rma_hit_print( rma_scanner_t *sc, const rma_db_t *db, const rma_n
 			c0 + cn == n_hits, st ) );
 		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
 	}
+	HIPCHK( hipEventRecord( names->used.get(), st ) );
+	return rma::stream_after( caller, st, err, errlen );
+}
+
+// ---------------------------------------------------------------- hit records as rmfmt lists them
+// rma_hit_list_shape() / rma_hit_list(): the kernels of rm_hitlist_dev.hip on the stream of the scanner's span scratch,
+// as rma_hit_print runs its own.  Both calls measure: every record checked and measured in chunks of HW_CHUNK, a chunk's
+// flags scanned (hit_offsets) and its printed records' indices compacted behind those of the chunks before it (the
+// running count waits in *hs_carry), the call's sums reduced into one block; one wait brings the sums back, and with
+// them the listing's mode, lines and widths or the least refused record.  rma_hit_list then queues the sort of the
+// indices into the caller's permutation and the fill, and returns.  The scratch is the scanner's: one fixed block (the
+// sums, the layout, the letters with their complements) on the device and one page-locked (the sums to start from,
+// the sums found, the layout), and per call the measured records, the indices and the sort's work area, grown behind a
+// wait for the kernels that read them.
+namespace {
+
+constexpr size_t	HL_AT_RESULT = 1024, HL_AT_LAYOUT = 2048, HL_AT_LETTERS = 3072, HL_FIXED_BYTES = 4096;
+static_assert( sizeof( rma::HitListSums ) <= HL_AT_RESULT && sizeof( rma::HitListLayout ) <= HL_AT_LETTERS - HL_AT_LAYOUT, "the fixed block's slots" );
+
+struct ListCall {
+	rma_scanner_t	*sc;
+	const rma_db	*db;
+	rma_names	*names;
+	const int32_t	*d_hits;
+	int64_t	n_hits;
+	const uint8_t	*d_accept, *d_text_bytes;
+	int32_t	text_width;
+	const int32_t	*d_text_len;
+	int	name_mode;
+	int64_t	smax;
+};
+
+struct ListShape {
+	int64_t	n_lines;
+	int	mode, k;
+	int32_t	widths[ rma::HL_MAX_SEGS ];
+	rma::HitListLayout	layout;
+};
+
+// a scratch piece with room for `want` bytes: grown only behind the kernels that read what is there
+int list_room( rma::DevMem &m, size_t want, hipStream_t st, char *err, size_t errlen )
+{
+	if( want <= m.bytes() )
+		return 0;
+	HIPCHK( hipStreamSynchronize( st ) );
+	HIPCHK( m.room( want ) );
+	return 0;
+}
+
+// What both calls do first: the scanner, the database, the records, the names, the inputs every record has -- and what
+// the host knows of the names: rmfmt splits a line at every blank, so a name with one in it, or one that is or trims to
+// nothing, is no field of its line.
+int hit_list_args( const char *who, const ListCall &c, char *err, size_t errlen )
+{
+	if( c.sc == nullptr || c.db == nullptr || c.names == nullptr ){
+		snprintf( err, errlen, "%s: no %s", who, c.sc == nullptr ? "scanner" : c.db == nullptr ? "database" : "names" );
+		return 1;
+	}
+	if( hit_structures_args( c.sc, c.db, c.d_hits, c.n_hits, who, err, errlen ) )
+		return 1;
+	if( c.names->db_serial != c.db->serial || c.names->n != c.db->n_seq ){
+		snprintf( err, errlen, "%s: the names were made for another database (%p) than this one (%p): nothing printed", who,
+			static_cast<const void *>( c.names->db ), static_cast<const void *>( c.db ) );
+		return 1;
+	}
+	if( c.name_mode != rma::HL_WHOLE && c.name_mode != rma::HL_LOCUS && c.name_mode != rma::HL_ACC ){
+		snprintf( err, errlen, "%s: name mode %d: RMA_LIST_WHOLE, RMA_LIST_LOCUS or RMA_LIST_ACC", who, c.name_mode );
+		return 1;
+	}
+	if( c.n_hits == 0 )
+		return 0;
+	if( c.d_text_len == nullptr || c.text_width < 0 || ( c.text_width > 0 && ( c.d_text_bytes == nullptr || c.n_hits > ( int64_t( 1 ) << 40 ) / c.text_width ) ) ){
+		snprintf( err, errlen, "%s: %lld records, score columns in rows of %d bytes: bad arguments", who, ( long long )c.n_hits, c.text_width );
+		return 1;
+	}
+	if( rma::check_device_bytes( c.d_text_len, c.sc->device, 0, c.n_hits * 4, "the text's lengths", err, errlen ) ||
+		( c.d_accept != nullptr && rma::check_device_bytes( c.d_accept, c.sc->device, 0, c.n_hits, "the accept flags", err, errlen ) ) ||
+		( c.text_width > 0 && rma::check_device_bytes( c.d_text_bytes, c.sc->device, 0, c.n_hits * c.text_width, "the score columns", err, errlen ) ) )
+		return 1;
+	for( int32_t e = 0; e < c.names->n; e++ ){
+		const int64_t	lo = c.names->h_off[ 2 * size_t( e ) ], m = c.names->h_off[ 2 * size_t( e ) + 1 ] - lo;
+		const uint8_t	*sid = c.names->h_bytes.data() + lo;
+		int32_t	at;
+		bool	bad = rma::rmlist_name( sid, int32_t( m ), c.name_mode, &at ) == 0;
+		for( int64_t j = 0; j < m && !bad; j++ )
+			bad = sid[ j ] == ' ' || sid[ j ] == '\t' || sid[ j ] == '\n';
+		if( bad ){
+			snprintf( err, errlen, "%s: entry %d: its name is empty, trims to nothing or has a blank, a tab or a newline in it: rmfmt would split the line there: nothing listed",
+				who, e );
+			return 1;
+		}
+	}
+	return 0;
+}
+
+rma::HitListCall list_call( const ListCall &c )
+{
+	rma::HitPost	&p = *c.sc->post;
+	return rma::HitListCall{ c.d_hits, ( long long )c.n_hits, rma_hit_stride( &c.sc->prog ), rma::hitwin_shape( c.sc->prog ), c.db->d_slen,
+		c.db->d_text_start, c.db->n_seq, c.d_accept, c.d_text_len, c.d_text_bytes, c.text_width,
+		rma::HitPrintNames{ c.names->d_bytes.as<uint8_t>(), c.names->d_off.as<int64_t>() }, c.name_mode, p.d_hl_rec.as<rma::HitListRec>() };
+}
+
+// the first two printed records whose numbers of score fields differ (the measured records come to the host: a refusal's path)
+int list_mixed( const char *who, const ListCall &c, hipStream_t st, char *err, size_t errlen )
+{
+	std::vector<rma::HitListRec>	recs( static_cast<size_t>( c.n_hits ) );
+	HIPCHK( hipMemcpyAsync( recs.data(), c.sc->post->d_hl_rec.as<void>(), recs.size() * sizeof( rma::HitListRec ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	int64_t	first = -1;
+	for( int64_t h = 0; h < c.n_hits; h++ ){
+		if( recs[ size_t( h ) ].k < 0 )
+			continue;
+		if( first < 0 )
+			first = h;
+		else if( recs[ size_t( h ) ].k != recs[ size_t( first ) ].k ){
+			rma::rmlist_refusal_mixed( err, errlen, who, ( long long )first, recs[ size_t( first ) ].k, ( long long )h, recs[ size_t( h ) ].k );
+			return 1;
+		}
+	}
+	snprintf( err, errlen, "%s: refused on the device, not on the host (records changed during the call?)", who );
+	return 1;
+}
+
+// Every record checked and measured on the device, the printed ones' indices compacted (n_hits > 0, hit_list_args has
+// passed): one synchronisation.  *shape: what the listing is, or the words of the refusal.
+int hit_list_measure_all( const char *who, const ListCall &c, void *stream, ListShape *shape, char *err, size_t errlen )
+{
+	rma::HitPost	&p = *c.sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream.get();
+	if( !p.d_hl ){
+		rma::DevMem	dev;
+		rma::PinMem	pin;
+		HIPCHK( dev.exact( HL_FIXED_BYTES ) );
+		HIPCHK( pin.exact( HL_FIXED_BYTES ) );
+		*pin.as<rma::HitListSums>() = rma::HitListSums::init();
+		p.d_hl = std::move( dev );
+		p.h_hl = std::move( pin );
+	}
+	if( list_room( p.d_hl_rec, size_t( c.n_hits ) * sizeof( rma::HitListRec ), st, err, errlen ) ||
+		list_room( p.d_hl_idx, size_t( c.n_hits ) * sizeof( int64_t ), st, err, errlen ) )
+		return 1;
+	if( check_records( s, c.db, c.sc->prog, c.d_hits, c.n_hits, stream, false, p.hs_carry(), sizeof( int64_t ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( st, c.names->ready.get(), 0 ) );
+	rma::HitListSums	*d_sums = p.d_hl.as<rma::HitListSums>();
+	const rma::HitListSums	*found = reinterpret_cast<const rma::HitListSums *>( p.h_hl.as<char>() + HL_AT_RESULT );
+	HIPCHK( hipMemcpyAsync( d_sums, p.h_hl.as<void>(), sizeof( rma::HitListSums ), hipMemcpyHostToDevice, st ) );
+	const rma::HitListCall	call = list_call( c );
+	for( int64_t c0 = 0; c0 < c.n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, c.n_hits - c0 );
+		HIPCHK( rma::hit_list_measure( call, c0, cn, s->d_len, d_sums, st ) );
+		size_t	tb = s->d_tmp.bytes();
+		HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp.as<void>(), &tb, st ) );
+		HIPCHK( rma::hit_list_compact( s->d_len, s->d_off, p.hs_carry(), c0, cn, p.d_hl_idx.as<int64_t>(), st ) );
+		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
+	}
+	HIPCHK( hipMemcpyAsync( const_cast<rma::HitListSums *>( found ), d_sums, sizeof( rma::HitListSums ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipEventRecord( c.names->used.get(), st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( found->bad != ~0ull ){
+		const int64_t	h = int64_t( found->bad >> 4 );
+		const int	code = int( found->bad & 15 );
+		if( code < rma::HP_TEXT )
+			return bad_record( s, c.db, c.sc->prog, c.d_hits, h, nullptr, "listed", err, errlen );
+		if( code == rma::HP_TEXT ){
+			int32_t	len = 0;
+			HIPCHK( hipMemcpyAsync( &len, c.d_text_len + h, sizeof( len ), hipMemcpyDeviceToHost, st ) );
+			HIPCHK( hipStreamSynchronize( st ) );
+			snprintf( err, errlen, "%s: record %lld: a score column of %d bytes, outside the [0, %d] of text_width: nothing listed", who,
+				( long long )h, len, c.text_width );
+			return 1;
+		}
+		rma::rmlist_refusal( err, errlen, who, code, ( long long )h );
+		return 1;
+	}
+	if( found->n_lines > 0 && found->k_min != found->k_max )
+		return list_mixed( who, c, st, err, errlen );
+	shape->n_lines = int64_t( found->n_lines );
+	shape->k = shape->n_lines > 0 ? int( found->k_min ) : 1;
+	shape->mode = int64_t( found->temp_bytes ) > c.smax ? 0 : shape->k == 1 && !found->not_number ? 1 : 2;
+	for( int g = 0; g < rma::HL_MAX_SEGS; g++ )
+		shape->widths[ g ] = int32_t( found->width[ g ] );
+	return 0;
+}
+
+// the listing of no records
+void list_nothing( ListShape *shape )
+{
+	shape->n_lines = 0;
+	shape->mode = 1;
+	shape->k = 1;
+	memset( shape->widths, 0, sizeof( shape->widths ) );
+}
+
+// the layout of a measured listing; refused where a line would not fit the 32 bits of its offsets
+int list_layout( const char *who, const rma_program_t &prog, ListShape *shape, char *err, size_t errlen )
+{
+	int64_t	sum = 0;
+	for( int g = 0; g < rma::HL_MAX_SEGS; g++ )
+		sum += int64_t( shape->widths[ g ] ) + 1;
+	if( sum > INT32_MAX / 2 ){
+		snprintf( err, errlen, "%s: lines of %lld bytes: nothing listed", who, ( long long )sum );
+		return 1;
+	}
+	uint8_t	right[ rma::HA_MAX_COLS ];
+	rma::hitalign_directions( prog, right );
+	shape->layout = rma::rmlist_layout( rma::hitwin_shape( prog ), right, shape->widths, shape->k );
+	return 0;
+}
+
+}	// namespace
+
+extern "C" int rma_hit_list_shape( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width, const int32_t *d_text_len, int32_t name_mode, int64_t smax,
+	int64_t *n_lines, int64_t *line_len, int32_t *widths, int32_t *mode, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_list_shape";
+	if( n_lines == nullptr || line_len == nullptr || widths == nullptr || mode == nullptr ){
+		snprintf( err, errlen, "%s: no room for the shape", who );
+		return 1;
+	}
+	const ListCall	c{ sc, db, const_cast<rma_names_t *>( names ), d_hits, n_hits, d_accept, d_text_bytes, text_width, d_text_len, name_mode,
+		smax > 0 ? smax : rma::HL_SMAX };
+	if( hit_list_args( who, c, err, errlen ) )
+		return 1;
+	ListShape	shape;
+	list_nothing( &shape );
+	if( n_hits > 0 && hit_list_measure_all( who, c, stream, &shape, err, errlen ) )
+		return 1;
+	if( list_layout( who, sc->prog, &shape, err, errlen ) )
+		return 1;
+	*n_lines = shape.n_lines;
+	*line_len = shape.layout.line_len;
+	*mode = shape.mode;
+	memcpy( widths, shape.widths, sizeof( shape.widths ) );
+	return 0;
+}
+
+extern "C" int rma_hit_list( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width, const int32_t *d_text_len, int32_t name_mode, int64_t smax,
+	const uint8_t *letters, int64_t n_lines, int64_t line_len, uint8_t *d_lines, int64_t *d_perm, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_list";
+	const ListCall	c{ sc, db, const_cast<rma_names_t *>( names ), d_hits, n_hits, d_accept, d_text_bytes, text_width, d_text_len, name_mode,
+		smax > 0 ? smax : rma::HL_SMAX };
+	if( hit_list_args( who, c, err, errlen ) )
+		return 1;
+	if( letters != nullptr )
+		for( int b = 0; b < 256; b++ )
+			if( letters[ b ] == ' ' || letters[ b ] == '\t' || letters[ b ] == '\n' ){
+				snprintf( err, errlen, "%s: the letters map byte %d to a blank, a tab or a newline: nothing listed", who, b );
+				return 1;
+			}
+	if( n_lines < 0 || line_len < 0 || n_lines > n_hits || ( n_lines > 0 && ( d_lines == nullptr || d_perm == nullptr || line_len > INT64_MAX / 16 / n_lines ) ) ){
+		snprintf( err, errlen, "%s: %lld lines of %lld bytes: bad arguments", who, ( long long )n_lines, ( long long )line_len );
+		return 1;
+	}
+	// the outputs: the caller's, each inside its allocation on the scanner's device
+	if( n_lines > 0 && ( ( line_len > 0 && rma::check_device_bytes( d_lines, sc->device, 0, n_lines * line_len, "the lines", err, errlen ) ) ||
+		rma::check_device_bytes( d_perm, sc->device, 0, n_lines * 8, "the permutation", err, errlen ) ) )
+		return 1;
+	ListShape	shape;
+	list_nothing( &shape );
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	// the letters as rma_hit_print takes them, on their way ahead of the measure pass, whose synchronisation leaves the
+	// page-locked copy free for the next call
+	if( n_hits > 0 && ( letters_on_device( sc->post->win, db, letters, &tab, &codes, err, errlen ) ||
+		hit_list_measure_all( who, c, stream, &shape, err, errlen ) ) )
+		return 1;
+	if( list_layout( who, sc->prog, &shape, err, errlen ) )
+		return 1;
+	if( shape.n_lines != n_lines || shape.layout.line_len != line_len ){
+		snprintf( err, errlen, "%s: the listing of the %lld records has %lld lines of %d bytes, not the %lld lines of %lld bytes given: nothing listed", who,
+			( long long )n_hits, ( long long )shape.n_lines, shape.layout.line_len, ( long long )n_lines, ( long long )line_len );
+		return 1;
+	}
+	if( n_lines == 0 )
+		return 0;
+	rma::HitPost	&p = *sc->post;
+	hipStream_t	st = p.win->stream.get(), caller = static_cast<hipStream_t>( stream );
+	const rma::HitListCall	call = list_call( c );
+	const int64_t	*d_idx = p.d_hl_idx.as<int64_t>();
+	uint8_t	*d_letcmp = p.d_hl.as<uint8_t>() + HL_AT_LETTERS;
+	const rma::HitListLayout	*d_layout = reinterpret_cast<const rma::HitListLayout *>( p.d_hl.as<char>() + HL_AT_LAYOUT );
+	// (the page-locked layout is free: the call before this one has had its copy made by the time the measure pass's wait ended)
+	memcpy( p.h_hl.as<char>() + HL_AT_LAYOUT, &shape.layout, sizeof( shape.layout ) );
+	HIPCHK( hipMemcpyAsync( const_cast<rma::HitListLayout *>( d_layout ), p.h_hl.as<char>() + HL_AT_LAYOUT, sizeof( shape.layout ), hipMemcpyHostToDevice, st ) );
+	HIPCHK( rma::hit_list_letters( tab, codes, d_letcmp, st ) );
+	if( shape.mode == 0 )
+		HIPCHK( hipMemcpyAsync( d_perm, d_idx, size_t( n_lines ) * 8, hipMemcpyDeviceToDevice, st ) );
+	else{
+		// (the library picks its algorithm by size: what a small sort needs is not bounded by the largest one's)
+		size_t	bytes = 0;
+		HIPCHK( rma::hit_list_sort( call, db->text, d_letcmp, shape.mode, d_idx, d_perm, n_lines, nullptr, &bytes, st ) );
+		if( list_room( p.d_hl_tmp, std::max<size_t>( bytes, 256 ), st, err, errlen ) )
+			return 1;
+		bytes = p.d_hl_tmp.bytes();
+		HIPCHK( rma::hit_list_sort( call, db->text, d_letcmp, shape.mode, d_idx, d_perm, n_lines, p.d_hl_tmp.as<void>(), &bytes, st ) );
+	}
+	HIPCHK( rma::hit_list_fill( call, db->text, d_letcmp, d_layout, shape.layout.line_len, d_perm, n_lines, d_lines, st ) );
 	HIPCHK( hipEventRecord( names->used.get(), st ) );
 	return rma::stream_after( caller, st, err, errlen );
 }
