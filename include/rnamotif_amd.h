@@ -626,6 +626,32 @@ int	rma_hit_list( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *name
 		int32_t name_mode, int64_t smax, const uint8_t *letters /* 256 or NULL */, int64_t n_lines, int64_t line_len,
 		uint8_t *d_lines /* n_lines * line_len */, int64_t *d_perm /* n_lines */, void *stream, char *err, size_t errlen );
 
+/* ---- hit records as rm2ct writes them, on the device: what `rm2ct` (RMA_CT_RNAMOTIF) or `rm2ct -t rnaviz`
+ * (RMA_CT_RNAVIZ) makes of rma_hit_print()'s bytes for the same arguments -- per printed record a header line and one
+ * line per base with its number, its neighbours, its partner and its place in the entry -- as one run of bytes in device
+ * memory (csrc/rm_hitct.h has the rule, shared by the host and the kernels).  rm2ct pairs by the words of the
+ * "#RM descr" line, so the call takes them: descr_words is what rma_descr_names() gives for the scanner's descriptor.
+ * The partner is the tool's: counted from 0 in p5/p3, -1 for a context's base.  rnaviz prints the number the tool reads
+ * behind the name with atof(), as a float.
+ * Arguments, checks, chunks, names and the two calls as rma_hit_print takes them: rma_hit_ct_size() returns the bytes of
+ * all records in *total and synchronises once; rma_hit_ct() checks and counts again, refuses another total, queues the
+ * fill and returns without waiting for it, ordered with `stream` as rma_hit_print() is.  Refused before a record is
+ * looked at: a descriptor with a triple or quad helix, in the tool's words; a type that is neither; an entry whose name
+ * is empty or holds a blank, a tab, a newline or another space; letters that map a byte to something that is no ASCII
+ * letter (the tool counts bases with isalpha).  Refused naming the least record, nothing written: a bad record, a
+ * d_text_len[ h ] outside [0, text_width], a newline in a score column, a hit line of 50 000 bytes or more (the tool's
+ * line buffer) and, for rnaviz, a text behind the name that is an inf, nan, 0x or exponent form of strtod's, has more
+ * than 19 digits from its first non-zero digit to its last or behind the point. */
+enum { RMA_CT_RNAMOTIF = 0, RMA_CT_RNAVIZ = 1 };
+int	rma_hit_ct_size( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *d_accept /* n_hits or NULL: all */, const uint8_t *d_text_bytes, int32_t text_width,
+		const int32_t *d_text_len /* n_hits */, int32_t type, const char *descr_words, const uint8_t *letters /* 256 or NULL */,
+		int64_t *total, void *stream, char *err, size_t errlen );
+int	rma_hit_ct( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+		const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width, const int32_t *d_text_len, int32_t type,
+		const char *descr_words, const uint8_t *letters, int64_t total, uint8_t *d_out /* total */, int64_t *d_off /* n_hits + 1 */,
+		void *stream, char *err, size_t errlen );
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,9 @@ def lib() -> C.CDLL:
     L.rma_hit_list.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_char_p, C.c_int64, C.c_int64,
                                vp, vp, vp, C.c_char_p, C.c_size_t]
     L.rma_print_header.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_ct_size.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, C.c_int32, C.c_char_p, C.c_char_p, i64p, vp, C.c_char_p, C.c_size_t]
+    L.rma_hit_ct.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, C.c_int32, C.c_char_p, C.c_char_p, C.c_int64, vp, vp, vp,
+                             C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -757,6 +760,28 @@ class HitPrint:
         return len(data) + (len(self.header) if header else 0)
 
 
+class HitCt:
+    """Scanner.ct_hits()'s result: what rm2ct writes for n records, as bytes on the scanner's device.
+
+    bytes   uint8 [T]     the connect record of every printed record, in the order given: a header line, a line per base
+    off     int64 [n+1]   record h is bytes[off[h]:off[h+1]], empty where it is not printed"""
+
+    def __init__(self, data, off):
+        self.bytes, self.off = data, off
+
+    def record(self, h: int) -> bytes:
+        """The connect record of record h (one copy), b"" for a record that is not printed."""
+        a, b = (int(x) for x in self.off[h:h + 2].cpu())
+        return bytes(self.bytes[a:b].cpu().numpy().tobytes())
+
+    def write(self, fp) -> int:
+        """All the bytes to the binary file fp, one device-to-host copy; no '#RM' lines: rm2ct writes none.  Returns the
+        bytes written."""
+        data = self.bytes.cpu().numpy().tobytes()
+        fp.write(data)
+        return len(data)
+
+
 class HitList:
     """Scanner.list_hits()'s result: rmfmt's listing of the printed records, as bytes on the scanner's device.
 
@@ -1123,6 +1148,41 @@ class Scanner:
         for x in (hits, tb, tl) + ((acc,) if accepted_only else ()):
             x.record_stream(cur)
         return p
+
+    def ct_hits(self, db: Database, hits, scores: HitScores, names: Optional[EntryNames] = None, accepted_only: bool = True,
+                type: str = "rnamotif", letters: Optional[bytes] = None) -> HitCt:
+        """These records as rm2ct writes them, on the GPU (rma_hit_ct; the rule is csrc/rm_hitct.h's): a HitCt whose bytes
+        are what `rm2ct` (type="rnamotif") or `rm2ct -t rnaviz` ("rnaviz") writes for print_hits(...).write() of the same
+        arguments -- per printed record a header line and a line per base: its number, its letter, its neighbours, its
+        partner and its place in the entry.  The partner is the tool's, paired by the words of the '#RM descr' line:
+        counted from 0 in p5/p3, -1 in a context -- where hit_structures' mate[:, 0] + 1 differs.  Everything else as
+        print_hits() takes it.  The call waits once, for the total length; the fill is queued behind torch's current
+        stream.  Refused (RnamotifError) before a record is looked at: a descriptor with a triple or quad helix, with
+        the tool's words; a name that is empty or has a blank in it; letters that are no ASCII letters.  Refused naming
+        the record, nothing written: a malformed record, a newline in a score column, a hit line of 50 000 bytes or
+        more and, for rnaviz, a text behind the name that atof() reads as inf, nan, a 0x or exponent form, or that has
+        more than 19 digits."""
+        import torch
+        types = {"rnamotif": 0, "rnaviz": 1}
+        if type not in types:
+            raise ValueError(f"type: 'rnamotif' or 'rnaviz', not {type!r}")
+        hits, n, dev, cur, letters, tb, tl, acc, names, _ = self._print_args(db, hits, scores, names, accepted_only, letters)
+        L = lib()
+        width = int(tb.shape[1])
+        err = C.create_string_buffer(_ERRLEN)
+        stream = cur.cuda_stream
+        accept = acc.data_ptr() if accepted_only and n else None
+        total = C.c_int64(0)
+        first = (self._h, db._h, names._h, hits.data_ptr() if n else None, n, accept, tb.data_ptr() if n and width else None, width,
+                 tl.data_ptr() if n else None, types[type], " ".join(self.descr.names()).encode(), letters)
+        _check(L.rma_hit_ct_size(*first, C.byref(total), stream, err, _ERRLEN), err)
+        t = int(total.value)
+        out = HitCt(torch.empty(t, dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev))
+        _check(L.rma_hit_ct(*first, t, out.bytes.data_ptr() if t else None, out.off.data_ptr(), stream, err, _ERRLEN), err)
+        # (the inputs are read by kernels queued behind this stream: torch keeps their memory until those have run)
+        for x in (hits, tb, tl) + ((acc,) if accepted_only else ()):
+            x.record_stream(cur)
+        return out
 
     def list_hits(self, db: Database, hits, scores: HitScores, names: Optional[EntryNames] = None, accepted_only: bool = True,
                   letters: Optional[bytes] = None, name: str = "whole", smax: Optional[int] = None) -> HitList:

@@ -10,7 +10,8 @@
 // the chain rma_hit_print (rm_hitprint_dev.hip): the records and their score columns as the lines rnamotif prints, the
 // rule of rm_hitprint.h, with the entries' names from a table rma_names_create puts on the device -- and beside it
 // rma_hit_list (rm_hitlist_dev.hip): the same records as rmfmt lists them, sorted and in columns, the rule of
-// rm_hitlist.h.  What they all do first is written once:
+// rm_hitlist.h -- and rma_hit_ct (rm_hitct_dev.hip): the same records as rm2ct writes them, the rule of rm_hitct.h.
+// What they all do first is written once:
 //   record_call_args    the database, the records and the device refused or accepted
 //   letters_on_device   the table the window bytes go through
 //   check_records       behind the caller's stream, the bad-record word reset, every record judged by the span kernel
@@ -28,6 +29,7 @@
 #define RMD_FN_MEMBER	inline
 #include "rm_hitprint_dev.h"
 #include "rm_hitlist_dev.h"
+#include "rm_hitct_dev.h"
 #include "rm_structenergy.h"
 #include "rm_structenergy_dev.h"
 #include "rm_score_core.h"
@@ -1504,6 +1506,23 @@ int list_room( rma::DevMem &m, size_t want, hipStream_t st, char *err, size_t er
 	return 0;
 }
 
+// The first entry whose name is no field of its hit line for a tool that splits the line at blanks: one that is empty,
+// trims to nothing (name_mode) or holds a blank, a tab or a newline -- any_space: or another of isspace()'s bytes; -1: none.
+int32_t names_first_split( const rma_names &names, int name_mode, bool any_space )
+{
+	for( int32_t e = 0; e < names.n; e++ ){
+		const int64_t	lo = names.h_off[ 2 * size_t( e ) ], m = names.h_off[ 2 * size_t( e ) + 1 ] - lo;
+		const uint8_t	*sid = names.h_bytes.data() + lo;
+		int32_t	at;
+		bool	bad = rma::rmlist_name( sid, int32_t( m ), name_mode, &at ) == 0;
+		for( int64_t j = 0; j < m && !bad; j++ )
+			bad = sid[ j ] == ' ' || sid[ j ] == '\t' || sid[ j ] == '\n' || ( any_space && ( sid[ j ] == '\v' || sid[ j ] == '\f' || sid[ j ] == '\r' ) );
+		if( bad )
+			return e;
+	}
+	return -1;
+}
+
 // What both calls do first: the scanner, the database, the records, the names, the inputs every record has -- and what
 // the host knows of the names: rmfmt splits a line at every blank, so a name with one in it, or one that is or trims to
 // nothing, is no field of its line.
@@ -1534,18 +1553,11 @@ int hit_list_args( const char *who, const ListCall &c, char *err, size_t errlen 
 		( c.d_accept != nullptr && rma::check_device_bytes( c.d_accept, c.sc->device, 0, c.n_hits, "the accept flags", err, errlen ) ) ||
 		( c.text_width > 0 && rma::check_device_bytes( c.d_text_bytes, c.sc->device, 0, c.n_hits * c.text_width, "the score columns", err, errlen ) ) )
 		return 1;
-	for( int32_t e = 0; e < c.names->n; e++ ){
-		const int64_t	lo = c.names->h_off[ 2 * size_t( e ) ], m = c.names->h_off[ 2 * size_t( e ) + 1 ] - lo;
-		const uint8_t	*sid = c.names->h_bytes.data() + lo;
-		int32_t	at;
-		bool	bad = rma::rmlist_name( sid, int32_t( m ), c.name_mode, &at ) == 0;
-		for( int64_t j = 0; j < m && !bad; j++ )
-			bad = sid[ j ] == ' ' || sid[ j ] == '\t' || sid[ j ] == '\n';
-		if( bad ){
-			snprintf( err, errlen, "%s: entry %d: its name is empty, trims to nothing or has a blank, a tab or a newline in it: rmfmt would split the line there: nothing listed",
-				who, e );
-			return 1;
-		}
+	const int32_t	e = names_first_split( *c.names, c.name_mode, false );
+	if( e >= 0 ){
+		snprintf( err, errlen, "%s: entry %d: its name is empty, trims to nothing or has a blank, a tab or a newline in it: rmfmt would split the line there: nothing listed",
+			who, e );
+		return 1;
 	}
 	return 0;
 }
@@ -1758,6 +1770,191 @@ extern "C" int rma_hit_list( rma_scanner_t *sc, const rma_db_t *db, const rma_na
 		HIPCHK( rma::hit_list_sort( call, db->text, d_letcmp, shape.mode, d_idx, d_perm, n_lines, p.d_hl_tmp.as<void>(), &bytes, st ) );
 	}
 	HIPCHK( rma::hit_list_fill( call, db->text, d_letcmp, d_layout, shape.layout.line_len, d_perm, n_lines, d_lines, st ) );
+	HIPCHK( hipEventRecord( names->used.get(), st ) );
+	return rma::stream_after( caller, st, err, errlen );
+}
+
+// ---------------------------------------------------------------- hit records as rm2ct writes them
+// rma_hit_ct_size() / rma_hit_ct(): the size kernel of rm_hitct_dev.hip and the scan of rm_hitwin_dev.hip in chunks of
+// HW_CHUNK records, then the fill kernel, on the stream of the scanner's span scratch with the running total in
+// *hs_carry, as rma_hit_print runs its own.  The descriptor's table (rm_hitct.h) is made per call from the words of the
+// "#RM descr" line and goes to the kernels with their arguments.  Words of the scratch's d_bad: [ 6 ] the least refused
+// record with its reason, [ 7 ] where the fill call's second pass over a later chunk puts it (the same records, already
+// judged).
+namespace {
+
+struct CtCall {
+	PrintCall	p;
+	const uint8_t	*d_text_bytes;
+	int32_t	type;
+	rma::HitCtTable	table;
+};
+
+rma::HitCtBatch ct_batch( const CtCall &c, int64_t c0, int64_t cn )
+{
+	return rma::HitCtBatch{ print_batch( c.p, c0, cn ), c.d_text_bytes, c.type, c.table };
+}
+
+// What both calls do first: rma_hit_print's arguments, then what rm2ct refuses or would misread before it has seen a
+// record -- a triple or quad helix, a type it does not know, a name it would cut, letters it would not count as bases.
+int hit_ct_args( const char *who, CtCall *c, const char *descr_words, const uint8_t *letters, char *err, size_t errlen )
+{
+	const PrintCall	&p = c->p;
+	if( hit_print_args( who, p, err, errlen ) )
+		return 1;
+	if( descr_words == nullptr ){
+		snprintf( err, errlen, "%s: no words of the \"#RM descr\" line (rma_descr_names)", who );
+		return 1;
+	}
+	char	why[ 256 ];
+	if( rma::hitct_table( descr_words, rma::hitalign_n_cols( rma::hitwin_shape( p.sc->prog ) ), &c->table, why, sizeof( why ) ) ){
+		snprintf( err, errlen, "%s: %s", who, why );
+		return 1;
+	}
+	if( c->type != rma::HC_RNAMOTIF && c->type != rma::HC_RNAVIZ ){
+		snprintf( err, errlen, "%s: type %d: RMA_CT_RNAMOTIF or RMA_CT_RNAVIZ", who, c->type );
+		return 1;
+	}
+	const int32_t	e = names_first_split( *p.names, rma::HL_WHOLE, true );
+	if( e >= 0 ){
+		snprintf( err, errlen, "%s: entry %d: its name is empty or has a blank, a tab, a newline or another space in it: rm2ct would cut the name there: nothing written",
+			who, e );
+		return 1;
+	}
+	if( letters != nullptr )
+		for( int b = 0; b < 256; b++ )
+			if( !( ( letters[ b ] >= 'a' && letters[ b ] <= 'z' ) || ( letters[ b ] >= 'A' && letters[ b ] <= 'Z' ) ) ){
+				snprintf( err, errlen, "%s: the letters map byte %d to %d, which is no ASCII letter: rm2ct counts bases with isalpha(): nothing written", who, b,
+					int( letters[ b ] ) );
+				return 1;
+			}
+	if( p.n_hits == 0 )
+		return 0;
+	if( p.text_width < 0 || ( p.text_width > 0 && ( c->d_text_bytes == nullptr || p.n_hits > ( int64_t( 1 ) << 40 ) / p.text_width ) ) ){
+		snprintf( err, errlen, "%s: %lld records, score columns in rows of %d bytes: bad arguments", who, ( long long )p.n_hits, p.text_width );
+		return 1;
+	}
+	if( p.text_width > 0 && rma::check_device_bytes( c->d_text_bytes, p.sc->device, 0, p.n_hits * p.text_width, "the score columns", err, errlen ) )
+		return 1;
+	return 0;
+}
+
+// One chunk's sizes and offsets into the scratch; the bad word as hit_ct_sizes takes it
+int hit_ct_sizes_of( const CtCall &c, int64_t c0, int64_t cn, unsigned long long *bad, char *err, size_t errlen )
+{
+	rma::HitWindowScratch	*s = c.p.sc->post->win;
+	HIPCHK( rma::hit_ct_sizes( ct_batch( c, c0, cn ), s->d_len, bad, s->stream.get() ) );
+	size_t	tb = s->d_tmp.bytes();
+	HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp.as<void>(), &tb, s->stream.get() ) );
+	return 0;
+}
+
+// Every record checked and measured on the device and the bytes of their .ct records counted (n_hits > 0, hit_ct_args has
+// passed): one synchronisation.  A call of one chunk leaves that chunk's offsets in the scratch.
+int hit_ct_count( const char *who, const CtCall &c, void *stream, int64_t *total, char *err, size_t errlen )
+{
+	const PrintCall	&pc = c.p;
+	rma::HitPost	&p = *pc.sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream.get();
+	if( check_records( s, pc.db, pc.sc->prog, pc.d_hits, pc.n_hits, stream, false, p.hs_carry(), sizeof( int64_t ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( st, pc.names->ready.get(), 0 ) );
+	HIPCHK( hipMemsetAsync( s->d_bad + 6, 0xff, sizeof( unsigned long long ), st ) );
+	for( int64_t c0 = 0; c0 < pc.n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, pc.n_hits - c0 );
+		if( hit_ct_sizes_of( c, c0, cn, s->d_bad + 6, err, errlen ) )
+			return 1;
+		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
+	}
+	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad + 6, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipEventRecord( pc.names->used.get(), st ) );
+	HIPCHK( hipStreamSynchronize( st ) );
+	if( s->h_bad[ 0 ] != ~0ull ){
+		const int64_t	h = int64_t( s->h_bad[ 0 ] >> 4 );
+		const int	code = int( s->h_bad[ 0 ] & 15 );
+		if( code < rma::HP_TEXT )
+			return bad_record( s, pc.db, pc.sc->prog, pc.d_hits, h, nullptr, "written", err, errlen );
+		if( code == rma::HP_TEXT ){
+			int32_t	len = 0;
+			HIPCHK( hipMemcpyAsync( &len, pc.d_text_len + h, sizeof( len ), hipMemcpyDeviceToHost, st ) );
+			HIPCHK( hipStreamSynchronize( st ) );
+			snprintf( err, errlen, "%s: record %lld: a score column of %d bytes, outside the [0, %d] of text_width: nothing written", who,
+				( long long )h, len, pc.text_width );
+			return 1;
+		}
+		rma::hitct_refusal( err, errlen, who, code, ( long long )h );
+		return 1;
+	}
+	*total = int64_t( s->h_bad[ 1 ] );
+	return 0;
+}
+
+}	// namespace
+
+extern "C" int rma_hit_ct_size( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width, const int32_t *d_text_len, int32_t type, const char *descr_words,
+	const uint8_t *letters, int64_t *total, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_ct_size";
+	if( total == nullptr ){
+		snprintf( err, errlen, "%s: no room for the total", who );
+		return 1;
+	}
+	*total = 0;
+	CtCall	c{ PrintCall{ sc, db, const_cast<rma_names_t *>( names ), d_hits, n_hits, d_accept, d_text_len, text_width }, d_text_bytes, type, {} };
+	if( hit_ct_args( who, &c, descr_words, letters, err, errlen ) )
+		return 1;
+	return n_hits == 0 ? 0 : hit_ct_count( who, c, stream, total, err, errlen );
+}
+
+extern "C" int rma_hit_ct( rma_scanner_t *sc, const rma_db_t *db, const rma_names_t *names, const int32_t *d_hits, int64_t n_hits,
+	const uint8_t *d_accept, const uint8_t *d_text_bytes, int32_t text_width, const int32_t *d_text_len, int32_t type, const char *descr_words,
+	const uint8_t *letters, int64_t total, uint8_t *d_out, int64_t *d_off, void *stream, char *err, size_t errlen )
+{
+	const char	*who = "rma_hit_ct";
+	CtCall	c{ PrintCall{ sc, db, const_cast<rma_names_t *>( names ), d_hits, n_hits, d_accept, d_text_len, text_width }, d_text_bytes, type, {} };
+	if( hit_ct_args( who, &c, descr_words, letters, err, errlen ) )
+		return 1;
+	if( total < 0 || total > INT64_MAX / 16 || d_off == nullptr || ( total > 0 && d_out == nullptr ) ){
+		snprintf( err, errlen, "%s: %lld bytes: bad arguments", who, ( long long )total );
+		return 1;
+	}
+	// the outputs: the caller's, each inside its allocation on the scanner's device
+	if( rma::check_device_bytes( d_off, sc->device, 0, ( n_hits + 1 ) * 8, "the offsets", err, errlen ) ||
+		( total > 0 && rma::check_device_bytes( d_out, sc->device, 0, total, "the .ct bytes", err, errlen ) ) )
+		return 1;
+	hipStream_t	caller = static_cast<hipStream_t>( stream );
+	int64_t	found = 0;
+	const uint8_t	*tab = nullptr;
+	int	codes = 0;
+	// the letters as rma_hit_print takes them, on their way ahead of the count, whose synchronisation leaves the
+	// page-locked copy free for the next call
+	if( n_hits > 0 && ( letters_on_device( sc->post->win, db, letters, &tab, &codes, err, errlen ) ||
+		hit_ct_count( who, c, stream, &found, err, errlen ) ) )
+		return 1;
+	if( found != total ){
+		snprintf( err, errlen, "%s: the .ct records of the %lld records have %lld bytes, not the %lld of `total`: nothing written", who,
+			( long long )n_hits, ( long long )found, ( long long )total );
+		return 1;
+	}
+	if( n_hits == 0 ){
+		HIPCHK( hipMemsetAsync( d_off, 0, sizeof( int64_t ), caller ) );
+		return 0;
+	}
+	rma::HitPost	&p = *sc->post;
+	rma::HitWindowScratch	*s = p.win;
+	hipStream_t	st = s->stream.get();
+	HIPCHK( hipMemsetAsync( p.hs_carry(), 0, sizeof( int64_t ), st ) );
+	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
+		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
+		// (a call of one chunk: the count's offsets are still there)
+		if( n_hits > HW_CHUNK && hit_ct_sizes_of( c, c0, cn, s->d_bad + 7, err, errlen ) )
+			return 1;
+		HIPCHK( rma::hit_ct_fill( ct_batch( c, c0, cn ), db->text, tab, codes, s->d_off, p.hs_carry(), d_out, d_off + c0, c0 + cn == n_hits, st ) );
+		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
+	}
 	HIPCHK( hipEventRecord( names->used.get(), st ) );
 	return rma::stream_after( caller, st, err, errlen );
 }
