@@ -70,7 +70,7 @@ int	rma_scanner_create( const rma_program_t *prog, const rma_efndata_t *efn, int
 int	rma_scanner_set_efn2data( rma_scanner_t *sc, const rma_efn2data_t *efn2, char *err, size_t errlen );
 /* Launch-shape and diagnostic switches (DESIGN.md has the table).  The RNAMOTIF_* environment is read
  * once, by rma_scanner_create(); the switches that may change between scans change through this call
- * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "struct_wgs", "score_budget", "score_heap", "flush", "efn_light", "host_sort", "timing", "short".
+ * only: "dbg", "pool", "pool_min", "pool_refill", "drain", "glist", "drain_waves", "search_wgs", "struct_wgs", "score_budget", "score_heap", "flush", "efn_light", "host_sort", "spec_tail", "timing", "short".
  * None of them changes the records a scan returns. */
 int	rma_scanner_set_option( rma_scanner_t *sc, const char *name, int value, char *err, size_t errlen );
 /* One scan of eight start positions, thrown away: what the runtime sets up on first use (code objects,
@@ -207,7 +207,8 @@ int	rma_db_read_packed( const rma_db_t *db, uint32_t *codes, uint32_t *amask, in
 /* ---- scan every sequence of db (both strands when the program says so).
  * *hits receives *n_hits records of rma_hit_stride( prog ) words, sorted by
  * (seq, comp, szero, rank, order) = the reference's output order; the memory
- * belongs to the scanner and is valid until its next scan or destruction.
+ * belongs to the scanner and is valid until its next scan BEGINS (rma_scan, rma_scan_begin, rma_scan_device) or its
+ * destruction: a scanner's next begin may write the same memory, or free it, before that scan's end is called.
  * Energies of the program's efn sites are filled in.  The records are candidates before the score section;
  * for a program with loose seq= elements (rma_program_loose() > 0) they are a superset of the reference's
  * candidates until replayed. */
@@ -219,7 +220,12 @@ int	rma_scan( rma_scanner_t *sc, const rma_db_t *db, const int32_t **hits, int64
  * back and returns them as rma_scan() does.  Between the two the host is free: to begin the scan of
  * another scanner (two descriptors over one database run side by side), or to upload the next
  * database (rma_db_create_packed_async).  One scan in flight per scanner.  rma_scan_end's records are
- * rma_scan's: a superset of the candidates for a program with loose seq= elements until replayed. */
+ * rma_scan's: a superset of the candidates for a program with loose seq= elements until replayed.
+ * Lifetime of *hits: until the SAME scanner's next rma_scan_begin() (not only its next end) -- from its second scan on
+ * a scanner's begin enqueues the energies, the ordering and the records' way into that memory behind the kernels
+ * (rma_scanner_last_end below), and may replace the memory by a larger piece.  Read or copy a scan's records before
+ * beginning that scanner's next scan; another scanner's begin touches nothing of it.  The same holds for *d_hits of
+ * rma_scan_end_on_device(). */
 int	rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err, size_t errlen );
 int	rma_scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, char *err, size_t errlen );
 /* rma_scan_end() that leaves the ordered records in HBM (*d_hits is a device pointer, valid until
@@ -247,6 +253,15 @@ int	rma_scanner_last_kernel_ms( rma_scanner_t *sc, float ms[ 3 ], char *err, siz
  * default, when another scanner of the device has a scan in flight as this one begins; 0 never; 1 always).
  * All 0 before the first launch.  Returns 0. */
 int	rma_scanner_last_launch( rma_scanner_t *sc, int out[ 4 ] );
+/* What the scanner's last rma_scan_end() (rma_scan(), rma_scan_end_on_device()) did.  From a scanner's second scan on,
+ * rma_scan_begin() enqueues the scan's tail -- energies, ordering, the records' way back -- behind its kernels, sized by
+ * the scans the scanner has ended; rma_scan_end() then waits once and takes the records, or, when the scan found more
+ * than was planned for or has to be repeated, does the tail again as a first scan does.  Option "spec_tail": -1, the
+ * default, by that rule; 0 never.  dbg, timing and host_sort turn it off, and rma_scan_device() never does it.
+ * out[0] the times the end waited for the scanner's stream, out[1] 1 when it took the records of the tail enqueued
+ * ahead, out[2] launches of the search kernel, out[3] launches of an energy kernel, both from the scan's begin.
+ * Returns 0. */
+int	rma_scanner_last_end( rma_scanner_t *sc, int out[ 4 ] );
 
 /* Records from several scans (the slices of one database searched by several GPUs or hosts, word 0
  * already the database-wide entry number) into the reference's output order: by the five header

@@ -14,10 +14,14 @@ db = scs[0].database(seqs)
 for s in scs:
     s.attach(db)
 pend = None
+ends = {}       # what the steps' ends did (Scanner.last_end(): waits, tail ahead taken, search launches, energy launches) -> steps
 for i in range(60):
     s = scs[i & 1]
     s.scan_begin(db)
     if pend is not None:
         pend.scan_end(copy=False)
+        if hasattr(R.lib(), "rma_scanner_last_end"):
+            ends[pend.last_end()] = ends.get(pend.last_end(), 0) + 1
     pend = s
 pend.scan_end(copy=False)
+print("last_end of 59 steps:", ends, file=sys.stderr)

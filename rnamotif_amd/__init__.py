@@ -125,6 +125,8 @@ def lib() -> C.CDLL:
     L.rma_scanner_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
     if hasattr(L, "rma_scanner_last_launch"):       # (RNAMOTIF_AMD_LIB may name a build from before the call: comparisons in turns)
         L.rma_scanner_last_launch.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, "rma_scanner_last_end"):
+        L.rma_scanner_last_end.argtypes = [vp, C.POINTER(C.c_int)]
     L.rma_scan_device.argtypes = [vp, vp, i64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                   C.c_char_p, C.c_size_t]
     L.rma_replay_open.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_size_t]
@@ -1333,6 +1335,9 @@ class Scanner:
         _check(lib().rma_scan_begin(self._h, db._h, err, _ERRLEN), err)
 
     def scan_end(self, copy: bool = True) -> np.ndarray:
+        """The records of the scan begun with scan_begin(), as scan() returns them.  With copy=False the array is a view of
+        the scanner's own buffer, valid until THIS scanner's next scan_begin() (or scan()): from its second scan on a scanner's
+        begin already writes that buffer, or replaces it -- read the records before beginning the scanner's next scan."""
         L = lib()
         hits = C.POINTER(C.c_int32)()
         n = C.c_int64()
@@ -1357,7 +1362,7 @@ class Scanner:
 
     def scan(self, db: Database, copy: bool = True) -> np.ndarray:
         """All candidates of db in reference order: int32 array [n, hit_stride].  With
-        copy=False the array is a view of the scanner's own buffer, valid until its next scan.
+        copy=False the array is a view of the scanner's own buffer, valid until its next scan begins (scan(), scan_begin()).
         When descr.loose > 0 the records are a superset of rnamotif's candidates until replayed."""
         L = lib()
         hits = C.POINTER(C.c_int32)()
@@ -1387,6 +1392,13 @@ class Scanner:
         (rma_scanner_last_launch); beside is 1 when the shape leaves another scanner's drain kernel room."""
         out = (C.c_int * 4)()
         lib().rma_scanner_last_launch(self._h, out)
+        return out[0], out[1], out[2], out[3]
+
+    def last_end(self) -> Tuple[int, int, int, int]:
+        """(host waits, 1 if the records of the tail enqueued at scan_begin were taken, search launches, energy launches)
+        of the last scan ended (rma_scanner_last_end)."""
+        out = (C.c_int * 4)()
+        lib().rma_scanner_last_end(self._h, out)
         return out[0], out[1], out[2], out[3]
 
     def close(self) -> None:

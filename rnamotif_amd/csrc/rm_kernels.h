@@ -159,6 +159,7 @@ struct rmk_efn_args {
 	const int16_t	*t16;		// efn's tables as int16 (RME_N16 entries, padded to 8), or null
 	const int32_t	*tlkey, *loginc;
 	const rma_efn2data_t	*e2;	// efn2's tables, or null
+	const unsigned long long	*n_dev = nullptr;	// the count on the device, or null: with it the kernels take min( *n_dev, n_hits ) records (n_hits: the room)
 };
 hipError_t	rmk_launch_efn( int grid, hipStream_t s, const rmk_efn_args &a );
 hipError_t	rmk_launch_efn_light( int grid, hipStream_t s, const rmk_efn_args &a );	// (grid: workgroups of 64 lanes)

@@ -30,6 +30,7 @@ void Options::latch()
 	flush = env_int( "RNAMOTIF_FLUSH", -1 );
 	efn_light = env_int( "RNAMOTIF_EFN_LIGHT", -1 );
 	host_sort = env_int( "RNAMOTIF_HOSTSORT", 0 );
+	spec_tail = env_int( "RNAMOTIF_SPEC_TAIL", -1 );
 	timing = getenv( "RNAMOTIF_TIMING" ) != nullptr;
 	if( const char *f = getenv( "RNAMOTIF_SHORT" ) )
 		short_force = f[ 0 ] == '1' ? 1 : f[ 0 ] == '2' ? 2 : 0;
@@ -58,6 +59,7 @@ bool Options::set( const std::string &n, int value )
 	else if( n == "flush" ) flush = value;
 	else if( n == "efn_light" ) efn_light = value;
 	else if( n == "host_sort" ) host_sort = value;
+	else if( n == "spec_tail" ) spec_tail = value;
 	else if( n == "timing" ) timing = value;
 	else if( n == "short" ) short_force = value;
 	else return false;

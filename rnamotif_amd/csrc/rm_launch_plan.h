@@ -32,6 +32,7 @@ struct Options {
 	int	score_budget = 1 << 20;	// instructions of the score section a record of rma_score_hits may take before it stops (RMS_DEFAULT_BUDGET)
 	int	score_heap = 256;	// bytes of heap a record of a score program with text has for the strings it makes (RMS_DEFAULT_HEAP)
 	int	host_sort = 0, timing = 0;
+	int	spec_tail = -1;		// a scan's tail enqueued by rma_scan_begin, ahead of the count (rm_tail_plan.h): -1 by the rule, 0 never
 	int	short_force = -1;	// -1: by the mean entry length, 0 never, 1 always groups of small tiles, 2 always tiles over the concatenation
 	int	tile = 0, qcap = 0;	// forced tile size / queue entries, 0: computed
 	int	spill = -1;		// forced spill area, -1: SPILL_ITEMS

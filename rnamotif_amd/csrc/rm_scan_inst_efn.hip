@@ -3,7 +3,7 @@
 hipError_t rmk_launch_efn( int grid, hipStream_t s, const rmk_efn_args &a )
 {
 	hipLaunchKernelGGL( rma_efn_kernel<EFN_BLOCK>, dim3( unsigned( grid ) ), dim3( EFN_BLOCK ), 0, s,
-		a.d_prog, a.db, a.hits, a.n_hits, a.t16, a.tlkey, a.loginc, a.e2 );
+		a.d_prog, a.db, a.hits, a.n_hits, a.t16, a.tlkey, a.loginc, a.e2, a.n_dev );
 	return hipGetLastError();
 }
 
@@ -19,6 +19,6 @@ hipError_t rmk_preload_efn( void )
 hipError_t rmk_launch_efn_light( int grid, hipStream_t s, const rmk_efn_args &a )
 {
 	hipLaunchKernelGGL( rma_efn_light_kernel<0>, dim3( unsigned( grid ) ), dim3( 64 ), EFN_LIGHT_LDS, s,
-		a.d_prog, a.db, a.hits, a.n_hits, a.t16, a.tlkey, a.loginc, a.e2 );
+		a.d_prog, a.db, a.hits, a.n_hits, a.t16, a.tlkey, a.loginc, a.e2, a.n_dev );
 	return hipGetLastError();
 }

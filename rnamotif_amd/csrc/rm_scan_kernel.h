@@ -2545,8 +2545,17 @@ static_assert( EFN_CACHE <= RMW_MAX, "a cached call is one window of DevSeq::win
 // a wave per SIMD), where the staged form -- 136 KB -- waits until the other scanner's search kernel is through.
 template< int BLOCK, int BIG, bool STAGE >
 __device__ __forceinline__ void efn_body( const rmd_program_t * __restrict__ gP, const DbView &db, int32_t * __restrict__ hits, long long n_hits,
-	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2 )
+	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2,
+	const unsigned long long * __restrict__ n_dev )
 {
+	// (launched before the host knows the count -- rm_tail_plan.h --: the count is where the search and drain kernels left it,
+	// n_hits is the hit buffer's room, and a workgroup whose first candidate lies past the count leaves before it stages anything)
+	if( n_dev != nullptr ){
+		const unsigned long long	found = *n_dev;
+		n_hits = found < ( unsigned long long )n_hits ? ( long long )found : n_hits;
+		if( ( long long )blockIdx.x * BLOCK >= n_hits )
+			return;
+	}
 	// tables staged 16 bytes per lane and step (the device copy is padded to a multiple of 8 entries)
 	__shared__ __align__( 16 ) int16_t	t16_s[ STAGE ? RME_N16_PAD : 8 ];
 	const int16_t	*t16 = g16;
@@ -2590,21 +2599,24 @@ __device__ __forceinline__ void efn_body( const rmd_program_t * __restrict__ gP,
 template< int BLOCK, int BIG = 0 >
 __global__ void __launch_bounds__( BLOCK )
 rma_efn_kernel( const rmd_program_t * __restrict__ gP, DbView db, int32_t * __restrict__ hits, long long n_hits,
-	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2 )
+	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2,
+	const unsigned long long * __restrict__ n_dev )
 {
-	efn_body<BLOCK, BIG, true>( gP, db, hits, n_hits, g16, tlkey, loginc, e2 );
+	__builtin_amdgcn_s_setprio( 3 );	// (enqueued behind its scan's search kernel it may start while another scanner's runs)
+	efn_body<BLOCK, BIG, true>( gP, db, hits, n_hits, g16, tlkey, loginc, e2, n_dev );
 }
 
 // (120 registers: four workgroups of the search instance that walks nothing, at 96 each, leave a SIMD 128)
 template< int BIG = 0 >
 __global__ void __launch_bounds__( 64, 4 )
 rma_efn_light_kernel( const rmd_program_t * __restrict__ gP, DbView db, int32_t * __restrict__ hits, long long n_hits,
-	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2 )
+	const int16_t * __restrict__ g16, const int32_t * __restrict__ tlkey, const int32_t * __restrict__ loginc, const rma_efn2data_t * __restrict__ e2,
+	const unsigned long long * __restrict__ n_dev )
 {
 	// (like the drain kernel in front of it on the stream it runs beside another scanner's search kernel, the youngest wave
 	// on its SIMD: at priority 3 it takes 0.147 against 0.18 ms there and the step of two scanners in turns 0.605 against 0.619)
 	__builtin_amdgcn_s_setprio( 3 );
-	efn_body<64, BIG, false>( gP, db, hits, n_hits, g16, tlkey, loginc, e2 );
+	efn_body<64, BIG, false>( gP, db, hits, n_hits, g16, tlkey, loginc, e2, n_dev );
 }
 
 // ---------------------------------------------------------------- launchers

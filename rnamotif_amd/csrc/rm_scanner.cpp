@@ -252,7 +252,7 @@ extern "C" int rma_scanner_create( const rma_program_t *prog, const rma_efndata_
 	// (63 per Mbase for trna.descr); a scan that finds more is repeated into a buffer of the right
 	// size (count-then-emit, rma_scan_end)
 	HIPCHK( sc->d_hits.exact( ( size_t( 1 ) << 17 ) * sc->dprog.hit_stride * sizeof( int32_t ) ) );
-	HIPCHK( sc->h_ctr.exact( RMK_C_COPIED * sizeof( unsigned long long ) ) );
+	HIPCHK( sc->h_ctr.exact( ( RMK_C_COPIED + 1 ) * sizeof( unsigned long long ) ) );
 	// page-locked room for the records of a usual batch (16 K of them) now, not in the first scan
 	HIPCHK( sc->h_raw.exact( size_t( 16384 ) * sc->dprog.hit_stride * sizeof( int32_t ) ) );
 	if( sc->dsort.reserve( sc->hit_cap(), sc->dprog.hit_stride ) != hipSuccess )
@@ -294,7 +294,7 @@ extern "C" int rma_scanner_set_option( rma_scanner_t *sc, const char *name, int 
 		sc->last_relabelled = false;
 	}else if( !sc->opt.set( n, value ) ){
 		snprintf( err, errlen, "rma_scanner_set_option: no option '%s' that can change after creation "
-			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, beside, struct_wgs, score_budget, score_heap, flush, efn_light, host_sort, timing, short; forget_last)", n.c_str() );
+			"(dbg, pool, pool_min, pool_refill, drain, glist, drain_waves, search_wgs, beside, struct_wgs, score_budget, score_heap, flush, efn_light, host_sort, spec_tail, timing, short; forget_last)", n.c_str() );
 		return 1;
 	}
 	return 0;
@@ -1099,9 +1099,11 @@ static int grow_h_raw( rma_scanner_t *sc, size_t words, char *err, size_t errlen
 	return 0;
 }
 
-static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
+// (tail: the caller enqueues the scan's tail behind the kernels and the counters' copy behind that, launch_tail)
+static int launch_search( rma_scanner_t *sc, char *err, size_t errlen, bool tail = false )
 {
 	const rma_scanner::InFlight	&f = sc->fly;
+	sc->search_launches++;
 	HIPCHK( hipMemsetAsync( sc->counters(), 0, RMK_N_COUNTERS * sizeof( unsigned long long ), sc->stream.get() ) );
 	rmk_search_args	a;
 	a.d_prog = sc->d_prog.as<rmd_program_t>();
@@ -1129,7 +1131,48 @@ static int launch_search( rma_scanner_t *sc, char *err, size_t errlen )
 	}
 	HIPCHK( hipEventRecord( sc->ev[ 1 ].get(), sc->stream.get() ) );
 	// RMK_C_COUNT, RMK_C_QUEUE_NEED / RMK_C_PIECE_OVERFLOW, RMK_C_LIST_RESERVED, RMK_C_FLUSH_QUEUE_NEED: one copy, one wait
-	HIPCHK( hipMemcpyAsync( sc->ctr(), sc->counters(), RMK_C_COPIED * sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream.get() ) );
+	if( !tail )
+		HIPCHK( hipMemcpyAsync( sc->ctr(), sc->counters(), RMK_C_COPIED * sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream.get() ) );
+	return 0;
+}
+
+static int launch_efn( rma_scanner_t *sc, int64_t count, const unsigned long long *n_dev, char *err, size_t errlen );
+
+// The widths of the ordering's key fields for a database (DevHitSort::run).
+struct KeyWidths { int seq, pos, rank; };
+static KeyWidths key_widths( const rma_scanner_t *sc, const rma_db *db )
+{
+	return KeyWidths{ rma::bits_of( unsigned( db->n_seq > 0 ? db->n_seq - 1 : 0 ) ), rma::bits_of( unsigned( db->max_slen ) ),
+		rma::bits_of( unsigned( sc->dprog.w_winsize ) ) };
+}
+
+// What plan_tail() needs of the scanner to say yes: the ordering's buffers for the hit buffer as it is, its work area and
+// the staging buffer for n_sort records -- all of it before anything of the scan is enqueued.  false: no tail ahead.
+static bool tail_room( rma_scanner_t *sc, const rma_db *db, int64_t n_sort, char *err, size_t errlen )
+{
+	const KeyWidths	w = key_widths( sc, db );
+	if( sc->dsort.reserve( sc->hit_cap(), sc->dprog.hit_stride ) != hipSuccess || !sc->dsort.widths_ok( w.seq, w.pos, w.rank ) ||
+		sc->dsort.plan( n_sort, sc->stream.get() ) != hipSuccess ){
+		( void )hipGetLastError();
+		return false;
+	}
+	return grow_h_raw( sc, size_t( n_sort ) * sc->dprog.hit_stride, err, errlen ) == 0;
+}
+
+// The tail of the scan in flight behind its search and drain kernels, sized by f.tail.n_sort on the host and by RMK_C_COUNT
+// on the device: energies, ordering, the records' way back, and last the copy of the counters with the ordering's flag behind
+// them -- rma_scan_end() waits once and reads what it needs to take the records or to do the tail again (tail_verdict).
+static int launch_tail( rma_scanner_t *sc, char *err, size_t errlen )
+{
+	const rma_scanner::InFlight	&f = sc->fly;
+	const int64_t	n_sort = f.tail.n_sort;
+	const unsigned long long	*d_count = sc->counters() + RMK_C_COUNT;
+	if( launch_efn( sc, n_sort, d_count, err, errlen ) )
+		return 1;
+	const KeyWidths	w = key_widths( sc, f.db );
+	// (the gather kernel stores the records into the staging buffer as well: the copy back without a copy of its own)
+	HIPCHK( sc->dsort.run( sc->hits(), n_sort, d_count, sc->counters() + rma_scanner::TAIL_FLAG, sc->raw(), w.seq, w.pos, w.rank, sc->stream.get() ) );
+	HIPCHK( hipMemcpyAsync( sc->ctr(), sc->counters(), ( RMK_C_COPIED + 1 ) * sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream.get() ) );
 	return 0;
 }
 
@@ -1145,7 +1188,8 @@ static void debug_report( rma_scanner_t *sc )
 
 // The search kernel of a scan is on its way when this returns; rma_scan_end() (or search_finish())
 // waits for it.  Two scanners that have begun run side by side on their own streams.
-extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err, size_t errlen )
+// (timed_apart: rma_scan_device() is the caller, which times the kernels apart: no tail behind the search kernel)
+static int scan_begin( rma_scanner_t *sc, const rma_db_t *db, bool timed_apart, char *err, size_t errlen )
 {
 	HIPCHK( hipSetDevice( sc->device ) );
 	if( sc->fly.db != nullptr ){
@@ -1164,6 +1208,8 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 	sc->n_last = 0;
 	sc->last_state = 0;
 	sc->last_relabelled = false;
+	sc->end_waits = sc->search_launches = sc->efn_launches = 0;
+	sc->tail_taken = false;
 	const Layout	*lay = layout_for( sc, db, err, errlen );
 	if( lay == nullptr )
 		return 1;
@@ -1183,6 +1229,7 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 			sc->flying.lower();
 		} } }	unfly{ sc, true };
 	f.plan = rma::LaunchPlan();
+	f.tail = rma::TailPlan();
 	if( lay->n_tiles == 0 ){
 		unfly.armed = false;
 		return 0;
@@ -1211,16 +1258,28 @@ extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err,
 	// the database's upload and the tiling's, on the device's upload stream, come first
 	HIPCHK( hipStreamWaitEvent( sc->stream.get(), db->ready.get(), 0 ) );
 	HIPCHK( hipStreamWaitEvent( sc->stream.get(), lay->ready.get(), 0 ) );
+	// the scan's tail behind its kernels, where the rule allows it and there is room (rm_tail_plan.h)
+	f.tail = rma::plan_tail( sc->count_max, sc->hit_cap(), rma::TailOpts{ sc->opt.spec_tail, sc->opt.dbg, sc->opt.timing, sc->opt.host_sort, timed_apart } );
+	if( f.tail.speculate && !tail_room( sc, db, f.tail.n_sort, err, errlen ) )
+		f.tail = rma::TailPlan();
 	sc->flying.raise( sc->device );		// (nothing is left that can refuse the scan; a launch that fails lowers it again: unfly)
-	if( launch_search( sc, err, errlen ) )
+	if( launch_search( sc, err, errlen, f.tail.speculate ) )
+		return 1;
+	if( f.tail.speculate && launch_tail( sc, err, errlen ) )
 		return 1;
 	unfly.armed = false;
 	return 0;
 }
 
+extern "C" int rma_scan_begin( rma_scanner_t *sc, const rma_db_t *db, char *err, size_t errlen )
+{
+	return scan_begin( sc, db, false, err, errlen );
+}
+
 // Wait for the search kernel of the scan in flight; repeat it while it asks for a larger spill area
 // or hit buffer (count-then-emit).  On return the candidates are in d_hits, unordered, no energies.
-static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, char *err, size_t errlen )
+// (waited: the caller has waited for the stream and the counters of the first launch are on the host)
+static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, char *err, size_t errlen, bool waited = false )
 {
 	rma_scanner::InFlight	&f = sc->fly;
 	*n_hits = 0;
@@ -1229,7 +1288,10 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 	const rmd_program_t	&dp = sc->dprog;
 	unsigned long long	count = 0;
 	for( int attempt = 0; ; attempt++ ){
-		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		if( !( waited && attempt == 0 ) ){
+			HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+			sc->end_waits++;
+		}
 		count = sc->ctr()[ RMK_C_COUNT ];
 		if( sc->opt.dbg )
 			debug_report( sc );
@@ -1297,15 +1359,18 @@ static int search_finish( rma_scanner_t *sc, int64_t *n_hits, float *search_ms, 
 	return 0;
 }
 
-static int launch_efn( rma_scanner_t *sc, int64_t count, char *err, size_t errlen )
+// n_dev: null, or the count on the device -- then `count` is what the grid is planned for and the kernels take
+// min( *n_dev, the hit buffer's room ) records
+static int launch_efn( rma_scanner_t *sc, int64_t count, const unsigned long long *n_dev, char *err, size_t errlen )
 {
 	const rmd_program_t	&dp = sc->dprog;
 	if( !( ( sc->have_efn || sc->d_efn2 ) && dp.n_efn > 0 && count > 0 ) )
 		return 0;
+	sc->efn_launches++;
 	// one workgroup per CU at most (its LDS), each striding over the candidates
 	const int64_t	blocks = std::min<int64_t>( ( count + EFN_BLOCK - 1 ) / EFN_BLOCK, sc->grid_blocks / 8 );
-	rmk_efn_args	a{ sc->d_prog.as<rmd_program_t>(), view_of( sc->fly.db, sc->fly.lay ), sc->hits(), ( long long )count,
-		sc->have_efn ? sc->d_t16.as<int16_t>() : nullptr, sc->d_tlkey.as<int32_t>(), sc->d_loginc.as<int32_t>(), sc->efn2() };
+	rmk_efn_args	a{ sc->d_prog.as<rmd_program_t>(), view_of( sc->fly.db, sc->fly.lay ), sc->hits(), ( long long )( n_dev != nullptr ? sc->hit_cap() : count ),
+		sc->have_efn ? sc->d_t16.as<int16_t>() : nullptr, sc->d_tlkey.as<int32_t>(), sc->d_loginc.as<int32_t>(), sc->efn2(), n_dev };
 	sc->efn_ran = true;
 	HIPCHK( hipEventRecord( sc->ev[ 2 ].get(), sc->stream.get() ) );
 	if( sc->fly.plan.efn_light )
@@ -1338,15 +1403,16 @@ extern "C" int rma_scan_device( rma_scanner_t *sc, const rma_db_t *db, int64_t *
 	*n_hits = 0;
 	if( search_ms ) *search_ms = 0;
 	if( efn_ms ) *efn_ms = 0;
-	if( rma_scan_begin( sc, db, err, errlen ) )
+	if( scan_begin( sc, db, true, err, errlen ) )	// (the kernels timed apart: no tail behind the search kernel, one energy launch behind the wait)
 		return 1;
 	struct Done { rma_scanner *sc; ~Done(){ scan_done( sc ); } }	done{ sc };
 	int64_t	n = 0;
 	if( search_finish( sc, &n, search_ms, err, errlen ) )
 		return 1;
 	*n_hits = n;
+	sc->count_max = rma::tail_seen( sc->count_max, n );
 	const bool	has_efn = ( sc->have_efn || sc->d_efn2 ) && sc->dprog.n_efn > 0 && n > 0;
-	if( launch_efn( sc, n, err, errlen ) )
+	if( launch_efn( sc, n, nullptr, err, errlen ) )
 		return 1;
 	HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
 	if( efn_ms && has_efn )
@@ -1383,6 +1449,18 @@ extern "C" int rma_scanner_last_launch( rma_scanner_t *sc, int out[ 4 ] )
 	return 0;
 }
 
+// What the scanner's last rma_scan_end() (or rma_scan(), rma_scan_end_on_device()) did: out[ 0 ] the times it waited for the
+// stream, out[ 1 ] 1 when it took the records of the tail that rma_scan_begin() had enqueued ahead (rm_tail_plan.h), out[ 2 ]
+// launches of the search kernel, out[ 3 ] launches of an energy kernel -- of the whole scan, from its begin.
+extern "C" int rma_scanner_last_end( rma_scanner_t *sc, int out[ 4 ] )
+{
+	out[ 0 ] = sc->end_waits;
+	out[ 1 ] = sc->tail_taken ? 1 : 0;
+	out[ 2 ] = sc->search_launches;
+	out[ 3 ] = sc->efn_launches;
+	return 0;
+}
+
 // Energies, reference order, copy back.  With on_device_only the ordered records stay in HBM
 // (rma_scanner::d_last, for rma_gather_hits) and *hits is not set.
 static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, bool copy_back, char *err, size_t errlen )
@@ -1406,18 +1484,48 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 		}
 	};
 	int64_t	n = 0;
-	if( search_finish( sc, &n, nullptr, err, errlen ) )
+	const bool	ahead = sc->fly.tail.speculate;
+	if( ahead ){
+		// the tail was enqueued at rma_scan_begin: one wait, and the counters say whether its records are the scan's
+		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		sc->end_waits++;
+		const rma_scanner::InFlight	&f = sc->fly;
+		const unsigned long long	*c = sc->ctr(), count = c[ RMK_C_COUNT ];
+		rma::TailRepeat	r;
+		r.queue_need = !f.plan.lean && c[ RMK_C_QUEUE_NEED ] > 0;
+		r.flush_queue_need = f.plan.walks_nothing && c[ RMK_C_FLUSH_QUEUE_NEED ] > 0;
+		r.list_need = f.plan.walks_nothing && c[ RMK_C_LIST_RESERVED ] > ( unsigned long long )sc->glist_cap;
+		r.piece_overflow = f.plan.lean && c[ RMK_C_PIECE_OVERFLOW ] != 0 && !sc->whole_items;
+		if( rma::tail_verdict( count, f.tail.n_sort, sc->hit_cap(), r, c[ rma_scanner::TAIL_FLAG ] != 0, int64_t( count ) ) == rma::TAIL_TAKE ){
+			n = int64_t( count );
+			*n_hits = n;
+			sc->count_max = rma::tail_seen( sc->count_max, n );
+			sc->tail_taken = true;
+			sc->d_last = sc->dsort.d_out();
+			sc->n_last = n;
+			sc->last_state = 1;
+			if( hits )
+				*hits = copy_back ? sc->raw() : nullptr;
+			return 0;
+		}
+		// not taken: on from here as without a tail ahead -- the energies again, which are written from a record's other words
+	}
+	if( search_finish( sc, &n, nullptr, err, errlen, ahead ) )
 		return 1;
 	lap( "search" );
 	*n_hits = n;
+	sc->count_max = rma::tail_seen( sc->count_max, n );
 	sc->last_state = 1;		// (no records: nothing to be anywhere)
-	if( n == 0 )
+	if( n == 0 ){
+		sc->efn_ran = false;	// (an energy kernel of a tail ahead had nothing to do)
 		return 0;
+	}
 	sc->last_state = 2;		// (until the ordered records are known to be in HBM)
-	if( launch_efn( sc, n, err, errlen ) )
+	if( launch_efn( sc, n, nullptr, err, errlen ) )
 		return 1;
 	if( timing ){
 		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		sc->end_waits++;
 		lap( "energies" );
 	}
 	const rma_db	*db = sc->fly.db;
@@ -1433,17 +1541,17 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 		if( sc->dsort.reserve( sc->hit_cap(), stride ) == hipSuccess &&
 			sc->dsort.run( sc->hits(), n, rma::bits_of( unsigned( db->n_seq > 0 ? db->n_seq - 1 : 0 ) ), rma::bits_of( unsigned( db->max_slen ) ),
 				rma::bits_of( unsigned( sc->dprog.w_winsize ) ), sc->stream.get() ) == hipSuccess ){
-			int	flag = 1;
 			if( timing ){
 				HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+				sc->end_waits++;
 				lap( "sorted" );
 			}
 			if( copy_back )
 				HIPCHK( hipMemcpyAsync( sc->raw(), sc->dsort.d_out(), words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream.get() ) );
-			HIPCHK( hipMemcpyAsync( sc->ctr(), sc->dsort.d_flag(), sizeof( int ), hipMemcpyDeviceToHost, sc->stream.get() ) );
+			HIPCHK( hipMemcpyAsync( sc->ctr(), sc->dsort.d_flag(), sizeof( unsigned long long ), hipMemcpyDeviceToHost, sc->stream.get() ) );
 			HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
-			memcpy( &flag, sc->ctr(), sizeof( flag ) );
-			on_device = flag == 0;
+			sc->end_waits++;
+			on_device = sc->ctr()[ 0 ] != sc->dsort.epoch;	// (raised: the word holds this run's number, rm_hitsort_dev.h)
 			if( !on_device && sc->dsort.w_ord < 31 )
 				sc->dsort.w_ord = 31;	// (order words above 255: room for them from now on, if the other fields leave it)
 		}else
@@ -1465,6 +1573,7 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 		if( copy_back )
 			HIPCHK( hipMemcpyAsync( sc->raw(), sc->hits(), words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream.get() ) );
 		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		sc->end_waits++;
 		sc->d_last = sc->hits();
 		sc->n_last = 1;
 		sc->last_state = 1;
@@ -1476,6 +1585,7 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 		return 1;
 	HIPCHK( hipMemcpyAsync( sc->raw(), sc->hits(), words * sizeof( int32_t ), hipMemcpyDeviceToHost, sc->stream.get() ) );
 	HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+	sc->end_waits++;
 	lap( "copy back" );
 	sc->h_sorted.resize( words );
 	rma::sort_hits( sc->raw(), n, stride, sc->h_sorted.data(), sc->keys, sc->keys_tmp );
@@ -1484,6 +1594,7 @@ static int scan_end( rma_scanner_t *sc, const int32_t **hits, int64_t *n_hits, b
 		// the ordered records back where a device-side consumer finds them
 		HIPCHK( hipMemcpyAsync( sc->hits(), sc->h_sorted.data(), words * sizeof( int32_t ), hipMemcpyHostToDevice, sc->stream.get() ) );
 		HIPCHK( hipStreamSynchronize( sc->stream.get() ) );
+		sc->end_waits++;
 		sc->d_last = sc->hits();
 		sc->n_last = n;
 		sc->last_state = 1;
@@ -1582,9 +1693,10 @@ extern "C" int rma_scanner_warmup( rma_scanner_t *sc, char *err, size_t errlen )
 		( void )hipStreamSynchronize( sc->stream.get() );
 		( void )hipGetLastError();
 	}
-	if( rc == 0 && sc->dsort.cap >= 4096 ){
-		// ... and one pass of the ordering over a cleared hit buffer
-		( void )hipMemsetAsync( sc->hits(), 0, size_t( 4096 ) * sc->dprog.hit_stride * sizeof( int32_t ), sc->stream.get() );
+	if( rc == 0 && sc->dsort.cap >= 16384 ){
+		// ... and a pass of the ordering over a cleared hit buffer at either size: its own sort of a few thousand records, the library's
+		( void )hipMemsetAsync( sc->hits(), 0, size_t( 16384 ) * sc->dprog.hit_stride * sizeof( int32_t ), sc->stream.get() );
+		( void )sc->dsort.run( sc->hits(), 16384, 10, 20, 8, sc->stream.get() );
 		( void )sc->dsort.run( sc->hits(), 4096, 10, 20, 8, sc->stream.get() );
 		// ... and the way back of the records, as a scan ends: the first copy of this size from the device
 		// sets up the engine that makes it
@@ -1594,5 +1706,6 @@ extern "C" int rma_scanner_warmup( rma_scanner_t *sc, char *err, size_t errlen )
 		( void )hipGetLastError();
 	}
 	sc->opt = keep;
+	sc->count_max = -1;		// (the warm-up is not a scan the tail is planned from)
 	return rc;
 }

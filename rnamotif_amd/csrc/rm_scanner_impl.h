@@ -14,6 +14,7 @@
 #include "rm_hip_own.h"
 #include "rm_flight_count.h"
 #include "rm_launch_plan.h"
+#include "rm_tail_plan.h"
 #include "rm_hitsort.h"
 #include "rm_hitsort_dev.h"
 #include "rnamotif_amd.h"
@@ -96,7 +97,12 @@ struct rma_scanner {
 	std::vector<int32_t>	h_sorted;
 	std::vector<rma::HitKey>	keys, keys_tmp;
 	rma::DevHitSort	dsort;		// ordering on the device (rm_hitsort_dev.h)
-	rma::PinMem	h_ctr;			// unsigned long long: the first RMK_C_COPIED counters as a launch leaves them
+	rma::PinMem	h_ctr;			// unsigned long long: the first RMK_C_COPIED counters as a launch leaves them, then the word of TAIL_FLAG
+	// The word of the counter block in which the ordering of a tail enqueued ahead raises its flag (rm_tail_plan.h): the first
+	// one behind those the host reads after every launch, so that one copy brings the count, the repeat conditions and the
+	// flag; zeroed with the block before every launch.
+	static constexpr int	TAIL_FLAG = RMK_C_COPIED;
+	static_assert( TAIL_FLAG < RMK_N_COUNTERS, "a word of the counter block" );
 	int	grid_blocks = 0;		// most workgroups of a launch of a lean instance (eight of four waves per CU)
 	int	spill_blocks = 0;		// workgroups d_spill has areas for
 	// the capacities of d_hits (records), d_spill (items a workgroup) and h_raw (words) are what the buffers hold
@@ -114,7 +120,11 @@ struct rma_scanner {
 		const rma_db	*db = nullptr;
 		const rma::Layout	*lay = nullptr;
 		rma::LaunchPlan	plan;
+		rma::TailPlan	tail;		// energies, ordering and copy back enqueued behind the kernels of rma_scan_begin (rm_tail_plan.h)
 	}	fly;
+	int64_t	count_max = -1;		// rma::tail_seen() over the counts of the scans this scanner has ended (-1: it has ended none): plan_tail
+	int	end_waits = 0, search_launches = 0, efn_launches = 0;	// of the scan begun last, and whether rma_scan_end took
+	bool	tail_taken = false;		// the records of the tail enqueued ahead (rma_scanner_last_end)
 	rma::FlightMark	flying;			// ... counted among its device's scans in flight (rm_flight_count.h), from its launch to scan_done()
 	int	last_launch[ 4 ] = { 0, 0, 0, 0 };	// grid, dynamic LDS, the drain kernel's grid and beside of the last search launch (rma_scanner_last_launch)
 	// what the last scan left on the device, in order (rma_scan_end): for rma_gather_hits()
