@@ -11,10 +11,13 @@
 // rule of rm_hitprint.h, with the entries' names from a table rma_names_create puts on the device -- and beside it
 // rma_hit_list (rm_hitlist_dev.hip): the same records as rmfmt lists them, sorted and in columns, the rule of
 // rm_hitlist.h -- and rma_hit_ct (rm_hitct_dev.hip): the same records as rm2ct writes them, the rule of rm_hitct.h.
-// What they all do first is written once:
+// The file also holds what the calls are given besides records: rma_names_* (the entries' names on the device) and
+// rma_scanner_load_energy_tables.  What the calls all do first is written once:
 //   record_call_args    the database, the records and the device refused or accepted
 //   letters_on_device   the table the window bytes go through
 //   check_records       behind the caller's stream, the bad-record word reset, every record judged by the span kernel
+// The refusal words of the span scratch, which several calls share, are named in rm_hitpost.h (HitBadSlot on the
+// device, HitBadHostSlot page-locked), and the scratch is carved for as many as are named.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -202,9 +205,9 @@ int letters_on_device( rma::HitWindowScratch *s, const rma_db *db, const uint8_t
 }
 
 // The record check, queued on the scratch's stream behind the caller's work on its stream (the records) and the
-// database's tables: *d_bad -- the least index of a bad record -- reset, zero_bytes bytes at `zero` (the call's running
-// result; may be null) cleared, and, with `whole`, every record judged by the span kernel, which writes nothing else.
-// The caller queues its own kernels, copies *d_bad back with its result and synchronises once.
+// database's tables: d_bad[ HB_RECORD ] -- the least index of a bad record -- reset, zero_bytes bytes at `zero` (the
+// call's running result; may be null) cleared, and, with `whole`, every record judged by the span kernel, which writes
+// nothing else.  The caller queues its own kernels, copies the word back with its result and synchronises once.
 int check_records( rma::HitWindowScratch *s, const rma_db *db, const rma_program_t &prog, const int32_t *d_hits, int64_t n_hits,
 	void *stream, bool whole, void *zero, size_t zero_bytes, char *err, size_t errlen )
 {
@@ -212,12 +215,12 @@ int check_records( rma::HitWindowScratch *s, const rma_db *db, const rma_program
 	if( rma::stream_after( st, static_cast<hipStream_t>( stream ), err, errlen ) )
 		return 1;
 	HIPCHK( hipStreamWaitEvent( st, db->ready.get(), 0 ) );
-	HIPCHK( hipMemsetAsync( s->d_bad, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( s->d_bad + rma::HB_RECORD, 0xff, sizeof( unsigned long long ), st ) );
 	if( zero != nullptr )
 		HIPCHK( hipMemsetAsync( zero, 0, zero_bytes, st ) );
 	if( whole )
 		HIPCHK( rma::hit_spans( d_hits, n_hits, rma_hit_stride( &prog ), rma::hitwin_shape( prog ), db->d_slen, db->d_text_start, db->n_seq,
-			nullptr, nullptr, nullptr, s->d_bad, st ) );
+			nullptr, nullptr, nullptr, s->d_bad + rma::HB_RECORD, st ) );
 	return 0;
 }
 
@@ -293,16 +296,16 @@ int rma_hit_windows( rma::HitWindowScratch **scratch, const rma_db *db, const rm
 		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
 		const int32_t	*ch = d_hits + c0 * stride;
 		HIPCHK( rma::hit_spans( ch, cn, stride, shape, db->d_slen, db->d_text_start, db->n_seq, s->d_lo, s->d_len, s->d_src,
-			s->d_bad, st ) );
+			s->d_bad + rma::HB_RECORD, st ) );
 		size_t	tb = s->d_tmp.bytes();
 		HIPCHK( rma::hit_offsets( s->d_len, s->d_off, cn + 1, s->d_tmp.as<void>(), &tb, st ) );
 		HIPCHK( hipMemcpyAsync( s->h_off, s->d_off, size_t( cn + 1 ) * 8, hipMemcpyDeviceToHost, st ) );
 		HIPCHK( hipMemcpyAsync( s->h_lo, s->d_lo, size_t( cn ) * 4, hipMemcpyDeviceToHost, st ) );
 		if( c0 == 0 )
-			HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+			HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_FIRST, s->d_bad + rma::HB_RECORD, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
 		HIPCHK( hipStreamSynchronize( st ) );
-		if( c0 == 0 && *s->h_bad != ~0ull )
-			return bad_record( s, db, prog, d_hits, int64_t( *s->h_bad ), nullptr, "printed", err, errlen );
+		if( c0 == 0 && s->h_bad[ rma::HBH_FIRST ] != ~0ull )
+			return bad_record( s, db, prog, d_hits, int64_t( s->h_bad[ rma::HBH_FIRST ] ), nullptr, "printed", err, errlen );
 		for( int64_t a = 0; a < cn; ){
 			int64_t	b = a + 1;
 			while( b < cn && b - a < piece_records && s->h_off[ b + 1 ] - s->h_off[ a ] <= HW_PIECE_WINDOW )
@@ -380,27 +383,27 @@ int hit_structures_count( rma_scanner_t *sc, const rma_db *db, const int32_t *d_
 	rma::HitWindowScratch	*s = p.win;
 	hipStream_t	st = s->stream.get();
 	const int	stride = rma_hit_stride( &sc->prog );
-	// d_bad[ 0 ]: the least index of a bad record, counted over the call; d_bad[ 2 ]: where the spans of a later chunk,
-	// which count from the chunk's first record, put theirs (the same records, already judged).  A call of one chunk
-	// has no pass over all records: the chunk's own spans judge them.
+	// HB_RECORD: the least index of a bad record, counted over the call; HB_STRUCT_SPARE: where the spans of a later
+	// chunk, which count from the chunk's first record, put theirs (the same records, already judged).  A call of one
+	// chunk has no pass over all records: the chunk's own spans judge them.
 	const bool	chunks = n_hits > HW_CHUNK;
 	if( check_records( s, db, sc->prog, d_hits, n_hits, stream, chunks, p.hs_carry(), sizeof( int64_t ), err, errlen ) )
 		return 1;
-	HIPCHK( rma::hit_helix_check( d_hits, n_hits, stride, p.hs_table(), s->d_bad, st ) );
+	HIPCHK( rma::hit_helix_check( d_hits, n_hits, stride, p.hs_table(), s->d_bad + rma::HB_RECORD, st ) );
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
 		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
-		if( hit_structures_spans( sc, db, d_hits + c0 * stride, cn, chunks ? s->d_bad + 2 : s->d_bad, err, errlen ) )
+		if( hit_structures_spans( sc, db, d_hits + c0 * stride, cn, s->d_bad + ( chunks ? rma::HB_STRUCT_SPARE : rma::HB_RECORD ), err, errlen ) )
 			return 1;
 		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
 	}
-	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_FIRST, s->d_bad + rma::HB_RECORD, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_TOTAL, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
 	HIPCHK( hipStreamSynchronize( st ) );
-	if( s->h_bad[ 0 ] != ~0ull ){
+	if( s->h_bad[ rma::HBH_FIRST ] != ~0ull ){
 		const rma::HitStructTable	tab = rma::hitstruct_table( sc->prog );
-		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), &tab, "written", err, errlen );
+		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ rma::HBH_FIRST ] ), &tab, "written", err, errlen );
 	}
-	*total = int64_t( s->h_bad[ 1 ] );
+	*total = int64_t( s->h_bad[ rma::HBH_TOTAL ] );
 	return 0;
 }
 
@@ -461,7 +464,7 @@ extern "C" int rma_hit_structures( rma_scanner_t *sc, const rma_db_t *db, const 
 		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
 		const int32_t	*ch = d_hits + c0 * stride;
 		// (a call of one chunk: the count's spans are still there)
-		if( n_hits > HW_CHUNK && hit_structures_spans( sc, db, ch, cn, s->d_bad + 2, err, errlen ) )
+		if( n_hits > HW_CHUNK && hit_structures_spans( sc, db, ch, cn, s->d_bad + rma::HB_STRUCT_SPARE, err, errlen ) )
 			return 1;
 		const rma::HitStructOut	out{ d_off + c0, d_lo + c0, d_base, d_elem, d_mate };
 		HIPCHK( rma::hit_struct_fill( db->text, ch, cn, stride, rma::hitwin_shape( sc->prog ), p.hs_table(), s->d_lo, s->d_src, s->d_off,
@@ -492,11 +495,11 @@ int hit_alignment_widths( rma_scanner_t *sc, const rma_db *db, const int32_t *d_
 		return 1;
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK )
 		HIPCHK( rma::hit_align_widths( d_hits + c0 * stride, std::min( HW_CHUNK, n_hits - c0 ), stride, shape, d_w, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_FIRST, s->d_bad + rma::HB_RECORD, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
 	HIPCHK( hipMemcpyAsync( h_w, d_w, rma::HA_MAX_COLS * sizeof( int32_t ), hipMemcpyDeviceToHost, st ) );
 	HIPCHK( hipStreamSynchronize( st ) );
-	if( s->h_bad[ 0 ] != ~0ull )
-		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ 0 ] ), nullptr, "written", err, errlen );
+	if( s->h_bad[ rma::HBH_FIRST ] != ~0ull )
+		return bad_record( s, db, sc->prog, d_hits, int64_t( s->h_bad[ rma::HBH_FIRST ] ), nullptr, "written", err, errlen );
 	memcpy( need, h_w, rma::HA_MAX_COLS * sizeof( int32_t ) );
 	return 0;
 }
@@ -1290,8 +1293,9 @@ extern "C" int rma_names_create( rma_scanner_t *sc, const rma_db_t *db, const ch
 // chunks of HW_CHUNK records, then the fill kernel, on the stream of the scanner's span scratch as rma_hit_structures
 // runs its kernels: a chunk's offsets count from its first record, the bytes of the chunks before it wait in a word on
 // the device (*hs_carry), so no chunk needs the host.  The size kernel checks each record, so the calls have no pass of
-// their own for the check.  Words of the scratch's d_bad: [ 0 ] the least index of a bad record, [ 3 ] of a bad
-// text_len; [ 4 ], [ 5 ] where the fill call's second pass over a later chunk puts them (the same records, already judged).
+// their own for the check.  Words of the scratch's d_bad (rm_hitpost.h): HB_RECORD the least index of a bad record,
+// HB_PRINT_TEXT of a bad text_len; HB_PRINT_SPARE, HB_PRINT_TEXT_SPARE where the fill call's second pass over a later
+// chunk puts them (the same records, already judged).
 namespace {
 
 struct PrintCall {
@@ -1360,22 +1364,22 @@ int hit_print_count( const char *who, const PrintCall &c, void *stream, int64_t 
 	if( check_records( s, c.db, c.sc->prog, c.d_hits, c.n_hits, stream, false, p.hs_carry(), sizeof( int64_t ), err, errlen ) )
 		return 1;
 	HIPCHK( hipStreamWaitEvent( st, c.names->ready.get(), 0 ) );
-	HIPCHK( hipMemsetAsync( s->d_bad + 3, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( s->d_bad + rma::HB_PRINT_TEXT, 0xff, sizeof( unsigned long long ), st ) );
 	for( int64_t c0 = 0; c0 < c.n_hits; c0 += HW_CHUNK ){
 		const int64_t	cn = std::min( HW_CHUNK, c.n_hits - c0 );
-		if( hit_print_sizes_of( c, c0, cn, s->d_bad, s->d_bad + 3, err, errlen ) )
+		if( hit_print_sizes_of( c, c0, cn, s->d_bad + rma::HB_RECORD, s->d_bad + rma::HB_PRINT_TEXT, err, errlen ) )
 			return 1;
 		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
 	}
-	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad + 2, s->d_bad + 3, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_FIRST, s->d_bad + rma::HB_RECORD, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_TOTAL, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_SECOND, s->d_bad + rma::HB_PRINT_TEXT, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
 	HIPCHK( hipEventRecord( c.names->used.get(), st ) );
 	HIPCHK( hipStreamSynchronize( st ) );
-	if( s->h_bad[ 0 ] != ~0ull )
-		return bad_record( s, c.db, c.sc->prog, c.d_hits, int64_t( s->h_bad[ 0 ] ), nullptr, "printed", err, errlen );
-	if( s->h_bad[ 2 ] != ~0ull ){
-		const int64_t	h = int64_t( s->h_bad[ 2 ] );
+	if( s->h_bad[ rma::HBH_FIRST ] != ~0ull )
+		return bad_record( s, c.db, c.sc->prog, c.d_hits, int64_t( s->h_bad[ rma::HBH_FIRST ] ), nullptr, "printed", err, errlen );
+	if( s->h_bad[ rma::HBH_SECOND ] != ~0ull ){
+		const int64_t	h = int64_t( s->h_bad[ rma::HBH_SECOND ] );
 		int32_t	len = 0;
 		HIPCHK( hipMemcpyAsync( &len, c.d_text_len + h, sizeof( len ), hipMemcpyDeviceToHost, st ) );
 		HIPCHK( hipStreamSynchronize( st ) );
@@ -1386,7 +1390,7 @@ int hit_print_count( const char *who, const PrintCall &c, void *stream, int64_t 
 				( long long )h, len, c.text_width );
 		return 1;
 	}
-	*total = int64_t( s->h_bad[ 1 ] );
+	*total = int64_t( s->h_bad[ rma::HBH_TOTAL ] );
 	return 0;
 }
 
@@ -1451,7 +1455,7 @@ extern "C" int rma_hit_print( rma_scanner_t *sc, const rma_db_t *db, const rma_n
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
 		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
 		// (a call of one chunk: the count's offsets are still there)
-		if( n_hits > HW_CHUNK && hit_print_sizes_of( c, c0, cn, s->d_bad + 4, s->d_bad + 5, err, errlen ) )
+		if( n_hits > HW_CHUNK && hit_print_sizes_of( c, c0, cn, s->d_bad + rma::HB_PRINT_SPARE, s->d_bad + rma::HB_PRINT_TEXT_SPARE, err, errlen ) )
 			return 1;
 		HIPCHK( rma::hit_print_fill( print_batch( c, c0, cn ), db->text, tab, codes, d_text_bytes, s->d_off, p.hs_carry(), d_out, d_off + c0,
 			c0 + cn == n_hits, st ) );
@@ -1778,9 +1782,9 @@ extern "C" int rma_hit_list( rma_scanner_t *sc, const rma_db_t *db, const rma_na
 // rma_hit_ct_size() / rma_hit_ct(): the size kernel of rm_hitct_dev.hip and the scan of rm_hitwin_dev.hip in chunks of
 // HW_CHUNK records, then the fill kernel, on the stream of the scanner's span scratch with the running total in
 // *hs_carry, as rma_hit_print runs its own.  The descriptor's table (rm_hitct.h) is made per call from the words of the
-// "#RM descr" line and goes to the kernels with their arguments.  Words of the scratch's d_bad: [ 6 ] the least refused
-// record with its reason, [ 7 ] where the fill call's second pass over a later chunk puts it (the same records, already
-// judged).
+// "#RM descr" line and goes to the kernels with their arguments.  Words of the scratch's d_bad (rm_hitpost.h): HB_CT the
+// least refused record with its reason, HB_CT_SPARE where the fill call's second pass over a later chunk puts it (the
+// same records, already judged).
 namespace {
 
 struct CtCall {
@@ -1860,20 +1864,20 @@ int hit_ct_count( const char *who, const CtCall &c, void *stream, int64_t *total
 	if( check_records( s, pc.db, pc.sc->prog, pc.d_hits, pc.n_hits, stream, false, p.hs_carry(), sizeof( int64_t ), err, errlen ) )
 		return 1;
 	HIPCHK( hipStreamWaitEvent( st, pc.names->ready.get(), 0 ) );
-	HIPCHK( hipMemsetAsync( s->d_bad + 6, 0xff, sizeof( unsigned long long ), st ) );
+	HIPCHK( hipMemsetAsync( s->d_bad + rma::HB_CT, 0xff, sizeof( unsigned long long ), st ) );
 	for( int64_t c0 = 0; c0 < pc.n_hits; c0 += HW_CHUNK ){
 		const int64_t	cn = std::min( HW_CHUNK, pc.n_hits - c0 );
-		if( hit_ct_sizes_of( c, c0, cn, s->d_bad + 6, err, errlen ) )
+		if( hit_ct_sizes_of( c, c0, cn, s->d_bad + rma::HB_CT, err, errlen ) )
 			return 1;
 		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );
 	}
-	HIPCHK( hipMemcpyAsync( s->h_bad, s->d_bad + 6, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
-	HIPCHK( hipMemcpyAsync( s->h_bad + 1, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_FIRST, s->d_bad + rma::HB_CT, sizeof( unsigned long long ), hipMemcpyDeviceToHost, st ) );
+	HIPCHK( hipMemcpyAsync( s->h_bad + rma::HBH_TOTAL, p.hs_carry(), sizeof( int64_t ), hipMemcpyDeviceToHost, st ) );
 	HIPCHK( hipEventRecord( pc.names->used.get(), st ) );
 	HIPCHK( hipStreamSynchronize( st ) );
-	if( s->h_bad[ 0 ] != ~0ull ){
-		const int64_t	h = int64_t( s->h_bad[ 0 ] >> 4 );
-		const int	code = int( s->h_bad[ 0 ] & 15 );
+	if( s->h_bad[ rma::HBH_FIRST ] != ~0ull ){
+		const int64_t	h = int64_t( s->h_bad[ rma::HBH_FIRST ] >> 4 );
+		const int	code = int( s->h_bad[ rma::HBH_FIRST ] & 15 );
 		if( code < rma::HP_TEXT )
 			return bad_record( s, pc.db, pc.sc->prog, pc.d_hits, h, nullptr, "written", err, errlen );
 		if( code == rma::HP_TEXT ){
@@ -1887,7 +1891,7 @@ int hit_ct_count( const char *who, const CtCall &c, void *stream, int64_t *total
 		rma::hitct_refusal( err, errlen, who, code, ( long long )h );
 		return 1;
 	}
-	*total = int64_t( s->h_bad[ 1 ] );
+	*total = int64_t( s->h_bad[ rma::HBH_TOTAL ] );
 	return 0;
 }
 
@@ -1950,7 +1954,7 @@ extern "C" int rma_hit_ct( rma_scanner_t *sc, const rma_db_t *db, const rma_name
 	for( int64_t c0 = 0; c0 < n_hits; c0 += HW_CHUNK ){
 		const int64_t	cn = std::min( HW_CHUNK, n_hits - c0 );
 		// (a call of one chunk: the count's offsets are still there)
-		if( n_hits > HW_CHUNK && hit_ct_sizes_of( c, c0, cn, s->d_bad + 7, err, errlen ) )
+		if( n_hits > HW_CHUNK && hit_ct_sizes_of( c, c0, cn, s->d_bad + rma::HB_CT_SPARE, err, errlen ) )
 			return 1;
 		HIPCHK( rma::hit_ct_fill( ct_batch( c, c0, cn ), db->text, tab, codes, s->d_off, p.hs_carry(), d_out, d_off + c0, c0 + cn == n_hits, st ) );
 		HIPCHK( rma::hit_carry_add( p.hs_carry(), s->d_off + cn, st ) );

@@ -42,8 +42,9 @@ def carved():
 
 
 def test_window_scratch(carved):
-    """lo[ chunk ] | len[ chunk + 1 ] | off[ chunk + 1 ] | src[ chunk ] | bad | letters[ 256 ] on the device,
-    off[ chunk + 1 ] | lo[ chunk ] | bad | letters[ 256 ] page-locked."""
+    """lo[ chunk ] | len[ chunk + 1 ] | off[ chunk + 1 ] | src[ chunk ] | bad[ HB_SLOTS ] | letters[ 256 ] on the device,
+    off[ chunk + 1 ] | lo[ chunk ] | bad[ HBH_SLOTS ] | letters[ 256 ] page-locked: the named refusal words of
+    rm_hitpost.h, which fit the 256 bytes an array has at least."""
     o_len = align256(HW_CHUNK * 4)
     o_off = o_len + align256((HW_CHUNK + 1) * 8)
     o_src = o_off + align256((HW_CHUNK + 1) * 8)
