@@ -188,7 +188,8 @@ int	rma_db_create_device( rma_scanner_t *sc, const void *text, int64_t text_byte
 int	rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, int64_t text_bytes, int32_t maxslen,
 		void *stream, rma_db_t **out, char *err, size_t errlen );
 /* entry i's name and definition as the readers deliver them (the name cut at 99 bytes); valid until rma_db_destroy.
- * Non-zero for a database that was not made by rma_db_create_device_fasta, or an entry it does not have. */
+ * Non-zero for a database that was not made by rma_db_create_device_fasta and has had no rma_db_text_attach_pack,
+ * or an entry it does not have. */
 int	rma_db_entry_name( const rma_db_t *db, int32_t i, const char **sid, const char **sdef );
 /* the number of entries of a database */
 int32_t	rma_db_entries( const rma_db_t *db );
@@ -203,6 +204,27 @@ void	rma_letter_codes( uint8_t codes[ 256 ] );
 int64_t	rma_db_mask_words( const rma_db_t *db );
 int	rma_db_read_packed( const rma_db_t *db, uint32_t *codes, uint32_t *amask, int64_t *base_off, int32_t *slen,
 		char *err, size_t errlen );
+/* The text of a database of packed words (rma_db_create*(), rma_db_create_packed*()), made on the device from the
+ * words in HBM (csrc/rm_dbtext.h has the rule, PackFile::unpack's): 1 byte per base of device memory, each entry on a
+ * 16-byte boundary, until rma_db_destroy(), which returns it to the cache.  From then on the database is a
+ * rma_db_create_device() database of the readers' letters over that text: rma_replay_device() and every call over
+ * hit records on the device work on it.  Its words, tilings and scans are unchanged.
+ * exc: the letters at masked positions, entry after entry, in order; exc_off[ n_seq + 1 ] (host arrays).
+ * exc NULL: every masked base reads n.
+ * The call orders itself behind `stream` and the database's upload, and waits once.  Refused, with words, nothing made
+ * and the database as it was: a database that has its text already (made from device text, or attached before), one
+ * with a scan in flight, a destroyed one, exc_off that does not ascend from 0, an entry whose mask has another number
+ * of bases set than it has exceptions, an exception that is not a lower-case letter other than a, c, g and t. */
+int	rma_db_text_attach( rma_db_t *db, const char *exc, const int64_t *exc_off, void *stream, char *err, size_t errlen );
+/* the same from the pack the database was made of: entry i of db is entry entry[ i ] of pk (entry NULL: first + i).
+ * The entries also get the pack's names (rma_db_entry_name).  Refused as well: a pack entry out of range or of
+ * another length than the database's. */
+int	rma_db_text_attach_pack( rma_db_t *db, const rma_pack_t *pk, const int32_t *entry, int32_t first, void *stream,
+		char *err, size_t errlen );
+/* verification, like rma_db_read_packed(): entry i's text read back, slen bytes (any database with text on the device) */
+int	rma_db_read_text( const rma_db_t *db, int32_t i, char *buf, char *err, size_t errlen );
+/* what the fill kernel of rma_db_text_attach*() took on the device, in ms (profiles); negative: never attached */
+float	rma_db_text_fill_ms( const rma_db_t *db );
 
 /* ---- scan every sequence of db (both strands when the program says so).
  * *hits receives *n_hits records of rma_hit_stride( prog ) words, sorted by

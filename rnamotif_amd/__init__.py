@@ -146,6 +146,11 @@ def lib() -> C.CDLL:
     L.rma_db_mask_words.argtypes = [vp]
     L.rma_db_mask_words.restype = C.c_int64
     L.rma_db_read_packed.argtypes = [vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.rma_db_text_attach.argtypes = [vp, C.c_char_p, i64p, vp, C.c_char_p, C.c_size_t]
+    L.rma_db_text_attach_pack.argtypes = [vp, vp, i32p, C.c_int32, vp, C.c_char_p, C.c_size_t]
+    L.rma_db_read_text.argtypes = [vp, C.c_int32, C.c_char_p, C.c_char_p, C.c_size_t]
+    L.rma_db_text_fill_ms.argtypes = [vp]
+    L.rma_db_text_fill_ms.restype = C.c_float
     L.rma_scan_records_to_device.argtypes = [vp, vp, C.c_int64, vp, C.c_char_p, C.c_size_t]
     L.rma_replay_device.argtypes = [vp, vp, vp, C.c_int64, C.c_char_p, cpp, cpp, vp, i64p, vp, C.c_char_p, C.c_size_t]
     L.rma_hit_structures_size.argtypes = [vp, vp, vp, C.c_int64, vp, i64p, C.c_char_p, C.c_size_t]
@@ -274,6 +279,9 @@ class Database:
                  entries: Optional[Sequence[int]] = None, wait: bool = True):
         L = lib()
         self.scanner = scanner
+        # (what device_text() defaults to: the pack the words came from and which of its entries)
+        self._made_of = (pack, int(first), None if entries is None else [int(e) for e in entries])
+        self._text, self.alphabet = None, None
         h = C.c_void_p()
         err = C.create_string_buffer(_ERRLEN)
         if pack is not None and entries is not None:
@@ -322,6 +330,81 @@ class Database:
         _check(L.rma_db_read_packed(self._h, codes.ctypes.data, amask.ctypes.data, base_off.ctypes.data,
                                     slen.ctypes.data, err, _ERRLEN), err)
         return codes, amask, base_off, slen
+
+    def device_text(self, pack: Optional["Pack"] = None, first: Optional[int] = None, entries: Optional[Sequence[int]] = None,
+                    exceptions: Optional[Sequence[bytes]] = None) -> "Database":
+        """Give a database of packed words its text in HBM, made there from the words (rma_db_text_attach*): one byte
+        per base of device memory until the database is closed.  From then on score(), seq_check(), prune(),
+        hit_structures(), align(), print_hits(), list_hits(), ct_hits() and Replay.device() take it as they take a
+        database made by database_from_tensor(); its words and scans are unchanged.
+
+        Default: the pack and the first / entries the database was made with; entry i of the database is entry
+        entries[i] (else first + i) of pack, and .sids / .sdefs become the pack's names.  A database made of host
+        strings has no pack: exceptions is one bytes per entry, the letters at its masked positions in order
+        (lower case, not a, c, g or t), or None: every masked base reads n.  Runs behind torch's current stream and
+        waits once.  Refused with words (RnamotifError), the database as it was: a database that has text already, a
+        scan in flight, exceptions that are not the mask's number or no such letters, a pack entry of another length."""
+        if getattr(self, "_h", None) is None or not self._h:
+            raise ValueError("the database is closed")
+        L = lib()
+        made = getattr(self, "_made_of", (None, 0, None))
+        if pack is None and exceptions is None:
+            pack = made[0]
+        if pack is not None and exceptions is not None:
+            raise ValueError("device_text: a pack or exceptions, not both")
+        stream = None
+        try:
+            import torch
+            if torch.cuda.is_available():
+                stream = torch.cuda.current_stream(torch.device("cuda", self.scanner.device)).cuda_stream
+        except ImportError:
+            pass
+        err = C.create_string_buffer(_ERRLEN)
+        if pack is not None:
+            if entries is None and first is None:
+                first, entries = made[1], made[2]
+            ent = None
+            if entries is not None:
+                if len(entries) != self.n_seqs:
+                    raise ValueError(f"entries: one per entry, {self.n_seqs}, not {len(entries)}")
+                ent = (C.c_int32 * max(len(entries), 1))(*[int(e) for e in entries])
+            _check(L.rma_db_text_attach_pack(self._h, pack._h, ent, int(first or 0), stream, err, _ERRLEN), err)
+            self.sids, self.sdefs = [], []
+            sid, sdef = C.c_char_p(), C.c_char_p()
+            for i in range(self.n_seqs):
+                L.rma_db_entry_name(self._h, i, C.byref(sid), C.byref(sdef))
+                self.sids.append(sid.value)
+                self.sdefs.append(sdef.value)
+        elif exceptions is not None:
+            if len(exceptions) != self.n_seqs:
+                raise ValueError(f"exceptions: one per entry, {self.n_seqs}, not {len(exceptions)}")
+            exc = b"".join(bytes(x) for x in exceptions)
+            off = np.zeros(self.n_seqs + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in exceptions], out=off[1:])
+            buf = C.create_string_buffer(exc, len(exc) + 1)
+            _check(L.rma_db_text_attach(self._h, buf, off.ctypes.data_as(C.POINTER(C.c_int64)), stream, err, _ERRLEN), err)
+        else:
+            _check(L.rma_db_text_attach(self._h, None, None, stream, err, _ERRLEN), err)
+        self._text = "owned"    # (as database_from_fasta_tensor(): the calls over records ask for a database with text)
+        return self
+
+    def read_text(self, i: int) -> bytes:
+        """Entry i's text in HBM, read back (verification): the readers' letters, one byte per base."""
+        if getattr(self, "_h", None) is None or not self._h:
+            raise ValueError("the database is closed")
+        L = lib()
+        if not 0 <= int(i) < self.n_seqs:
+            raise IndexError(f"entry {i} of {self.n_seqs}")
+        err = C.create_string_buffer(_ERRLEN)
+        slens = self.__dict__.get("_slens")
+        if slens is None:       # (the entries' lengths, read back once)
+            slens = np.zeros(max(self.n_seqs, 1), dtype=np.int32)
+            _check(L.rma_db_read_packed(self._h, None, None, None, slens.ctypes.data, err, _ERRLEN), err)
+            self._slens = slens
+        n = int(slens[int(i)])
+        buf = C.create_string_buffer(n + 1)
+        _check(L.rma_db_read_text(self._h, int(i), buf, err, _ERRLEN), err)
+        return buf.raw[:n]
 
     def wait(self) -> None:
         """Until the upload is complete (wait=False databases)."""
@@ -831,8 +914,14 @@ class Scanner:
 
     def database_from_pack(self, pack: "Pack", first: int = 0, count: Optional[int] = None,
                            entries: Optional[Sequence[int]] = None,
-                           ranges: Optional[Sequence[Tuple[int, int]]] = None, wait: bool = True) -> Database:
-        return Database(self, pack=pack, first=first, count=count, entries=entries, ranges=ranges, wait=wait)
+                           ranges: Optional[Sequence[Tuple[int, int]]] = None, wait: bool = True, text: bool = False) -> Database:
+        """Entries of a packed database, uploaded as they are.  text=True: Database.device_text() at once -- the
+        database's text made in HBM from the words (1 byte per base of device memory until it is closed), so that
+        the calls over hit records on the GPU take it."""
+        db = Database(self, pack=pack, first=first, count=count, entries=entries, ranges=ranges, wait=wait)
+        if text:
+            db.device_text()
+        return db
 
     def database_from_tensor(self, text, offsets=None, lengths=None, ranges: Optional[Sequence[Tuple[int, int]]] = None,
                              alphabet: Optional[str] = None, wait: bool = False) -> Database:
@@ -1646,6 +1735,10 @@ class Pack:
         buf = C.create_string_buffer(n + 1)
         L.rma_pack_seq(self._h, i, buf)
         return (C.string_at(L.rma_pack_sid(self._h, i)), C.string_at(L.rma_pack_sdef(self._h, i)), buf.raw[:n])
+
+    def seq(self, i: int) -> bytes:
+        """Entry i's sequence text, unpacked on the host: the readers' letters."""
+        return self.record(i)[2]
 
     def close(self) -> None:
         if self._h:

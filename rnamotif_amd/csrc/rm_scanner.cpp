@@ -34,6 +34,7 @@
 #include "rm_fasta.h"
 #include "rm_pack.h"
 #include "rm_dbpack_dev.h"
+#include "rm_dbtext_dev.h"
 #include "rm_fasta_dev_kernels.h"
 #include "rm_stream.h"
 
@@ -146,6 +147,15 @@ bool rma::is_device_db( const rma_db *db )
 {
 	std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
 	return g_device_dbs.count( db ) != 0;
+}
+
+// every database that has been made and not yet destroyed (rma_db_text_attach refuses any other); under g_device_dbs_mu
+static std::set<const rma_db *>	g_live_dbs;
+
+static bool is_live_db( const rma_db *db )
+{
+	std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+	return g_live_dbs.count( db ) != 0;
 }
 
 hipStream_t rma::upload_stream( const rma_db *db )
@@ -354,6 +364,10 @@ static int db_alloc( int device, const int64_t *base_off, const int32_t *slen, i
 	// every early return below frees what has been allocated so far
 	DbPtr	guard( new rma_db, rma_db_destroy );
 	rma_db	*db = guard.get();
+	{
+		std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+		g_live_dbs.insert( db );
+	}
 	db->device = device;
 	db->ctx = ctx;
 	db->n_seq = n;
@@ -884,6 +898,237 @@ extern "C" int rma_db_create_device_fasta( rma_scanner_t *sc, const void *text, 
 	return 0;
 }
 
+// ---------------------------------------------------------------- the text of a packed database, made on the device
+// A database of packed words gets what rma_db_create_device_fasta()'s has: a text of its own in text_blk, one byte per
+// base, made by the kernels of rm_dbtext_dev.hip from its words and the letters at its masked positions.  Everything
+// is refused before anything of the database changes; the one wait is for the word of the check, behind the fill.
+static int db_text_attach( const char *who, rma_db_t *db, const char *exc, const int64_t *exc_off, void *stream, char *err, size_t errlen )
+{
+	if( db == nullptr || !is_live_db( db ) ){
+		snprintf( err, errlen, "%s: the database (%p) has been destroyed or was never made", who, static_cast<const void *>( db ) );
+		return 1;
+	}
+	if( rma::is_device_db( db ) || db->text != nullptr ){
+		snprintf( err, errlen, "%s: the database already has its text in device memory (made from a tensor, from FASTA text, or attached before)", who );
+		return 1;
+	}
+	{
+		std::lock_guard<std::mutex>	lk( db->mu );
+		if( !db->busy.empty() ){
+			snprintf( err, errlen, "%s: a scan of the database is in flight: end it first", who );
+			return 1;
+		}
+	}
+	const int32_t	n = db->n_seq;
+	const size_t	nn = size_t( n );
+	const int64_t	n_mask = db->padded_bases / 32;
+	if( exc != nullptr ){
+		if( exc_off == nullptr ){
+			snprintf( err, errlen, "%s: exceptions without their offsets: bad arguments", who );
+			return 1;
+		}
+		for( int32_t i = 0; i <= n; i++ )
+			if( i == 0 ? exc_off[ 0 ] != 0 : exc_off[ i ] < exc_off[ i - 1 ] ){
+				snprintf( err, errlen, "%s: exc_off[ %d ] = %lld: the offsets ascend from 0", who, i, ( long long )exc_off[ i ] );
+				return 1;
+			}
+	}
+	// the entries' words inside the arrays (every database made here has them so: the kernels read through these)
+	std::vector<int64_t>	start( nn );
+	int64_t	text_bytes = 0;
+	for( size_t i = 0; i < nn; i++ ){
+		const int64_t	b = db->h_base_off[ i ];
+		if( b < 0 || b % 32 != 0 || db->h_slen[ i ] < 0 || b / 32 + ( int64_t( db->h_slen[ i ] ) + 31 ) / 32 > n_mask ){
+			snprintf( err, errlen, "%s: entry %zu: bases [%lld, %lld) are not whole words of the database's %lld", who, i, ( long long )b,
+				( long long )b + db->h_slen[ i ], ( long long )n_mask );
+			return 1;
+		}
+		start[ i ] = text_bytes;
+		text_bytes += rma::dbtext_entry_bytes( db->h_slen[ i ] );
+	}
+	const int64_t	n_exc = exc != nullptr ? exc_off[ n ] : 0;
+	HIPCHK( hipSetDevice( db->device ) );
+	DevCtx	*ctx = db->ctx;
+	hipStream_t	up = ctx->upload.get();
+	// the blocks of this call: back to the cache on every way out, once the upload stream is done with them; the text
+	// goes to the database instead
+	struct Blocks {
+		DevCtx	*ctx;
+		Block	work, text;
+		bool	idle = true;		// nothing on the upload stream uses them
+		~Blocks()
+		{
+			if( !idle )
+				( void )hipStreamSynchronize( ctx->upload.get() );
+			ctx->give( work ); ctx->give( text );
+		}
+	}	b{ ctx, {}, {} };
+	rma::DbTextArgs	a;
+	memset( &a, 0, sizeof( a ) );
+	size_t	scan_tmp = 0;
+	a.n_mask = n_mask;
+	HIPCHK( rma::dbtext_directory( a, nullptr, &scan_tmp, up ) );
+	// work: dir | exc_off | exc_base | bad | the scan's scratch | exc;  text: the text | text_start
+	Carver	cw, ct;
+	const size_t	runs = size_t( rma::dbtext_dir_runs( n_mask ) );
+	cw.take<uint64_t>( nullptr, runs ); cw.take<int64_t>( nullptr, nn + 1 ); cw.take<int64_t>( nullptr, nn + 1 );
+	cw.take<unsigned long long>( nullptr, 1 ); cw.take<char>( nullptr, scan_tmp + 1 ); cw.take<char>( nullptr, size_t( n_exc ) + 1 );
+	ct.take<uint8_t>( nullptr, size_t( text_bytes ) + 1 ); ct.take<int64_t>( nullptr, nn + 1 );
+	HIPCHK( ctx->take( cw.at, &b.work ) );
+	HIPCHK( ctx->take( ct.at, &b.text ) );
+	cw = Carver(); ct = Carver();
+	a.dir = cw.take<uint64_t>( b.work.p, runs );
+	int64_t	*d_exc_off = cw.take<int64_t>( b.work.p, nn + 1 );
+	a.exc_base = cw.take<int64_t>( b.work.p, nn + 1 );
+	a.bad = cw.take<unsigned long long>( b.work.p, 1 );
+	void	*d_scan_tmp = cw.take<char>( b.work.p, scan_tmp + 1 );
+	char	*d_exc = cw.take<char>( b.work.p, size_t( n_exc ) + 1 );
+	a.text = ct.take<uint8_t>( b.text.p, size_t( text_bytes ) + 1 );
+	int64_t	*d_start = ct.take<int64_t>( b.text.p, nn + 1 );
+	a.codes = db->d_codes;
+	a.amask = db->d_amask;
+	a.base_off = db->d_base_off;
+	a.slen = db->d_slen;
+	a.n = n;
+	a.exc = exc != nullptr ? d_exc : nullptr;
+	a.exc_off = exc != nullptr ? d_exc_off : nullptr;
+	a.n_exc = n_exc;
+	a.text_start = d_start;
+	a.text_bytes = text_bytes;
+	rma::Event	t0, t1;
+	HIPCHK( t0.create( hipEventDefault ) );
+	HIPCHK( t1.create( hipEventDefault ) );
+	unsigned long long	bad = rma::DT_BAD_NONE;
+	// behind the caller's stream and the database's words
+	if( rma::stream_after( up, static_cast<hipStream_t>( stream ), err, errlen ) )
+		return 1;
+	HIPCHK( hipStreamWaitEvent( up, db->ready.get(), 0 ) );
+	b.idle = false;
+	if( n > 0 )
+		HIPCHK( hipMemcpyAsync( d_start, start.data(), nn * 8, hipMemcpyHostToDevice, up ) );
+	if( exc != nullptr ){
+		HIPCHK( hipMemcpyAsync( d_exc_off, exc_off, ( nn + 1 ) * 8, hipMemcpyHostToDevice, up ) );
+		if( n_exc > 0 )
+			HIPCHK( hipMemcpyAsync( d_exc, exc, size_t( n_exc ), hipMemcpyHostToDevice, up ) );
+	}
+	HIPCHK( hipMemsetAsync( a.bad, 0xff, sizeof( unsigned long long ), up ) );
+	HIPCHK( rma::dbtext_directory( a, d_scan_tmp, &scan_tmp, up ) );
+	HIPCHK( rma::dbtext_check( a, up ) );
+	HIPCHK( hipEventRecord( t0.get(), up ) );
+	HIPCHK( rma::dbtext_fill( a, up ) );
+	HIPCHK( hipEventRecord( t1.get(), up ) );
+	HIPCHK( hipMemcpyAsync( &bad, a.bad, sizeof( bad ), hipMemcpyDeviceToHost, up ) );
+	HIPCHK( hipStreamSynchronize( up ) );
+	b.idle = true;
+	if( bad != rma::DT_BAD_NONE ){
+		const int32_t	e = rma::dbtext_bad_entry( bad );
+		const int64_t	have = exc_off[ e + 1 ] - exc_off[ e ];
+		if( rma::dbtext_bad_kind( bad ) == rma::DT_BAD_COUNT )
+			snprintf( err, errlen, "%s: entry %d: its mask has %u bases set, its exceptions are %lld", who, e, rma::dbtext_bad_value( bad ), ( long long )have );
+		else{
+			int64_t	k = 0;
+			while( k + 1 < have && rma::dbtext_exc_letter( static_cast<unsigned char>( exc[ exc_off[ e ] + k ] ) ) )
+				k++;
+			snprintf( err, errlen, "%s: entry %d: exception %lld is byte 0x%02x: a lower-case letter other than a, c, g and t stands at a masked position",
+				who, e, ( long long )k, static_cast<unsigned char>( exc[ exc_off[ e ] + k ] ) );
+		}
+		return 1;
+	}
+	float	ms = -1.0f;
+	if( hipEventElapsedTime( &ms, t0.get(), t1.get() ) != hipSuccess ){
+		( void )hipGetLastError();
+		ms = -1.0f;
+	}
+	// from here on it is a rma_db_create_device() database of the readers' letters over its own text
+	int64_t	lo = text_bytes, hi = 0;
+	for( size_t i = 0; i < nn; i++ )
+		if( db->h_slen[ i ] > 0 ){
+			lo = std::min( lo, start[ i ] );
+			hi = std::max( hi, start[ i ] + db->h_slen[ i ] );
+		}
+	HIPCHK( hipEventRecord( db->ready.get(), up ) );
+	db->h_text_start = std::move( start );
+	db->text = a.text;
+	db->text_bytes = text_bytes;
+	db->text_lo = lo;
+	db->text_hi = hi;
+	db->d_text_start = d_start;
+	db->default_table = true;
+	db->text_fill_ms = ms;
+	db->text_blk = b.text;
+	b.text = Block{};
+	std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
+	g_device_dbs.insert( db );
+	return 0;
+}
+
+extern "C" int rma_db_text_attach( rma_db_t *db, const char *exc, const int64_t *exc_off, void *stream, char *err, size_t errlen )
+{
+	return db_text_attach( "rma_db_text_attach", db, exc, exc_off, stream, err, errlen );
+}
+
+extern "C" int rma_db_text_attach_pack( rma_db_t *db, const rma_pack_t *pk, const int32_t *entry, int32_t first, void *stream,
+	char *err, size_t errlen )
+{
+	const char	*who = "rma_db_text_attach_pack";
+	if( db == nullptr || !is_live_db( db ) ){
+		snprintf( err, errlen, "%s: the database (%p) has been destroyed or was never made", who, static_cast<const void *>( db ) );
+		return 1;
+	}
+	const rma::PackFile	&pf = *rma_pack_file( pk );
+	const int32_t	n = db->n_seq;
+	// the exceptions of the named entries, one after the other
+	std::vector<char>	exc;
+	std::vector<int64_t>	exc_off( size_t( n ) + 1, 0 );
+	std::vector<std::string>	sids( static_cast<size_t>( n ) ), sdefs( static_cast<size_t>( n ) );
+	for( int32_t i = 0; i < n; i++ ){
+		const int64_t	e = entry != nullptr ? int64_t( entry[ i ] ) : int64_t( first ) + i;
+		if( e < 0 || e >= pf.count() ){
+			snprintf( err, errlen, "%s: entry %d of the database is entry %lld of the pack, which has %d entries", who, i, ( long long )e, pf.count() );
+			return 1;
+		}
+		if( pf.slen[ size_t( e ) ] != db->h_slen[ size_t( i ) ] ){
+			snprintf( err, errlen, "%s: entry %d of the database has %d bases, entry %lld of the pack %d", who, i, db->h_slen[ size_t( i ) ],
+				( long long )e, pf.slen[ size_t( e ) ] );
+			return 1;
+		}
+		const int64_t	x0 = pf.exc_off[ size_t( e ) ], x1 = e + 1 < pf.count() ? pf.exc_off[ size_t( e ) + 1 ] : int64_t( pf.exc.size() );
+		if( x0 < 0 || x1 < x0 || x1 > int64_t( pf.exc.size() ) ){
+			snprintf( err, errlen, "%s: entry %lld of the pack: exceptions [%lld, %lld) of %zu", who, ( long long )e, ( long long )x0, ( long long )x1, pf.exc.size() );
+			return 1;
+		}
+		exc.insert( exc.end(), pf.exc.begin() + x0, pf.exc.begin() + x1 );
+		exc_off[ size_t( i ) + 1 ] = int64_t( exc.size() );
+		sids[ size_t( i ) ] = pf.sid( int( e ) );
+		sdefs[ size_t( i ) ] = pf.sdef( int( e ) );
+	}
+	exc.push_back( 0 );		// (never null: a pack without exceptions still has its counts checked)
+	if( db_text_attach( who, db, exc.data(), exc_off.data(), stream, err, errlen ) )
+		return 1;
+	db->sids = std::move( sids );
+	db->sdefs = std::move( sdefs );
+	return 0;
+}
+
+extern "C" int rma_db_read_text( const rma_db_t *db, int32_t i, char *buf, char *err, size_t errlen )
+{
+	if( db == nullptr || !rma::is_device_db( db ) ){
+		snprintf( err, errlen, "rma_db_read_text: the database (%p) has no text in device memory or has been destroyed", static_cast<const void *>( db ) );
+		return 1;
+	}
+	if( i < 0 || i >= db->n_seq ){
+		snprintf( err, errlen, "rma_db_read_text: entry %d of %d", i, db->n_seq );
+		return 1;
+	}
+	HIPCHK( hipSetDevice( db->device ) );
+	HIPCHK( hipEventSynchronize( db->ready.get() ) );
+	if( db->h_slen[ size_t( i ) ] > 0 )
+		HIPCHK( hipMemcpy( buf, db->text + db->h_text_start[ size_t( i ) ], size_t( db->h_slen[ size_t( i ) ] ), hipMemcpyDeviceToHost ) );
+	return 0;
+}
+
+extern "C" float rma_db_text_fill_ms( const rma_db_t *db ) { return db != nullptr ? db->text_fill_ms : -1.0f; }
+
 extern "C" int32_t rma_db_entries( const rma_db_t *db ) { return db->n_seq; }
 
 extern "C" void rma_fasta_device_shape( int32_t shape[ 3 ] )
@@ -939,6 +1184,7 @@ extern "C" void rma_db_destroy( rma_db_t *db )
 	{
 		std::lock_guard<std::mutex>	lk( g_device_dbs_mu );
 		g_device_dbs.erase( db );
+		g_live_dbs.erase( db );
 	}
 	( void )hipSetDevice( db->device );
 	// scans of this database that were begun and not ended: their kernels read it

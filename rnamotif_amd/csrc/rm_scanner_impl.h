@@ -163,7 +163,10 @@ struct rma_db {
 	const uint8_t	*d_table = nullptr;
 	bool	default_table = true;
 	// rma_db_create_device_fasta: the clean text is the database's own, and the entries have names
+	// rma_db_text_attach: the same for a database of packed words -- text_blk holds the text made from them (rm_dbtext.h)
+	// and, behind it, d_text_start; text_fill_ms is what the fill kernel took
 	rma::Block	text_blk;
+	float	text_fill_ms = -1.0f;
 	std::vector<std::string>	sids, sdefs;
 	int32_t	n_seq = 0, max_slen = 0;
 	int64_t	total_bases = 0, sum_slen = 0;
